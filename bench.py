@@ -23,7 +23,9 @@ quoted on:
                 ranks: the history-free half of a frame (detector, extraction, stereo matching: > 95 % of its time) runs on whichever rank
                 the frame is dealt to, one all-to-all per time block hands the results to the rank that owns the sequence, where the
                 recurrence runs frame by frame (a sequence cannot be cut: boxTrack's ids depend on its whole history); strong scaling
-The non-default single-GPU workloads are also run (short) by the default invocation and reported under "extra".
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps of the workload and prints its line.  With --full the
+non-default single-GPU workloads are also run (short) and reported under "extra", beside the per-kernel pass (roofline), the CPU baseline and
+the vocabulary broadcast.  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
 
 Multi-GPU: one process per GPU.  `python bench.py --gpus N` without a torch.distributed environment starts the N ranks
 itself (child processes, before anything touches the GPU); under `python -m torch.distributed.run` it joins the given
@@ -31,7 +33,7 @@ world.  Lanes are independent: no data-path collective (kitti-batch: one all-to-
 Per step: asynchronous gather (to rank 0) of the per-frame result records (N, N_s, keypoints, descriptors, uRight, depth,
 boxes / box_idx / box_status), overlapped with the next step.  value = frames of ALL ranks / max rank time.
 
-Prints ONE compact JSON line (< 4 KB) on rank 0; the full record (per-kernel tables, the extras' rooflines) goes to bench_detail.json.
+Prints ONE compact JSON line (< 4 KB) on rank 0; with --full the full record (per-kernel tables, the extras' rooflines) goes to bench_detail.json.
 """
 import argparse
 import json
@@ -324,19 +326,70 @@ def colour_from_gray(gray, rng):
     return np.stack([np.clip(g + dr, 0, 255), g, np.clip(g + db, 0, 255)], axis=-1).astype(np.uint8)
 
 
-def synth_timestep(synth, kind, cfg, seq, t, cut=120):
+def synth_timestep(synth, kind, cfg, seq, t, cut=120, cache=None):
     """One frame of one synthetic sequence (a sequence stays inside its texture canvas for ~128 frames: scene cut every `cut`).
-    -> dict(images (ipl, H, W, 3) u8, depth (H, W) u16 or None, boxes (k, 4) f64, mask (H, W) u8 or None, stamp)."""
+    -> dict(images (ipl, H, W, 3) u8, depth (H, W) u16 or None, boxes (k, 4) f64, mask (H, W) u8 or None, stamp).
+    cache: a dict private to ONE sequence and one thread of work, which keeps the sequence's texture canvas between calls (synth's own
+    cache holds one canvas for all callers, so a loop over several sequences rebuilds it every frame); the frame is the same bits either way."""
     s, tt = seq + 1000 * (t // cut), t % cut
     rng = np.random.Generator(np.random.PCG64(7919 * seq + t))
     stamp = t / float(cfg["fps"])
     rows = synth.boxes_for_frame(s, tt, cfg)
+    W, H = cfg["width"], cfg["height"]
     if kind == "stereo":
-        left, right, _ = synth.stereo_frame_dyn(s, tt, cfg)
+        if cache is None:
+            left, right, _ = synth.stereo_frame_dyn(s, tt, cfg)
+        else:                                   # synth.stereo_frame_dyn step by step, with the canvas and the disparity map kept
+            if cache.get("key") != (s, W, H):
+                cache.clear()
+                cache.update(key=(s, W, H), tex=synth.base_texture(W, H, s), disp=synth.disparity_map(W, H, s))
+            left = synth.paste_objects(synth.cut_frame(cache["tex"], W, H, tt, cfg["cx"], cfg["cy"]), rows, s)
+            right = synth.warp_right(left, cache["disp"])
         return dict(images=np.stack([colour_from_gray(left, rng), colour_from_gray(right, rng)]), depth=None,
                     boxes=synth.rows_to_rects(rows), mask=None, stamp=stamp)
-    rgb, depth, _ = synth.rgbd_frame_dyn(s, tt, cfg)
-    return dict(images=rgb[None], depth=depth, boxes=synth.rows_to_rects(rows), mask=synth.mask_from_boxes(rows, cfg["width"], cfg["height"]), stamp=stamp)
+    if cache is None:
+        rgb, depth, _ = synth.rgbd_frame_dyn(s, tt, cfg)
+    else:                                       # synth.rgbd_frame_dyn with the sequence's own canvas cache
+        rgb, depth, _ = synth.rgbd_frame(s, tt, cfg, _cache=cache)
+        gray = synth.paste_objects(rgb[:, :, 1].copy(), rows, s)
+        changed = gray != rgb[:, :, 1]
+        for c in range(3):
+            rgb[:, :, c][changed] = gray[changed]
+    return dict(images=rgb[None], depth=depth, boxes=synth.rows_to_rects(rows), mask=synth.mask_from_boxes(rows, W, H), stamp=stamp)
+
+
+def _synth_sequence(kind, cfg, seq, ts):
+    """Worker of synth_frames (a fresh interpreter that never touches the GPU): frames ts of sequence seq."""
+    synth = graft.load_package().synth
+    cache = {}
+    return [synth_timestep(synth, kind, cfg, seq, t, cache=cache) for t in ts]
+
+
+def synth_frames(synth, kind, cfg, seqs, ts, chunk=8):
+    """Yields, time step by time step of ts, [synth_timestep(..., seq, t) for seq in seqs].  Host generation is most of a run's set-up
+    (~0.1 s per KITTI frame, 8 sequences per time step), so the sequences are generated side by side in worker processes, `chunk` time
+    steps per task, the next chunk under way while the caller consumes this one.  The workers are fresh interpreters (spawn, not fork:
+    the caller may hold the GPU) that import numpy and the synthetic generator only."""
+    ts, seqs = list(ts), list(seqs)
+    workers = min(len(seqs), usable_cpus())
+    main_file = getattr(sys.modules["__main__"], "__file__", None)      # a spawned worker re-imports the caller's main script: it must be a file
+    if workers < 2 or len(ts) * len(seqs) < 16 or (main_file is not None and not os.path.isfile(main_file)):
+        caches = [{} for _ in seqs]
+        for t in ts:
+            yield [synth_timestep(synth, kind, cfg, q, t, cache=c) for q, c in zip(seqs, caches)]
+        return
+    import multiprocessing
+    from concurrent.futures import ProcessPoolExecutor
+    chunks = [ts[i:i + chunk] for i in range(0, len(ts), chunk)]
+    with ProcessPoolExecutor(workers, mp_context=multiprocessing.get_context("spawn")) as ex:
+        submit = lambda c: [ex.submit(_synth_sequence, kind, cfg, q, c) for q in seqs]
+        pending = submit(chunks[0])
+        for i, c in enumerate(chunks):
+            nxt = submit(chunks[i + 1]) if i + 1 < len(chunks) else None
+            got = [f.result() for f in pending]
+            for j in range(len(c)):
+                yield [g[j] for g in got]
+            pending = nxt
 
 
 # --------------------------------------------------------------------------- CPU baseline (oracle; rank 0, N=1 only)
@@ -584,8 +637,7 @@ class Workload:
         reps = (S + D - 1) // D
         self.n_total += n_steps
         base = len(self.frames)
-        for t in range(base, min(base + n_steps, self.max_resident)):
-            per = [synth_timestep(synth, self.kind, cfg, 10 + 37 * self.rank + d, t) for d in range(D)]
+        for per in synth_frames(synth, self.kind, cfg, [10 + 37 * self.rank + d for d in range(D)], range(base, min(base + n_steps, self.max_resident))):
             img = torch.from_numpy(np.stack([p["images"] for p in per])).to(self.dev)                  # [D, ipl, H, W, 3]
             img = img.repeat((reps, 1, 1, 1, 1))[:S].contiguous()
             dep = None
@@ -990,7 +1042,7 @@ class SequenceBatchWorkload:
             self.det.close()
 
 
-def run_sequence_batch(args, rank, world, dev, pkg, dist, detector=True):
+def run_sequence_batch(args, rank, world, dev, pkg, dist, detector=True, headline=False):
     """kitti-batch on this rank -> (result dict on rank 0, workload object)."""
     import torch
     fe = pkg.frontend
@@ -1016,6 +1068,7 @@ def run_sequence_batch(args, rank, world, dev, pkg, dist, detector=True):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = max_over_ranks(dist, time.perf_counter() - t0, dev)
+    dumped = dump_outputs(wl, res, args.dump_outputs) if (headline and args.dump_outputs and rank == 0) else None
     out = None
     if rank == 0:
         frames = wl.total_frames_all_ranks
@@ -1027,6 +1080,8 @@ def run_sequence_batch(args, rank, world, dev, pkg, dist, detector=True):
                "max_detector_boxes_in_a_frame": wl.max_det_boxes if wl.det is not None else None,
                "lane0_last_frame": {"N": R.N, "N_s": R.N_s, "N_d": R.N_d, "n_boxes": R.n_boxes, "track_flag": R.track_flag, "separate_ret": R.separate_ret,
                                     "n_track_matches": R.n_track_matches, "n_last_matches": R.n_last_matches}}
+        if dumped is not None:
+            out["dumped"] = dumped
         if gatherer is not None:
             rec = gatherer.recv[world - 1].view(wl.S, layout["_stride"])[0].cpu().numpy()
             d = decode_record(rec, layout, cap)
@@ -1063,17 +1118,78 @@ def make_gatherer(wl, fe, dist, world, rank, dev):
     return gatherer, rec_parts, layout
 
 
+DUMP_LIMIT = 64 << 20          # bytes --dump-outputs may write in all
+DUMP_SEED = 20240611           # the lane sample of the per-keypoint arrays
+DUMP_LANE_FIELDS = ("frame_id", "ref_frame_id", "track_flag", "separate_ret", "n_track_matches", "n_track_pairs", "n_h", "n_f", "n_last_matches",
+                    "N", "N_s", "N_d", "n_boxes")
+
+
+def dump_lanes(n_lanes, cap, max_lanes=32):
+    """The fixed, seeded sample of lanes whose keypoints --dump-outputs writes (sorted lane indices), small enough for DUMP_LIMIT."""
+    per_lane = cap * (7 + 32 + 2) * 4
+    k = max(1, min(max_lanes, n_lanes, (DUMP_LIMIT // 2) // per_lane))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_lanes, k, replace=False))
+
+
+def dump_outputs(wl, res, out_dir):
+    """--dump-outputs DIR: what the timed path handed its caller in the last timed step, as DIR/<name>.npy in float32 / float64.
+    Every lane: the sd_lane_result fields (lane_<field>) and the frame's boxes (box_objects = cv::Rect2d x, y, w, h; box_idx; box_status;
+    zero beyond n_boxes).  The lanes of dump_lanes(): the Frame members mvKeys (x, y, size, angle, response, octave, class_id), mDescriptors
+    (one value per byte), mvuRight and mvDepth, zero beyond the lane's N.  tum-mask also writes the dense cloud (counts of every lane, the
+    points of the first four sampled lanes: x, y, z, b, g, r, a).  -> {name: shape}."""
+    batch, S, cap, M = wl.batch, wl.S, wl.batch.cap, wl.fe.MAXB
+    arrays = {"lane_" + f: np.array([getattr(res[l], f) for l in range(S)], np.float64) for f in DUMP_LANE_FIELDS}
+    nb = arrays["lane_n_boxes"].astype(np.int64)
+    keep = np.arange(M)[None, :] < nb[:, None]
+    arrays["box_objects"] = np.array([[list(o) for o in res[l].objects] for l in range(S)], np.float64) * keep[:, :, None]
+    arrays["box_idx"] = np.array([list(res[l].box_idx) for l in range(S)], np.float64) * keep
+    arrays["box_status"] = np.array([list(res[l].box_status) for l in range(S)], np.float64) * keep
+    lanes = dump_lanes(S, cap)
+    kps = np.zeros((len(lanes), cap, 7), np.float32)
+    descs = np.zeros((len(lanes), cap, 32), np.float32)
+    urs = np.zeros((len(lanes), cap), np.float32)
+    deps = np.zeros((len(lanes), cap), np.float32)
+    for i, l in enumerate(lanes):
+        slot = res[l].cur_slot
+        kp, desc, _ = batch.download(slot)
+        n = len(kp)
+        for j, f in enumerate(kp.dtype.names):
+            kps[i, :n, j] = kp[f]
+        descs[i, :n] = desc
+        ur, dep = batch.download_rgbd(slot)
+        urs[i, :n], deps[i, :n] = ur[:n], dep[:n]
+    arrays.update(dump_lanes=lanes.astype(np.float64), keypoints=kps, descriptors=descs, uright=urs, depth=deps)
+    if getattr(wl, "cloud", False):
+        wl.torch.cuda.synchronize()
+        cnt = wl.d_cnt.cpu().numpy()
+        arrays["cloud_counts"] = cnt.astype(np.float64)
+        pts = wl.d_pts[lanes[:4]].cpu().numpy().view(wl.fe.CLOUD_POINT_DTYPE)[..., 0]
+        cp = np.zeros(pts.shape + (7,), np.float32)
+        for j, f in enumerate(pts.dtype.names):
+            cp[..., j] = pts[f]
+        cp *= (np.arange(pts.shape[1])[None, :] < cnt[lanes[:4], 0][:, None])[:, :, None]
+        arrays["cloud_points"] = cp
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def run_workload(name, args, rank, world, dev, pkg, dist, headline, vocab=None):
     """-> dict with the measured figures of one workload (rank 0 fills everything, other ranks only take part)."""
     import torch
     fe = pkg.frontend
     if name == "kitti-batch":
-        return run_sequence_batch(args, rank, world, dev, pkg, dist, detector=not args.kitti_no_detector)
+        return run_sequence_batch(args, rank, world, dev, pkg, dist, detector=not args.kitti_no_detector, headline=headline)
     wl = Workload(name, args, rank, world, dev, pkg, dist, vocab=vocab)
     # extras: the detector-less workloads step in 2 - 5 ms, so 12 steps would be a 30 ms sample (one allocator hiccup moved `rgbd` by a quarter);
     # they run 5 x as many steps behind 3 warm-up steps
     steps, warm = (args.steps, args.warmup) if headline else ((args.extra_steps, 1) if name.startswith("stereo-yolo") else (5 * args.extra_steps, 3))
-    prof_steps = 4 if (not args.no_profile and (headline or name in ("stereo", "rgbd-bow", "stereo-yolo-f32w", "stereo-yolo-f32x3"))) else 0
+    # the per-kernel pass (roofline) belongs to --full: a plain run times its steps and nothing else
+    prof_steps = 4 if (args.full and not args.no_profile and (headline or name in ("stereo", "rgbd-bow", "stereo-yolo-f32w", "stereo-yolo-f32x3"))) else 0
     # every timed step enqueues ONE detector pass `depth` frames ahead: the run needs that many frames beyond the last timed / profiled step, or the
     # last timed steps would find nothing left to enqueue and the timed region would hold fewer passes than steps
     wl.prepare(1 + warm + steps + prof_steps + max(1, getattr(wl, "depth", 1)) + (2 if getattr(wl, "pipelined", False) else 0))
@@ -1104,6 +1220,7 @@ def run_workload(name, args, rank, world, dev, pkg, dist, headline, vocab=None):
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = max_over_ranks(dist, time.perf_counter() - t0, dev)
+    dumped = dump_outputs(wl, res, args.dump_outputs) if (headline and args.dump_outputs and rank == 0) else None
 
     out = None
     if rank == 0:
@@ -1115,6 +1232,8 @@ def run_workload(name, args, rank, world, dev, pkg, dist, headline, vocab=None):
                "max_detector_boxes_in_a_frame": wl.max_det_boxes if wl.det is not None else None,
                "lane0_last_frame": {"N": R.N, "N_s": R.N_s, "N_d": R.N_d, "n_boxes": R.n_boxes, "track_flag": R.track_flag, "separate_ret": R.separate_ret,
                                     "n_track_matches": R.n_track_matches, "n_last_matches": R.n_last_matches}}
+        if dumped is not None:
+            out["dumped"] = dumped
         if gatherer is not None:               # rank 0 decodes a record it received from the LAST rank: the gather carries usable data
             rec = gatherer.recv[world - 1].view(wl.S, layout["_stride"])[0].cpu().numpy()
             d = decode_record(rec, layout, cap)
@@ -1265,6 +1384,32 @@ WORKLOAD_TEXT = {
 }
 
 
+def share_vocabulary(fe, synth, rank, dist, dev):
+    """The packed vocabulary built on rank 0 and broadcast to every rank -> (Vocabulary, packed bytes, broadcast ms or None)."""
+    import torch
+    voc_ms = None
+    if rank == 0:
+        voc0 = fe.Vocabulary.from_nodes(synth.vocabulary(k=10, L=6, seed=1234))
+        vptr, voc_bytes = voc0.packed_device()
+        n_nodes_t = torch.tensor([voc0.info()["n_nodes"]], dtype=torch.int64, device=dev)
+    else:
+        n_nodes_t = torch.zeros(1, dtype=torch.int64, device=dev)
+    if dist is not None:
+        dist.broadcast(n_nodes_t, src=0)
+        voc_bytes = fe.Vocabulary.packed_bytes(int(n_nodes_t.item()))
+        voc_buf = fe.as_torch_u8(vptr, voc_bytes) if rank == 0 else torch.empty((voc_bytes,), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        dist.broadcast(voc_buf, src=0)
+        torch.cuda.synchronize()
+        voc_ms = (time.perf_counter() - t0) * 1e3
+        vocab = voc0 if rank == 0 else fe.Vocabulary.from_packed_device(voc_buf.data_ptr(), voc_bytes)
+    else:
+        vocab = voc0
+    assert vocab.info()["n_nodes"] == int(n_nodes_t.item()) and vocab.info()["k"] == 10 and vocab.info()["L"] == 6
+    return vocab, voc_bytes, voc_ms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1273,7 +1418,12 @@ def main():
     ap.add_argument("--lanes", "--batch", type=int, default=256, dest="lanes", help="independent camera streams per GPU = frames per step per GPU")
     ap.add_argument("--distinct", type=int, default=8, help="distinct synthetic sequences generated on the host (replicated over the lanes on the device)")
     ap.add_argument("--workload", choices=WORKLOADS, default="stereo-yolo")
-    ap.add_argument("--extra", default="auto", help="comma-separated workloads also run (short) and reported under 'extra'; 'auto' = " + ",".join(AUTO_EXTRAS) + " at N=1, none otherwise; 'none'")
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: the extra workloads, the per-kernel pass "
+                    "(roofline), the CPU baseline, the vocabulary broadcast, and write the full record (--detail); a plain run sets up, warms up, "
+                    "times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the timed path computed in its last timed step to DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB; see dump_outputs), e.g. bench_outputs/ (git-ignored)")
+    ap.add_argument("--extra", default="auto", help="with --full: comma-separated workloads also run (short) and reported under 'extra'; 'auto' = " + ",".join(AUTO_EXTRAS) + " at N=1, none otherwise; 'none'")
     ap.add_argument("--extra-steps", type=int, default=12)
     ap.add_argument("--kitti-frames", type=int, default=256)
     ap.add_argument("--kitti-sequences", type=int, default=11, help="kitti-batch: sequences of the job (BASELINE configs[4]: KITTI 00-10 = 11)")
@@ -1282,11 +1432,13 @@ def main():
     ap.add_argument("--kitti-no-detector", action="store_true", help="kitti-batch with the 3 given boxes per frame instead of the detector")
     ap.add_argument("--det-split", type=int, default=1, help="sub-batches the detector processes a step's images in, each on its own stream "
                     "(measured on MI355X: 1 -> 995.5, 2 -> 995.1, 4 -> 989.7 frames/s: the convolutions' drain phases are not worth filling)")
-    ap.add_argument("--cpu-budget", type=float, default=25.0, help="seconds of host time for the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--detail", default="bench_detail.json", help="file (next to bench.py, and under gpurun_out/ when present) that receives the FULL record; "
+    ap.add_argument("--cpu-budget", type=float, default=25.0, help="with --full: seconds of host time for the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--detail", default="bench_detail.json", help="with --full: file next to bench.py (see write_detail) that receives the FULL record; "
                     "the printed line is its compact form")
-    ap.add_argument("--no-profile", action="store_true", help="skip the separate per-kernel pass (no roofline block)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the separate per-kernel pass (no roofline block)")
     args = ap.parse_args()
+    if not args.full and args.extra not in ("auto", "none"):
+        raise SystemExit("--extra runs workloads beside the headline: it needs --full")
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:                    # start the ranks ourselves, before anything touches the GPU
@@ -1332,35 +1484,19 @@ def main():
 
     # ---- start-up collective: the packed ORB vocabulary (synthetic k=10, L=6 tree in ORBvoc.txt's shape; the real file
     # is a download that never was in the reference), rank 0 -> all over RCCL; every rank adopts the received buffer.
-    voc_ms = None
-    if rank == 0:
-        voc0 = fe.Vocabulary.from_nodes(synth.vocabulary(k=10, L=6, seed=1234))
-        vptr, voc_bytes = voc0.packed_device()
-        n_nodes_t = torch.tensor([voc0.info()["n_nodes"]], dtype=torch.int64, device=dev)
-    else:
-        n_nodes_t = torch.zeros(1, dtype=torch.int64, device=dev)
-    if dist is not None:
-        dist.broadcast(n_nodes_t, src=0)
-        voc_bytes = fe.Vocabulary.packed_bytes(int(n_nodes_t.item()))
-        voc_buf = fe.as_torch_u8(vptr, voc_bytes) if rank == 0 else torch.empty((voc_bytes,), dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        dist.broadcast(voc_buf, src=0)
-        torch.cuda.synchronize()
-        voc_ms = (time.perf_counter() - t0) * 1e3
-        vocab = voc0 if rank == 0 else fe.Vocabulary.from_packed_device(voc_buf.data_ptr(), voc_bytes)
-    else:
-        vocab = voc0
-    assert vocab.info()["n_nodes"] == int(n_nodes_t.item()) and vocab.info()["k"] == 10 and vocab.info()["L"] == 6
+    # Only rgbd-bow consumes it: a plain run of another workload leaves it out.
+    vocab = voc_bytes = voc_ms = None
+    if args.full or args.workload == "rgbd-bow":
+        vocab, voc_bytes, voc_ms = share_vocabulary(fe, synth, rank, dist, dev)
 
     head, wl = run_workload(args.workload, args, rank, world, dev, pkg, dist, headline=True, vocab=vocab)
     extras = {}
-    names = []
-    if args.extra == "auto":
+    names = []                                        # a plain run: the headline alone
+    if args.full and args.extra == "auto":
         # the other BASELINE configs (configs[1] rgbd, configs[3] tum-mask, configs[4] kitti-batch), the detector-less stereo front end (the HBM-side
         # kernel table) and the two other f32-class detector chains (value_f32x3, value_f32w); every other workload only on request (--extra a,b,c)
         names = [w for w in AUTO_EXTRAS if w != args.workload] if world == 1 else []
-    elif args.extra != "none":
+    elif args.full and args.extra != "none":
         names = [w for w in args.extra.split(",") if w]
     for w in names:
         if w not in WORKLOADS:
@@ -1387,7 +1523,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and args.cpu_budget > 0:
+        if args.full and world == 1 and args.cpu_budget > 0:
             P_SENSOR = {"stereo": 1, "rgbd": 2}[wl.kind]
             cpu = cpu_baseline(args.workload, wl.cfg, wl.kind, P_SENSOR, wl.with_boxes or wl.detector, wl.detector, pkg, budget_s=args.cpu_budget)
             nthr = max(1, min(usable_cpus(), 64))
@@ -1419,7 +1555,10 @@ def main():
                 out["config"][k] = head[k]
         if "gathered_record_check" in head:
             out["gathered_record_check"] = head["gathered_record_check"]
-        out["vocabulary"] = {"nodes": vocab.info()["n_nodes"], "words": vocab.info()["n_words"], "packed_bytes": int(voc_bytes)}
+        if vocab is not None:
+            out["vocabulary"] = {"nodes": vocab.info()["n_nodes"], "words": vocab.info()["n_words"], "packed_bytes": int(voc_bytes)}
+        if "dumped" in head:
+            out["dumped"] = {"dir": args.dump_outputs, "arrays": head["dumped"]}
         if voc_ms is not None:
             out["vocabulary_broadcast_ms"] = round(voc_ms, 3)
         x3 = extras.get("stereo-yolo-f32x3")
@@ -1433,7 +1572,7 @@ def main():
             # ... and with the 3 x 3 stride-1 layers as Winograd F(2x2, 3x3) in f32: the mode CLOSEST to a float64 forward of the three (same test)
             out["value_f32w"] = xw["value"]
             out["dtype_f32w"] = "u8+f32, Winograd F(2x2,3x3) on the 3x3 stride-1 layers"
-        detail = write_detail(out, args.detail)
+        detail = write_detail(out, args.detail) if args.full else None
         print(compact_line(out, detail))
         sys.stdout.flush()
     if dist is not None:

@@ -199,6 +199,31 @@ def test_bench_pingpong_index_keeps_neighbours():
     assert [bench.pingpong_index(t, 1) for t in range(4)] == [0, 0, 0, 0]
 
 
+def test_bench_frame_generation_is_the_synthetic_sequence(synth):
+    """Workload.prepare generates its frames through synth_frames (worker processes, a canvas cache per sequence): every frame must be the
+    bits synth_timestep gives without a cache -- across a scene cut, for both sensors."""
+    def same(a, b):
+        return all((a[k] is None and b[k] is None) or np.array_equal(a[k], b[k]) for k in ("images", "depth", "boxes", "mask")) and a["stamp"] == b["stamp"]
+    for kind, cfg in (("stereo", synth.KITTI_STEREO), ("rgbd", synth.KITTI03_RGBD), ("rgbd", synth.TUM3)):
+        cache = {}
+        for seq, t in ((10, 0), (10, 1), (10, 119), (10, 120), (11, 3), (10, 4)):
+            assert same(bench.synth_timestep(synth, kind, cfg, seq, t), bench.synth_timestep(synth, kind, cfg, seq, t, cache=cache)), (kind, seq, t)
+    seqs, ts = [10, 47], list(range(116, 124))                  # 16 frames: the worker-process path whenever two CPUs are usable
+    got = list(bench.synth_frames(synth, "stereo", synth.KITTI_STEREO, seqs, ts, chunk=3))
+    assert len(got) == len(ts)
+    for t, per in zip(ts, got):
+        assert all(same(p, bench.synth_timestep(synth, "stereo", synth.KITTI_STEREO, q, t)) for q, p in zip(seqs, per)), t
+
+
+def test_bench_dump_lane_sample_is_fixed_and_bounded():
+    """--dump-outputs: the sampled lanes are the same in every run, distinct, sorted, and their per-keypoint arrays fit the byte limit."""
+    a, b = bench.dump_lanes(256, 4000), bench.dump_lanes(256, 4000)
+    assert np.array_equal(a, b) and len(np.unique(a)) == len(a) == 32 and np.all(np.diff(a) > 0) and a.max() < 256
+    assert list(bench.dump_lanes(3, 4000)) == [0, 1, 2]
+    for cap in (2000, 10000, 100000):
+        assert len(bench.dump_lanes(256, cap)) * cap * (7 + 32 + 2) * 4 <= bench.DUMP_LIMIT // 2
+
+
 def test_sequence_batch_block_plan():
     """configs[4]: whole sequences per rank (11 over 8 ranks: at most 2 per rank), and blocks of D consecutive frames per owned sequence so that one
     detector / extraction batch holds >= 64 frames whatever the rank count."""

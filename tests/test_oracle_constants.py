@@ -1,12 +1,12 @@
 """Known-answer material the reference source holds for this path: the rBRIEF pattern,
 thresholds, and the tables the ORBextractor constructor derives.  Pins the oracle AND the C ABI host code."""
+import json
 import os
 import re
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src/ORBextractor.cc"
 
 
 def _inc(path):
@@ -23,21 +23,17 @@ def test_pattern_tables_equal_fixture():
 
 
 def test_pattern_equals_reference_source_when_present():
-    """In this container the reference tree is mounted: the fixture is checked against bit_pattern_31_ itself
-    (src/ORBextractor.cc:150-408).  On the GPU box (no /root/reference) the committed fixture stands in."""
-    if not os.path.exists(REF):
-        return
-    src = open(REF).read()
-    i = src.index("bit_pattern_31_[256*4]")
-    body = src[i:src.index("};", i)]
-    body = re.sub(r"/\*.*?\*/", "", body[body.index("{") + 1:], flags=re.S)
-    ref = np.array([int(x) for x in re.findall(r"-?\d+", body)], np.int32)
+    """The fixtures are the reference's own values: tests/golden/orb_pattern_i8.txt is bit_pattern_31_ (src/ORBextractor.cc:150-408, extracted
+    by tools/gen_pattern.py) and tests/golden/reference_constants.json holds the thresholds ORBextractor.cc:72-74 and ORBmatcher.cc:37-39
+    define.  The oracle must hard-code exactly those thresholds."""
     gold = np.loadtxt(os.path.join(ROOT, "tests/golden/orb_pattern_i8.txt"), dtype=np.int32, comments="#").reshape(-1)
-    assert np.array_equal(ref, gold)
-    # thresholds the oracle hard-codes (ORBextractor.cc:72-74, ORBmatcher.cc:37-39)
-    assert "const int PATCH_SIZE = 31;" in src and "const int HALF_PATCH_SIZE = 15;" in src and "const int EDGE_THRESHOLD = 19;" in src
-    m = open("/root/reference/src/ORBmatcher.cc").read()
-    assert "TH_HIGH = 100" in m and "TH_LOW = 50" in m and "HISTO_LENGTH = 30" in m
+    assert gold.shape == (1024,)
+    consts = json.load(open(os.path.join(ROOT, "tests/golden/reference_constants.json")))["values"]
+    assert consts == {"PATCH_SIZE": 31, "HALF_PATCH_SIZE": 15, "EDGE_THRESHOLD": 19, "TH_HIGH": 100, "TH_LOW": 50, "HISTO_LENGTH": 30}
+    src = open(os.path.join(ROOT, "oracle/sd_oracle.cpp")).read()
+    for name, value in consts.items():
+        found = re.findall(r"\b%s = (\d+)[;,]" % name, src)
+        assert found == [str(value)], "oracle/sd_oracle.cpp: %s = %r, the reference says %d" % (name, found, value)
 
 
 # SURVEY.md section 8a row 2 / Appendix B (computed from ORBextractor.cc:410-446,456-470,1111-1112)

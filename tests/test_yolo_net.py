@@ -1,9 +1,10 @@
-"""Detector network description (no GPU): the built-in YOLOv3 layer list equals the reference's cfg file."""
+"""Detector network description (no GPU): the built-in YOLOv3 layer list equals the reference's cfg file (src/yolo/yolov3.cfg, kept
+verbatim as tests/golden/yolov3.cfg)."""
 import os
 
 import numpy as np
 
-CFG = "/root/reference/src/yolo/yolov3.cfg"
+CFG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "yolov3.cfg")
 
 
 def test_builtin_v3_layers_match_reference_cfg(pkg):
@@ -11,8 +12,6 @@ def test_builtin_v3_layers_match_reference_cfg(pkg):
     assert len(layers) == 107 and (layers["type"] == pkg.yolo.CONV).sum() == 75
     assert (layers["type"] == pkg.yolo.SHORTCUT).sum() == 23 and (layers["type"] == pkg.yolo.YOLO).sum() == 3
     assert anchors.tolist() == [10, 13, 16, 30, 33, 23, 30, 61, 62, 45, 59, 119, 116, 90, 156, 198, 373, 326]
-    if not os.path.exists(CFG):
-        return          # GPU box: the reference tree is absent; the structural asserts above stand in
     ref, ranchors, classes = pkg.yolo.parse_cfg(CFG)
     assert classes == 80 and np.array_equal(ranchors, anchors)
     assert len(ref) == len(layers)

@@ -16,14 +16,14 @@ if [ "$1" = "build" ]; then
   exit 0
 fi
 set -e
-mkdir -p gpurun_out
+# logs and records next to the variants, under build/
 for v in A B C D A B C D; do
   L=$PWD/build/libsd_fast_$v.so
-  SD_FRONTEND_LIB=$L timeout -k 10 120 python -m pytest tests/test_gpu_extract.py -m gpu -x -q > gpurun_out/fast_$v.t.log 2>&1 || { echo "variant $v FAILED parity"; tail -5 gpurun_out/fast_$v.t.log; exit 1; }
-  SD_FRONTEND_LIB=$L timeout -k 10 200 python bench.py --workload stereo --extra none --cpu-budget 0 --detail fast_$v.json > gpurun_out/fast_$v.log 2>&1
+  SD_FRONTEND_LIB=$L timeout -k 10 120 python -m pytest tests/test_gpu_extract.py -m gpu -x -q > build/fast_$v.t.log 2>&1 || { echo "variant $v FAILED parity"; tail -5 build/fast_$v.t.log; exit 1; }
+  SD_FRONTEND_LIB=$L timeout -k 10 200 python bench.py --full --workload stereo --extra none --cpu-budget 0 --detail build/fast_$v.json > build/fast_$v.log 2>&1
   python3 - <<PY
 import json
-j=json.load(open("fast_$v.json")); r=j["roofline"]
+j=json.load(open("build/fast_$v.json")); r=j["roofline"]
 print("$v", j["value"], j["ms_per_step"], "k_fast_cells", r["kernels_ms_per_step"]["k_fast_cells"])
 PY
 done
