@@ -193,6 +193,37 @@ int sd_batch_search_local_map(sd_batch* b, int n_frames, const int32_t* frame_in
                               const sd_camera* cam, float th, float nnratio, float viewing_cos_limit,
                               const uint8_t* d_occupied, sd_track_info* d_track, int32_t* d_point_match,
                               int32_t* d_kp_match, int32_t* d_nmatches, void* stream);
+/* ---- Optimizer::PoseOptimization (src/Optimizer.cc:239-451; the vendored g2o's Levenberg-Marquardt) ----
+ * Pose-only bundle adjustment of many independent frames in one launch, as TrackReferenceKeyFrame, TrackWithMotionModel,
+ * TrackLocalMap and Relocalization call it (src/Tracking.cc:1636,1759,1801,2311).  One edge per frame keypoint i with
+ * mvpMapPoints[i] != NULL, in keypoint order (the edges' insertion order, which orders g2o's sums): xw = pMP->GetWorldPos(),
+ * (u, v) = mvKeysUn[i].pt, ur = mvuRight[i] (< 0: monocular edge, else stereo), inv_sigma2 = mvInvLevelSigma2[mvKeysUn[i].octave],
+ * kp_index = i (carried, not read by the solver). */
+typedef struct sd_pose_edge {
+    float xw[3];
+    float u, v, ur;
+    float inv_sigma2;
+    int32_t kp_index;
+} sd_pose_edge;                                   /* 32 bytes */
+/* Problem p owns edges [d_edge_offset[p], d_edge_offset[p+1]) of d_edges; cams [n_problems] (host): fx, fy, cx, cy, mbf of the
+ * frame; d_Tcw [n_problems][16] row-major f32: pFrame->mTcw in, the optimised pose out (untouched when the problem has fewer than
+ * 3 edges); d_outlier [edges] u8 = mvbOutlier of each edge; d_n_good [n_problems] = the function's return value
+ * (nInitialCorrespondences - nBad).  Asynchronous on `stream`, except that the cameras go through a ring of 8 library-owned device
+ * tables per device: a call waits on the host until the launch that used its table 8 calls earlier on the same device has finished. */
+int sd_pose_optimize_device(int n_problems, const int32_t* d_edge_offset, const sd_pose_edge* d_edges, const sd_camera* cams,
+                            float* d_Tcw, uint8_t* d_outlier, int32_t* d_n_good, void* stream);
+/* The same from host arrays (edge_offset [n_problems + 1], edges, Tcw in / out, outlier, n_good): uploads, runs, synchronises. */
+int sd_pose_optimize_host(int n_problems, const int32_t* edge_offset, const sd_pose_edge* edges, const sd_camera* cams,
+                          float* Tcw, uint8_t* outlier, int32_t* n_good);
+/* PoseOptimization of mCurrentFrame after ORBmatcher::SearchByProjection(mCurrentFrame, mLastFrame, ...) for projection pairs
+ * pair_index[k] (host, k < n_pairs) of the last sd_batch_search_by_projection: the edges are built on the device from the pair's
+ * Current slot (mvKeysUn, mvuRight, octave -> the extractor's mvInvLevelSigma2), its match array (mvpMapPoints) and the Last
+ * slot's map-point table (xw[match[i]]), with the camera the pair was matched with.  Tcw_host (nullable, [n_pairs][16]): the prior;
+ * NULL = the Tcw the pair was matched with.  Results stay per pair: sd_batch_download_pose. */
+int sd_batch_pose_optimize(sd_batch* b, int n_pairs, const int32_t* pair_index, const float* Tcw_host, void* stream);
+/* Tcw[16] = the optimised mTcw (the prior when fewer than 3 edges), outlier [cap] = mvbOutlier per CURRENT keypoint (0 where no
+ * edge), n_initial = nInitialCorrespondences, n_good = the return value. */
+int sd_batch_download_pose(sd_batch* b, int pair, float* Tcw, uint8_t* outlier, int cap, int* n_initial, int* n_good);
 /* ---- vocabulary + bag of words (Thirdparty/DBoW2, src/Frame.cc:803-810, src/ORBmatcher.cc:159-288) ----
  * sd_vocab = ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>): one packed buffer in HBM
  * (header | desc[n][32] | weight[n] f64 | parent[n] | childStart[n+1] | childIdx[n-1] | wordId[n]; node ids and the
@@ -467,6 +498,22 @@ int sd_tracker_discard_prefetched(sd_tracker* t);
  *    run, Tracking.cc:971).  NULL returns to the automatic rule (frame 0, 1 of a lane: neither; later: both). */
 int sd_tracker_set_mappoints(sd_tracker* t, const float* xw, const uint8_t* flags, const int32_t* n);
 int sd_tracker_set_state(sd_tracker* t, const int32_t* state);
+/* Opt-in TrackWithMotionModel tail (src/Tracking.cc:1728-1789), with track_last: after the last-frame matcher the search is repeated
+ * with 2*th for the lanes below 20 matches, a lane still below 20 stops there (ran = 0), the others run PoseOptimization with the Tcw
+ * argument of sd_tracker_track as the prior, count nmatchesMap (non-outlier matches whose mLastFrame point has flag bit1, i.e.
+ * Observations() > 0: 0 in the sharded batch mode, where a frame's own stereo points have no observations) and set
+ * ok = nmatchesMap >= 10.  All of it is enqueued before the step's one synchronisation.  enable = 0 (the default): nothing changes.
+ * The matches stay at pair n_lanes + s; the pose problem of lane s is pair n_lanes + s of sd_batch_download_pose. */
+typedef struct sd_pose_result {
+    float Tcw[16];          /* the optimised mCurrentFrame.mTcw (the prior when ran == 0) */
+    int32_t ran;            /* PoseOptimization ran (nmatches >= 20 after the 2*th retry) */
+    int32_t n_matches;      /* nmatches after the retry (the same as sd_lane_result.n_last_matches) */
+    int32_t n_initial, n_good;      /* nInitialCorrespondences, PoseOptimization's return value */
+    int32_t n_matches_map;  /* nmatchesMap */
+    int32_t ok;             /* TrackWithMotionModel's return value: nmatchesMap >= 10 */
+} sd_pose_result;
+int sd_tracker_set_pose_optimization(sd_tracker* t, int enable);
+int sd_tracker_pose_results(sd_tracker* t, sd_pose_result* results);   /* [n_lanes], of the last sd_tracker_track */
 /* Batch copy of frame slots (Frame's copy constructor, src/Frame.cc:39-63) in one launch: slot src[i] -> dst[i]. */
 int sd_batch_copy_frames(sd_batch* b, int n, const int32_t* src, const int32_t* dst, void* stream);
 

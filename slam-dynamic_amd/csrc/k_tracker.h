@@ -89,6 +89,12 @@ struct SdLaneSummary {
     int box_idx[SD_MAXB], box_status[SD_MAXB], keptOrig[SD_MAXB];
     double boxes[SD_MAXB][4];
 };
+// TrackWithMotionModel's tail (sd_tracker_set_pose_optimization), written by k_pose_lane_summary.  The tracker keeps these behind its
+// lane summaries in the same buffer, so the step's one results copy simply grows by them when the tail ran.
+struct SdPoseSummary {
+    float Tcw[16];
+    int ran, nMatches, nInitial, nGood, nMap, ok;
+};
 
 __global__ void __launch_bounds__(64) k_lane_summary(const SdFrameBoxes* __restrict__ fb, const int* __restrict__ count,
                                                      const SdMotionResult* __restrict__ moRes, const int* __restrict__ sepRet,
@@ -109,5 +115,35 @@ __global__ void __launch_bounds__(64) k_lane_summary(const SdFrameBoxes* __restr
         O.flag = moRes ? moRes[s].flag : 0; O.nH = moRes ? moRes[s].nH : 0; O.nF = moRes ? moRes[s].nF : 0;
         O.sepRet = sepRet[s]; O.nTrackMatches = nmatch[s]; O.nTrackPairs = npairs[s];
         O.nLastMatches = haveLast ? nmatch[nLanes + s] : -1;
+    }
+}
+
+// TrackWithMotionModel after PoseOptimization (src/Tracking.cc:1762-1789) for lane s = pair nLanes + s: nmatchesMap counts the
+// non-outlier matches whose mLastFrame point has Observations() > 0 (flag bit1 of the Last slot's map-point table).
+__global__ void __launch_bounds__(256) k_pose_lane_summary(const sd_pose_edge* __restrict__ edges, const int* __restrict__ first,
+                                                           const int* __restrict__ last, const float* __restrict__ Tcw,
+                                                           const uint8_t* __restrict__ outlier, const int* __restrict__ good,
+                                                           const int* __restrict__ ran, const int* __restrict__ match,
+                                                           const uint8_t* __restrict__ flags, const int2* __restrict__ pairIdx,
+                                                           const int* __restrict__ nmatch, const int* __restrict__ active, int nLanes,
+                                                           int cap, SdPoseSummary* __restrict__ out)
+{
+    __shared__ int nMap;
+    const int s = blockIdx.x, pair = nLanes + s, tid = threadIdx.x;
+    if (tid == 0) nMap = 0;
+    __syncthreads();
+    const int e0 = first[pair], e1 = last[pair];
+    const size_t lst = (size_t)pairIdx[pair].y * cap;
+    int c = 0;
+    for (int i = e0 + tid; i < e1; i += 256)
+        if (!outlier[i]) c += (flags[lst + match[(size_t)pair * cap + edges[i].kp_index]] & 2) ? 1 : 0;
+    if (c) atomicAdd(&nMap, c);
+    __syncthreads();
+    SdPoseSummary& O = out[s];
+    if (tid < 16) O.Tcw[tid] = Tcw[(size_t)pair * 16 + tid];
+    if (tid == 0) {
+        const int r = ran[pair], n = e1 - e0;
+        O.ran = r; O.nMatches = active[s] ? nmatch[pair] : -1; O.nInitial = n; O.nGood = n < 3 ? 0 : good[pair];
+        O.nMap = nMap; O.ok = r && nMap >= 10;
     }
 }

@@ -9,6 +9,7 @@
 #include <cmath>
 #include <string>
 #include <vector>
+#include <mutex>
 #include "k_extract.h"
 #include "k_frame.h"
 #include "k_fast.h"
@@ -16,6 +17,7 @@
 #include "k_cull.h"
 #include "k_tracker.h"
 #include "k_cloud.h"
+#include "k_pose.h"
 #include "sd_common.h"
 #include "sd_vocab.h"
 
@@ -96,6 +98,12 @@ struct sd_batch {
     int* d_npairs = nullptr;
     int* d_nmatch = nullptr;
     float* d_pose = nullptr;        // staging for host poses: [2][maxImages][16]
+    // PoseOptimization per projection pair (sd_batch_pose_optimize), allocated on first use: edges [maxImages][cap], edge ranges,
+    // pose in / out, mvbOutlier per edge, return value, camera, whether it ran; pairCam = the camera each pair was matched with
+    sd_pose_edge* d_poseEdges = nullptr; int* d_poseFirst = nullptr; int* d_poseLast = nullptr; float* d_poseT = nullptr;
+    uint8_t* d_poseOut = nullptr; int* d_poseGood = nullptr; sd_camera* d_poseCam = nullptr; int* d_poseMap = nullptr; int* d_poseRan = nullptr;
+    float* d_poseTin = nullptr;
+    std::vector<sd_camera> pairCam, hPoseCam; std::vector<int32_t> hPoseMap;
     int nPairs = 0;
     int dlPairs = 0;          // pairs sd_batch_download_matches may read (the tracker also keeps pairs at [n_lanes, 2 * n_lanes))
     // dynamic-object cull
@@ -232,7 +240,8 @@ static void batch_free(sd_batch* b)
                     b->d_sepPairs, b->d_kpD, b->d_descD, b->d_urD, b->d_depD, b->d_rowIdx, b->d_rowStart,
                     b->d_lmCand, b->d_lmN, b->d_lmOvf, b->d_lmIdx, b->d_bowWordF, b->d_bowWF, b->d_bowNidF, b->d_fvNode, b->d_fvFeat,
                     b->d_fvRunStart, b->d_fvRunNode, b->d_bowWord, b->d_bowVal, b->d_bowMeta, b->d_bowImg,
-                    b->d_moPts, b->d_moNorm, b->d_moCounts, b->d_moModels, b->d_moMaskH, b->d_moMaskF, b->d_moRes, b->d_pyrExt, b->d_copyPairs, b->d_kpUn, b->d_kpDUn, b->d_unSlots, b->d_cloudBits, b->d_cloudRows, b->d_cloudT, b->d_cloudSlots};
+                    b->d_moPts, b->d_moNorm, b->d_moCounts, b->d_moModels, b->d_moMaskH, b->d_moMaskF, b->d_moRes, b->d_pyrExt, b->d_copyPairs, b->d_kpUn, b->d_kpDUn, b->d_unSlots, b->d_cloudBits, b->d_cloudRows, b->d_cloudT, b->d_cloudSlots,
+                    b->d_poseEdges, b->d_poseFirst, b->d_poseLast, b->d_poseT, b->d_poseOut, b->d_poseGood, b->d_poseCam, b->d_poseMap, b->d_poseRan, b->d_poseTin};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& r : b->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (auto e : b->pool) (void)hipEventDestroy(e);
@@ -1104,6 +1113,8 @@ static int search_by_projection_impl(sd_batch* b, int pairBase, int n_pairs, con
     LAUNCH_CHECK("k_proj_resolve");
     if (pairBase == 0) b->nPairs = n_pairs;
     b->dlPairs = std::max(pairBase + n_pairs, pairBase ? b->dlPairs : 0);
+    if (b->pairCam.size() != (size_t)b->maxImages) b->pairCam.assign(b->maxImages, sd_camera());
+    for (int p = 0; p < n_pairs; p++) b->pairCam[pairBase + p] = *cam;
     return SD_OK;
 }
 
@@ -1647,6 +1658,182 @@ int sd_batch_download_matches(sd_batch* b, int pair, int32_t* match, int32_t* pa
     if (pairs && np > 0) HIPCHK(hipMemcpy(pairs, b->d_pairs + (size_t)pair * b->plan.kpCap * 2, (size_t)np * 8, hipMemcpyDeviceToHost));
     if (npairs) *npairs = np;
     if (nmatches) *nmatches = nm;
+    return SD_OK;
+}
+
+
+// ---------------------------------------------------------------- Optimizer::PoseOptimization (k_pose.h)
+// Plain form: the caller's edges.  The cameras travel through a per-device ring of SD_POSE_CAM_RING library-owned device tables; an
+// event recorded after each launch guards the reuse of its table, so the host waits only when the launch SD_POSE_CAM_RING calls
+// earlier on the same device has not finished yet.
+#define SD_POSE_CAM_RING 8
+#define SD_POSE_MAX_DEVICES 64
+namespace {
+struct PoseCamRing { sd_camera* d[SD_POSE_CAM_RING] = {}; size_t cap[SD_POSE_CAM_RING] = {}; hipEvent_t done[SD_POSE_CAM_RING] = {}; int next = 0; };
+PoseCamRing g_poseCams[SD_POSE_MAX_DEVICES];
+std::mutex g_poseCamsMu;
+}
+
+static int pose_launch(const SdPoseArgs& A, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_pose_optimize, dim3(n), dim3(SD_POSE_THREADS), 0, s, A);
+    LAUNCH_CHECK("k_pose_optimize");
+    return SD_OK;
+}
+
+int sd_pose_optimize_device(int n_problems, const int32_t* d_edge_offset, const sd_pose_edge* d_edges, const sd_camera* cams,
+                            float* d_Tcw, uint8_t* d_outlier, int32_t* d_n_good, void* stream_)
+{
+    if (n_problems < 0 || (n_problems > 0 && (!d_edge_offset || !d_edges || !cams || !d_Tcw || !d_outlier || !d_n_good)))
+        return set_err(SD_ERR_INVALID, "bad pose_optimize arguments");
+    if (n_problems == 0) return SD_OK;
+    hipStream_t s = (hipStream_t)stream_;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the pose camera tables");
+    std::lock_guard<std::mutex> lk(g_poseCamsMu);
+    PoseCamRing& C = g_poseCams[dev];
+    const int k = C.next;
+    if (C.done[k]) HIPCHK(hipEventSynchronize(C.done[k]));     // the launch that last used this table has read it
+    else HIPCHK(hipEventCreateWithFlags(&C.done[k], hipEventDisableTiming));
+    if (C.cap[k] < (size_t)n_problems) {
+        if (C.d[k]) HIPCHK(hipFree(C.d[k]));
+        C.d[k] = nullptr; C.cap[k] = 0;
+        HIPCHK(hipMalloc((void**)&C.d[k], (size_t)n_problems * sizeof(sd_camera)));
+        C.cap[k] = (size_t)n_problems;
+    }
+    HIPCHK(hipMemcpyAsync(C.d[k], cams, (size_t)n_problems * sizeof(sd_camera), hipMemcpyHostToDevice, s));
+    SdPoseArgs A;
+    A.edges = d_edges; A.first = d_edge_offset; A.last = d_edge_offset + 1; A.cam = C.d[k]; A.Tcw = d_Tcw; A.outlier = d_outlier;
+    A.nGood = d_n_good; A.map = nullptr;
+    int rc = pose_launch(A, n_problems, s);
+    if (rc != SD_OK) return rc;
+    HIPCHK(hipEventRecord(C.done[k], s));
+    C.next = (k + 1) % SD_POSE_CAM_RING;
+    return SD_OK;
+}
+
+int sd_pose_optimize_host(int n_problems, const int32_t* edge_offset, const sd_pose_edge* edges, const sd_camera* cams,
+                          float* Tcw, uint8_t* outlier, int32_t* n_good)
+{
+    if (n_problems < 0 || (n_problems > 0 && (!edge_offset || !cams || !Tcw || !n_good))) return set_err(SD_ERR_INVALID, "bad pose_optimize arguments");
+    if (n_problems == 0) return SD_OK;
+    if (edge_offset[0] != 0) return set_err(SD_ERR_INVALID, "edge_offset[0] must be 0");
+    for (int p = 0; p < n_problems; p++) if (edge_offset[p + 1] < edge_offset[p]) return set_err(SD_ERR_INVALID, "edge offsets must not decrease");
+    const size_t nE = (size_t)edge_offset[n_problems];
+    if (nE > 0 && (!edges || !outlier)) return set_err(SD_ERR_INVALID, "bad pose_optimize arguments");
+    int rc = require_device();
+    if (rc != SD_OK) return rc;
+    int32_t* d_off = nullptr; sd_pose_edge* d_e = nullptr; float* d_T = nullptr; uint8_t* d_o = nullptr; int32_t* d_g = nullptr;
+    hipError_t e = hipMalloc((void**)&d_off, (size_t)(n_problems + 1) * 4);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_e, std::max<size_t>(nE, 1) * sizeof(sd_pose_edge));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_T, (size_t)n_problems * 64);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_o, std::max<size_t>(nE, 1));
+    if (e == hipSuccess) e = hipMalloc((void**)&d_g, (size_t)n_problems * 4);
+    if (e == hipSuccess) e = hipMemcpy(d_off, edge_offset, (size_t)(n_problems + 1) * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && nE) e = hipMemcpy(d_e, edges, nE * sizeof(sd_pose_edge), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_T, Tcw, (size_t)n_problems * 64, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        rc = sd_pose_optimize_device(n_problems, d_off, d_e, cams, d_T, d_o, d_g, nullptr);
+        if (rc == SD_OK) e = hipStreamSynchronize(nullptr);
+        if (rc == SD_OK && e == hipSuccess) e = hipMemcpy(Tcw, d_T, (size_t)n_problems * 64, hipMemcpyDeviceToHost);
+        if (rc == SD_OK && e == hipSuccess && nE) e = hipMemcpy(outlier, d_o, nE, hipMemcpyDeviceToHost);
+        if (rc == SD_OK && e == hipSuccess) e = hipMemcpy(n_good, d_g, (size_t)n_problems * 4, hipMemcpyDeviceToHost);
+    }
+    for (void* p : {(void*)d_off, (void*)d_e, (void*)d_T, (void*)d_o, (void*)d_g}) if (p) (void)hipFree(p);
+    if (rc != SD_OK) return rc;
+    HIPCHK(e);
+    return SD_OK;
+}
+
+static int pose_alloc(sd_batch* b)
+{
+    if (b->d_poseEdges) return SD_OK;
+    const size_t nI = b->maxImages, cap = b->plan.kpCap;
+    HIPCHK(hipMalloc((void**)&b->d_poseEdges, nI * cap * sizeof(sd_pose_edge)));
+    HIPCHK(hipMalloc((void**)&b->d_poseFirst, nI * 4));
+    HIPCHK(hipMalloc((void**)&b->d_poseLast, nI * 4));
+    HIPCHK(hipMalloc((void**)&b->d_poseT, nI * 64));
+    HIPCHK(hipMalloc((void**)&b->d_poseOut, nI * cap));
+    HIPCHK(hipMalloc((void**)&b->d_poseGood, nI * 4));
+    HIPCHK(hipMalloc((void**)&b->d_poseCam, nI * sizeof(sd_camera)));
+    HIPCHK(hipMalloc((void**)&b->d_poseMap, nI * 4));
+    HIPCHK(hipMalloc((void**)&b->d_poseRan, nI * 4));
+    HIPCHK(hipMalloc((void**)&b->d_poseTin, nI * 64));
+    HIPCHK(hipMemset(b->d_poseFirst, 0, nI * 4));
+    HIPCHK(hipMemset(b->d_poseLast, 0, nI * 4));
+    HIPCHK(hipMemset(b->d_poseGood, 0, nI * 4));
+    HIPCHK(hipMemset(b->d_poseRan, 0, nI * 4));
+    return SD_OK;
+}
+
+// d_active / activeBase / minMatches: the tracker's gating (SdPoseEdgeArgs); the plain entry passes none
+static int batch_pose_impl(sd_batch* b, int n_pairs, const int32_t* pair_index, const float* Tcw_host, hipStream_t s, const int* d_active,
+                           int activeBase, int minMatches)
+{
+    if (!b || n_pairs < 0 || (n_pairs > 0 && !pair_index)) return set_err(SD_ERR_INVALID, "bad batch pose_optimize arguments");
+    if (n_pairs == 0) return SD_OK;
+    if (b->pairCam.size() != (size_t)b->maxImages) return set_err(SD_ERR_STATE, "pose_optimize before search_by_projection");
+    std::vector<uint8_t> seen(b->maxImages, 0);
+    for (int k = 0; k < n_pairs; k++) {
+        if (pair_index[k] < 0 || pair_index[k] >= b->dlPairs) return set_err(SD_ERR_STATE, "pose_optimize: pair holds no projection matches");
+        if (seen[pair_index[k]]++) return set_err(SD_ERR_INVALID, "pose_optimize: a pair is listed twice");
+    }
+    int rc = pose_alloc(b);
+    if (rc != SD_OK) return rc;
+    b->lastStream = s;
+    b->hPoseMap.assign(pair_index, pair_index + n_pairs);
+    b->hPoseCam.resize(n_pairs);
+    for (int k = 0; k < n_pairs; k++) b->hPoseCam[k] = b->pairCam[pair_index[k]];
+    HIPCHK(hipMemcpyAsync(b->d_poseMap, b->hPoseMap.data(), (size_t)n_pairs * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b->d_poseCam, b->hPoseCam.data(), (size_t)n_pairs * sizeof(sd_camera), hipMemcpyHostToDevice, s));
+    if (Tcw_host) HIPCHK(hipMemcpyAsync(b->d_poseTin, Tcw_host, (size_t)n_pairs * 64, hipMemcpyHostToDevice, s));
+    SdPoseEdgeArgs E;
+    E.kp = KPUN(b); E.uRight = b->d_uright; E.count = b->d_count; E.xw = b->d_xw; E.match = b->d_match; E.pairIdx = b->d_pairIdx;
+    E.TcwPair = b->d_pose; E.Tin = Tcw_host ? b->d_poseTin : nullptr; E.map = b->d_poseMap; E.active = d_active; E.activeBase = activeBase; E.nmatch = b->d_nmatch;
+    E.minMatches = minMatches; E.edges = b->d_poseEdges; E.first = b->d_poseFirst; E.last = b->d_poseLast; E.Tout = b->d_poseT; E.ran = b->d_poseRan;
+    for (int l = 0; l < SD_MAX_LEVELS; l++) E.invSigma2[l] = l < b->ex->prm.nlevels ? b->ex->prm.invSigma2[l] : 0.f;
+    E.nLevels = b->ex->prm.nlevels; E.cap = b->plan.kpCap;
+    hipLaunchKernelGGL(k_pose_edges, dim3(n_pairs), dim3(256), 0, s, E);
+    LAUNCH_CHECK("k_pose_edges");
+    SdPoseArgs A;
+    A.edges = b->d_poseEdges; A.first = b->d_poseFirst; A.last = b->d_poseLast; A.cam = b->d_poseCam; A.Tcw = b->d_poseT;
+    A.outlier = b->d_poseOut; A.nGood = b->d_poseGood; A.map = b->d_poseMap;
+    return pose_launch(A, n_pairs, s);
+}
+
+int sd_batch_pose_optimize(sd_batch* b, int n_pairs, const int32_t* pair_index, const float* Tcw_host, void* stream_)
+{
+    if (!b) return set_err(SD_ERR_INVALID, "null batch");
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
+    return batch_pose_impl(b, n_pairs, pair_index, Tcw_host, s, nullptr, 0, 0);
+}
+
+int sd_batch_download_pose(sd_batch* b, int pair, float* Tcw, uint8_t* outlier, int cap, int* n_initial, int* n_good)
+{
+    if (!b || pair < 0 || pair >= b->maxImages) return set_err(SD_ERR_INVALID, "bad download_pose arguments");
+    if (!b->d_poseEdges) return set_err(SD_ERR_STATE, "no pose_optimize ran on this batch");
+    int rc = sd_batch_sync(b);
+    if (rc != SD_OK) return rc;
+    if (outlier && cap < b->plan.kpCap) return set_err(SD_ERR_CAPACITY, "outlier buffer needs kp_capacity entries");
+    int f = 0, l = 0, g = 0;
+    HIPCHK(hipMemcpy(&f, b->d_poseFirst + pair, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&l, b->d_poseLast + pair, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&g, b->d_poseGood + pair, 4, hipMemcpyDeviceToHost));
+    if (Tcw) HIPCHK(hipMemcpy(Tcw, b->d_poseT + (size_t)pair * 16, 64, hipMemcpyDeviceToHost));
+    const int n = l - f;
+    if (outlier) {
+        memset(outlier, 0, (size_t)b->plan.kpCap);
+        if (n > 0) {
+            std::vector<sd_pose_edge> e(n);
+            std::vector<uint8_t> o(n);
+            HIPCHK(hipMemcpy(e.data(), b->d_poseEdges + f, (size_t)n * sizeof(sd_pose_edge), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(o.data(), b->d_poseOut + f, (size_t)n, hipMemcpyDeviceToHost));
+            for (int i = 0; i < n; i++) outlier[e[i].kp_index] = o[i];
+        }
+    }
+    if (n_initial) *n_initial = n;
+    if (n_good) *n_good = n < 3 ? 0 : g;
     return SD_OK;
 }
 

@@ -38,6 +38,9 @@ struct sd_tracker {
     Block blocks[2]; int blockHead = 0, blockCount = 0;
     // caller-owned SLAM state (sd_tracker_set_state); empty = the automatic rule of the sharded batch mode
     std::vector<int32_t> state;
+    // opt-in TrackWithMotionModel tail (sd_tracker_set_pose_optimization) and its per-lane results of the last call
+    bool poseOpt = false, poseRanStep = false;
+    std::vector<sd_pose_result> poseRes;
     bool notInitialised(int l) const { return state.empty() ? lanes[l].frameNo == 0 : !(state[l] & 1); }         // mState == NOT_INITIALIZED on entry to Track_new
     bool useIniExtractor(int l) const { return bIni && (state.empty() ? lanes[l].frameNo < 2 : !(state[l] & 1)); } // GrabImageMonocular, Tracking.cc:335-338
     bool canTrackHomo(int l) const { return state.empty() ? lanes[l].frameNo >= 2 : (state[l] & 2) != 0; }       // mState==OK && !mVelocity.empty(), Tracking.cc:971
@@ -110,8 +113,9 @@ int sd_tracker_create(sd_tracker** out, sd_extractor* ex, const sd_tracker_param
     if (e == hipSuccess) e = hipMalloc((void**)&t->d_active, (size_t)t->S * 4);
     if (e == hipSuccess) e = hipMalloc((void**)&t->d_activeLast, (size_t)t->S * 4);
     if (e == hipSuccess) e = hipMalloc((void**)&t->d_slotList, (size_t)t->S * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->d_sum, (size_t)t->S * sizeof(SdLaneSummary));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&t->h_sum, (size_t)t->S * sizeof(SdLaneSummary), hipHostMallocDefault);
+    const size_t sumBytes = (size_t)t->S * (sizeof(SdLaneSummary) + sizeof(SdPoseSummary));   // lane summaries, then the pose tail's
+    if (e == hipSuccess) e = hipMalloc((void**)&t->d_sum, sumBytes);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&t->h_sum, sumBytes, hipHostMallocDefault);
     for (auto& bl : t->blocks) if (e == hipSuccess && t->bp[0]) e = hipEventCreateWithFlags(&bl.ready, hipEventDisableTiming);
     if (e == hipSuccess && !b->d_moPts) {                 // the model-fit buffers (lazily allocated by sd_batch_estimate_motion otherwise)
         e = hipMalloc((void**)&b->d_moPts, nI * cap * 16);
@@ -372,6 +376,23 @@ static int tracker_dynamic_round(sd_tracker* t, const float* Tcw, hipStream_t s)
     return SD_OK;
 }
 
+// TrackWithMotionModel's matcher against mLastFrame (pairs [S, 2S)); with pose mode also its tail: the 2*th retry below 20 matches
+// (the redoBelow path TrackHomo uses), then PoseOptimization of the lanes with >= 20 matches (Tracking.cc:1741-1759)
+static int tracker_last_matcher(sd_tracker* t, const int32_t* cur, const int32_t* last, const float* Tcw, hipStream_t s)
+{
+    sd_batch* b = t->b;
+    const int S = t->S, bMono = t->p.sensor == SD_SENSOR_MONOCULAR;
+    const float th = t->p.sensor == SD_SENSOR_STEREO ? 7.0f : 15.0f;           // Tracking.cc:1727-1731
+    TRK(search_by_projection_impl(b, S, S, cur, last, Tcw, t->hTlw.data(), &t->p.cam, th, bMono, 1, nullptr, nullptr, s, t->d_activeLast, 0, 1));
+    if (!t->poseOpt) return SD_OK;
+    TRK(search_by_projection_impl(b, S, S, cur, last, Tcw, t->hTlw.data(), &t->p.cam, 2 * th, bMono, 1, nullptr, nullptr, s, t->d_activeLast, 20, 0));
+    std::vector<int32_t> pairs(S);
+    for (int l = 0; l < S; l++) pairs[l] = S + l;
+    TRK(batch_pose_impl(b, S, pairs.data(), nullptr, s, t->d_activeLast, S, 20));
+    t->poseRanStep = true;
+    return SD_OK;
+}
+
 static int tracker_summary(sd_tracker* t, int haveLast, hipStream_t s)
 {
     sd_batch* b = t->b;
@@ -379,7 +400,14 @@ static int tracker_summary(sd_tracker* t, int haveLast, hipStream_t s)
     hipLaunchKernelGGL(k_lane_summary, dim3(t->S), dim3(64), 0, s, b->d_fb, b->d_count, b->d_moRes, b->d_sepRet, b->d_nmatch, b->d_npairs, t->S, t->ipl,
                        haveLast, t->d_sum);
     LAUNCH_CHECK("k_lane_summary");
-    HIPCHK(hipMemcpyAsync(t->h_sum, t->d_sum, (size_t)t->S * sizeof(SdLaneSummary), hipMemcpyDeviceToHost, s));
+    if (t->poseRanStep) {
+        hipLaunchKernelGGL(k_pose_lane_summary, dim3(t->S), dim3(256), 0, s, b->d_poseEdges, b->d_poseFirst, b->d_poseLast, b->d_poseT, b->d_poseOut,
+                           b->d_poseGood, b->d_poseRan, b->d_match, b->d_flags, b->d_pairIdx, b->d_nmatch, t->d_activeLast, t->S, b->plan.kpCap,
+                           (SdPoseSummary*)(t->d_sum + t->S));
+        LAUNCH_CHECK("k_pose_lane_summary");
+    }
+    const size_t bytes = (size_t)t->S * (sizeof(SdLaneSummary) + (t->poseRanStep ? sizeof(SdPoseSummary) : 0));
+    HIPCHK(hipMemcpyAsync(t->h_sum, t->d_sum, bytes, hipMemcpyDeviceToHost, s));
     return sd_batch_sync(b);
 }
 
@@ -548,6 +576,7 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
 
     // ---- TrackWithMotionModel's matcher against mLastFrame (pairs [S, 2S))
     bool anyLast = false;
+    t->poseRanStep = false;
     if (t->p.track_last) {
         t->hActiveLast.assign(S, 0);
         std::vector<int32_t> cur(S), last(S);
@@ -562,10 +591,8 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
             if (P.size() == 16) memcpy(&t->hTlw[(size_t)l * 16], P.data(), 64);
         }
         if (anyLast) {
-            const float th = t->p.sensor == SD_SENSOR_STEREO ? 7.0f : 15.0f;       // Tracking.cc:1727-1731
             HIPCHK(hipMemcpyAsync(t->d_activeLast, t->hActiveLast.data(), (size_t)S * 4, hipMemcpyHostToDevice, s));
-            TRK(search_by_projection_impl(b, S, S, cur.data(), last.data(), Tcw, t->hTlw.data(), cam, th, t->p.sensor == SD_SENSOR_MONOCULAR, 1,
-                                          nullptr, nullptr, s, t->d_activeLast, 0, 1));
+            TRK(tracker_last_matcher(t, cur.data(), last.data(), Tcw, s));
         }
     }
 
@@ -627,9 +654,7 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
             if (anyLast) {
                 std::vector<int32_t> cur(S), last(S);
                 for (int l = 0; l < S; l++) { cur[l] = l * ipl; last[l] = t->hActiveLast[l] ? t->lanes[l].lastSlot : l * ipl; }
-                const float th = t->p.sensor == SD_SENSOR_STEREO ? 7.0f : 15.0f;
-                TRK(search_by_projection_impl(b, S, S, cur.data(), last.data(), Tcw, t->hTlw.data(), cam, th, t->p.sensor == SD_SENSOR_MONOCULAR, 1,
-                                              nullptr, nullptr, s, t->d_activeLast, 0, 1));
+                TRK(tracker_last_matcher(t, cur.data(), last.data(), Tcw, s));
             }
             TRK(sd_batch_copy_frames(b, S, src.data(), dst.data(), s));
             TRK(tracker_summary(t, anyLast ? 1 : 0, s));
@@ -656,6 +681,17 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
             L.lastOmit[j] = t->hOmit[(size_t)l * SD_MAXB + o];
             L.lastVel[j][0] = t->hVel[((size_t)l * SD_MAXB + o) * 2]; L.lastVel[j][1] = t->hVel[((size_t)l * SD_MAXB + o) * 2 + 1];
         }
+        if (t->poseOpt) {                                          // TrackWithMotionModel's tail (defaults when no matcher ran)
+            sd_pose_result& P = t->poseRes[l];
+            memset(&P, 0, sizeof(P));
+            P.n_matches = -1;
+            memcpy(P.Tcw, Tcw + (size_t)l * 16, 64);
+            if (t->poseRanStep) {
+                const SdPoseSummary& Q = ((const SdPoseSummary*)(t->h_sum + S))[l];
+                memcpy(P.Tcw, Q.Tcw, 64);
+                P.ran = Q.ran; P.n_matches = Q.nMatches; P.n_initial = Q.nInitial; P.n_good = Q.nGood; P.n_matches_map = Q.nMap; P.ok = Q.ok;
+            }
+        }
         if (results) {
             sd_lane_result& Rr = results[l];
             memset(&Rr, 0, sizeof(Rr));
@@ -672,6 +708,27 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
         }
         L.frameNo++;
     }
+    return SD_OK;
+}
+
+int sd_tracker_set_pose_optimization(sd_tracker* t, int enable)
+{
+    if (!t) return set_err(SD_ERR_INVALID, "null tracker");
+    if (enable && !t->p.track_last) return set_err(SD_ERR_STATE, "pose optimisation needs track_last");
+    if (enable) {                                              // the pose buffers now, not inside the first step
+        int rc = pose_alloc(t->b);
+        if (rc != SD_OK) return rc;
+    }
+    t->poseOpt = enable != 0;
+    t->poseRes.assign(t->poseOpt ? t->S : 0, sd_pose_result());
+    return SD_OK;
+}
+
+int sd_tracker_pose_results(sd_tracker* t, sd_pose_result* results)
+{
+    if (!t || !results) return set_err(SD_ERR_INVALID, "bad pose_results arguments");
+    if (!t->poseOpt) return set_err(SD_ERR_STATE, "pose optimisation is off");
+    memcpy(results, t->poseRes.data(), (size_t)t->S * sizeof(sd_pose_result));
     return SD_OK;
 }
 

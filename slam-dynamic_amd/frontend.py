@@ -126,6 +126,12 @@ def lib():
         L.sd_batch_download_keys_un.argtypes = [vp, i, vp, i, C.POINTER(i)]
         L.sd_image_bounds.argtypes = [i, i, vp, vp, vp]
         L.sd_batch_backproject_dense.argtypes = [vp, i, vp, vp, sz, sz, vp, sz, sz, f, vp, sz, sz, vp, vp, vp, i, vp, vp]
+        L.sd_pose_optimize_device.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
+        L.sd_pose_optimize_host.argtypes = [i, vp, vp, vp, vp, vp, vp]
+        L.sd_batch_pose_optimize.argtypes = [vp, i, vp, vp, vp]
+        L.sd_batch_download_pose.argtypes = [vp, i, vp, vp, i, C.POINTER(i), C.POINTER(i)]
+        L.sd_tracker_set_pose_optimization.argtypes = [vp, i]
+        L.sd_tracker_pose_results.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -395,6 +401,20 @@ class Batch:
         a = np.ascontiguousarray(src, np.int32); d = np.ascontiguousarray(dst, np.int32)
         check(lib().sd_batch_copy_frames(self.h, len(a), _p(a), _p(d), C.c_void_p(stream or 0)))
 
+    def pose_optimize(self, pair_index, Tcw=None, stream=None):
+        """Optimizer::PoseOptimization of the Current frame of each listed projection pair (sd_batch_pose_optimize): edges from the
+        pair's matches; Tcw (n, 4, 4) = the prior, None = the pose the pair was matched with."""
+        pi = np.ascontiguousarray(pair_index, np.int32).reshape(-1)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(len(pi), 16) if Tcw is not None else None
+        self._keep_pose = (pi, T)
+        check(lib().sd_batch_pose_optimize(self.h, len(pi), _p(pi), _p(T) if T is not None else None, C.c_void_p(stream or 0)))
+
+    def download_pose(self, pair):
+        """(Tcw (4, 4) f32, mvbOutlier per Current keypoint (cap,) u8, nInitialCorrespondences, return value)."""
+        T = np.zeros(16, np.float32); out = np.zeros(self.cap, np.uint8); ni = C.c_int(); ng = C.c_int()
+        check(lib().sd_batch_download_pose(self.h, pair, _p(T), _p(out), self.cap, C.byref(ni), C.byref(ng)))
+        return T.reshape(4, 4), out, ni.value, ng.value
+
     def download_matches(self, pair):
         match = np.zeros(self.cap, np.int32); pairs = np.zeros((self.cap, 2), np.int32)
         npairs = C.c_int(); nm = C.c_int()
@@ -514,6 +534,12 @@ class LaneResult(C.Structure):
                 ("objects", (C.c_double * 4) * MAXB), ("box_velocity", (C.c_double * 2) * MAXB)]
 
 
+class PoseResult(C.Structure):
+    """sd_pose_result (include/sd_frontend.h)."""
+    _fields_ = [("Tcw", C.c_float * 16), ("ran", C.c_int32), ("n_matches", C.c_int32), ("n_initial", C.c_int32), ("n_good", C.c_int32),
+                ("n_matches_map", C.c_int32), ("ok", C.c_int32)]
+
+
 class Tracker:
     """sd_tracker: System::TrackStereo / TrackRGBD / TrackMonocular for n_lanes independent camera streams, one frame per lane per call
     (Tracking::GrabImage* -> Frame::Frame -> Track_new's dynamic block -> match vs mLastFrame -> q_frame)."""
@@ -620,6 +646,16 @@ class Tracker:
                                      bp, np_, _p(ts), _p(tc) if tc is not None else None, _p(tw) if tw is not None else None,
                                      C.cast(self.results, C.c_void_p), C.c_void_p(stream or 0)))
         return self.results
+
+    def set_pose_optimization(self, enable):
+        """Opt-in TrackWithMotionModel tail: 2*th retry, PoseOptimization, nmatchesMap (sd_tracker_set_pose_optimization)."""
+        check(lib().sd_tracker_set_pose_optimization(self.h, int(bool(enable))))
+
+    def pose_results(self):
+        """Per lane sd_pose_result of the last track() call."""
+        out = (PoseResult * self.n_lanes)()
+        check(lib().sd_tracker_pose_results(self.h, C.cast(out, C.c_void_p)))
+        return out
 
 
 class RefQueue:
@@ -809,3 +845,24 @@ class Vocabulary:
             self.close()
         except Exception:
             pass
+
+
+# ---- Optimizer::PoseOptimization on the device (include/sd_frontend.h: sd_pose_optimize_*) ----
+POSE_EDGE_DTYPE = np.dtype([("xw", "<f4", (3,)), ("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("inv_sigma2", "<f4"), ("kp_index", "<i4")])   # sd_pose_edge
+
+
+def pose_optimize(edge_offset, edges, cams, Tcw):
+    """n independent PoseOptimization problems in one launch (sd_pose_optimize_host).  edge_offset (n + 1,) int32, edges (E,)
+    POSE_EDGE_DTYPE, cams: one camera dict (make_camera) or a list of n, Tcw (n, 4, 4).  Returns (Tcw (n, 4, 4) f32, outlier (E,) u8,
+    n_good (n,) int32)."""
+    off = np.ascontiguousarray(edge_offset, np.int32).reshape(-1)
+    n = len(off) - 1
+    e = np.ascontiguousarray(edges, POSE_EDGE_DTYPE).reshape(-1)
+    assert len(e) == off[-1]
+    cl = [cams] * n if isinstance(cams, dict) else list(cams)
+    keys = ("fx", "fy", "cx", "cy", "mbf", "mb", "mnMinX", "mnMaxX", "mnMinY", "mnMaxY")        # sd_camera; the solver reads fx .. mbf
+    c = np.array([[x.get(k, 0.0) for k in keys] for x in cl], np.float32).reshape(n, 10)
+    T = np.ascontiguousarray(np.array(Tcw, np.float32).reshape(n, 16))
+    out = np.zeros(max(len(e), 1), np.uint8); good = np.zeros(max(n, 1), np.int32)
+    check(lib().sd_pose_optimize_host(n, _p(off), _p(e), _p(c), _p(T), _p(out), _p(good)))
+    return T.reshape(n, 4, 4), out[:len(e)], good[:n]

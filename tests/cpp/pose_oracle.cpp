@@ -1,0 +1,415 @@
+// Independent CPU oracle of Optimizer::PoseOptimization (src/Optimizer.cc:239-451) and the pieces of the vendored g2o it runs:
+// OptimizationAlgorithmLevenberg::solve (core/optimization_algorithm_levenberg.cpp:60-180), SparseOptimizer::optimize /
+// activeRobustChi2 / initializeOptimization (core/sparse_optimizer.cpp:100-114, 206-290, 354-420), BaseUnaryEdge::
+// constructQuadraticForm (core/base_unary_edge.hpp:43-70), robustInformation (core/base_edge.h:96-101), RobustKernelHuber
+// (core/robust_kernel_impl.cpp:65-91), the two pose-only edges (types/types_six_dof_expmap.cpp:266-360), SE3Quat
+// (types/se3quat.h), LinearSolverDense (solvers/linear_solver_dense.h:100-118) and Converter::toSE3Quat / toCvMat.
+// A literal, sequential restatement: sums over edges run in edge order, the 6x6 system is factorised by a pivoted LDL^T as
+// Eigen::LDLT does it.  Shares no code with the device kernel (slam-dynamic_amd/csrc/k_pose.h).  Test infrastructure only:
+// the tests compile it with g++ -O2 -ffp-contract=off.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+namespace {
+
+struct Edge { float xw[3]; float u, v, ur; float inv_sigma2; int32_t kp_index; };   // sd_pose_edge (include/sd_frontend.h)
+static_assert(sizeof(Edge) == 32, "edge record");
+
+struct Quat { double x, y, z, w; };                      // Eigen::Quaterniond coefficient order
+struct SE3 { Quat r; double t[3]; };
+
+// ---- Eigen leaves (recalled: Eigen is not vendored in the reference) ----
+void q_normalize(Quat& q)
+{
+    const double n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
+    if (n2 > 0) { const double n = std::sqrt(n2); q.x /= n; q.y /= n; q.z /= n; q.w /= n; }
+}
+void normalize_rotation(Quat& q)                         // SE3Quat::normalizeRotation
+{
+    if (q.w < 0) { q.x = -q.x; q.y = -q.y; q.z = -q.z; q.w = -q.w; }
+    q_normalize(q);
+}
+Quat q_from_matrix(const double m[3][3])                 // Quaterniond(const Matrix3d&)
+{
+    Quat q;
+    double c[4];                                         // x, y, z
+    const double tr = m[0][0] + m[1][1] + m[2][2];
+    if (tr > 0) {
+        double t = std::sqrt(tr + 1.0);
+        q.w = 0.5 * t;
+        t = 0.5 / t;
+        q.x = (m[2][1] - m[1][2]) * t;
+        q.y = (m[0][2] - m[2][0]) * t;
+        q.z = (m[1][0] - m[0][1]) * t;
+        return q;
+    }
+    int i = 0;
+    if (m[1][1] > m[0][0]) i = 1;
+    if (m[2][2] > m[i][i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    double t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
+    c[i] = 0.5 * t;
+    t = 0.5 / t;
+    q.w = (m[k][j] - m[j][k]) * t;
+    c[j] = (m[j][i] + m[i][j]) * t;
+    c[k] = (m[k][i] + m[i][k]) * t;
+    q.x = c[0]; q.y = c[1]; q.z = c[2];
+    return q;
+}
+Quat q_mul(const Quat& a, const Quat& b)
+{
+    Quat r;
+    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
+    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
+    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
+    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
+    return r;
+}
+void q_rotate(const Quat& q, const double v[3], double out[3])     // q * v: uv = vec x v; uv += uv; v + w uv + vec x uv
+{
+    double uv[3] = {q.y * v[2] - q.z * v[1], q.z * v[0] - q.x * v[2], q.x * v[1] - q.y * v[0]};
+    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
+    const double c[3] = {q.y * uv[2] - q.z * uv[1], q.z * uv[0] - q.x * uv[2], q.x * uv[1] - q.y * uv[0]};
+    for (int i = 0; i < 3; i++) out[i] = v[i] + q.w * uv[i] + c[i];
+}
+void q_to_matrix(const Quat& q, double R[3][3])          // toRotationMatrix
+{
+    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
+    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
+    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+    R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz;       R[0][2] = txz + twy;
+    R[1][0] = txy + twz;       R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
+    R[2][0] = txz - twy;       R[2][1] = tyz + twx;       R[2][2] = 1 - (txx + tyy);
+}
+
+// ---- SE3Quat ----
+SE3 se3_from_rt(const double R[3][3], const double t[3]) { SE3 s; s.r = q_from_matrix(R); s.t[0] = t[0]; s.t[1] = t[1]; s.t[2] = t[2]; normalize_rotation(s.r); return s; }
+SE3 se3_mul(const SE3& a, const SE3& b)
+{
+    SE3 r = a;
+    double rb[3];
+    q_rotate(a.r, b.t, rb);
+    for (int i = 0; i < 3; i++) r.t[i] += rb[i];
+    r.r = q_mul(a.r, b.r);
+    normalize_rotation(r.r);
+    return r;
+}
+void mat3_mul(const double A[3][3], const double B[3][3], double C[3][3])
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) C[i][j] = A[i][0] * B[0][j] + A[i][1] * B[1][j] + A[i][2] * B[2][j];
+}
+SE3 se3_exp(const double u[6])                            // SE3Quat::exp
+{
+    const double w[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
+    const double theta = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+    const double Om[3][3] = {{0, -w[2], w[1]}, {w[2], 0, -w[0]}, {-w[1], w[0], 0}};
+    double Om2[3][3], R[3][3], V[3][3];
+    mat3_mul(Om, Om, Om2);
+    if (theta < 0.00001) {
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) R[i][j] = V[i][j] = ((i == j ? 1.0 : 0.0) + Om[i][j]) + Om2[i][j];
+    } else {
+        const double a = std::sin(theta) / theta, b = (1 - std::cos(theta)) / (theta * theta), c = (theta - std::sin(theta)) / std::pow(theta, 3);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                R[i][j] = ((i == j ? 1.0 : 0.0) + a * Om[i][j]) + b * Om2[i][j];
+                V[i][j] = ((i == j ? 1.0 : 0.0) + b * Om[i][j]) + c * Om2[i][j];
+            }
+    }
+    double t[3];
+    for (int i = 0; i < 3; i++) t[i] = V[i][0] * up[0] + V[i][1] * up[1] + V[i][2] * up[2];
+    return se3_from_rt(R, t);
+}
+SE3 to_se3quat(const float* T)                            // Converter::toSE3Quat
+{
+    double R[3][3], t[3];
+    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) R[i][j] = T[i * 4 + j]; t[i] = T[i * 4 + 3]; }
+    return se3_from_rt(R, t);
+}
+void to_cvmat(const SE3& s, float* T)                     // Converter::toCvMat(SE3Quat) = to_homogeneous_matrix, f32
+{
+    double R[3][3];
+    q_to_matrix(s.r, R);
+    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) T[i * 4 + j] = (float)R[i][j]; T[i * 4 + 3] = (float)s.t[i]; }
+    T[12] = T[13] = T[14] = 0.f; T[15] = 1.f;
+}
+
+struct Cam { double fx, fy, cx, cy, bf; };
+
+// ---- edges ----
+// computeError at pose s: e = obs - cam_project(s.map(Xw)); returns the dimension (2 mono, 3 stereo)
+int edge_error(const Edge& E, const Cam& c, const SE3& s, double e[3], bool f64_invz)
+{
+    const double X[3] = {E.xw[0], E.xw[1], E.xw[2]};
+    double p[3];
+    q_rotate(s.r, X, p);
+    for (int i = 0; i < 3; i++) p[i] = p[i] + s.t[i];
+    if (E.ur < 0) {
+        const double r0 = (p[0] / p[2]) * c.fx + c.cx, r1 = (p[1] / p[2]) * c.fy + c.cy;
+        e[0] = (double)E.u - r0; e[1] = (double)E.v - r1; e[2] = 0;
+        return 2;
+    }
+    const double invz = f64_invz ? 1.0 / p[2] : (double)(float)(1.0 / p[2]);     // const float invz = 1.0f/trans_xyz[2]
+    const double r0 = p[0] * invz * c.fx + c.cx, r1 = p[1] * invz * c.fy + c.cy, r2 = r0 - c.bf * invz;
+    e[0] = (double)E.u - r0; e[1] = (double)E.v - r1; e[2] = (double)E.ur - r2;
+    return 3;
+}
+void edge_jacobian(const Edge& E, const Cam& c, const SE3& s, double J[3][6])     // linearizeOplus
+{
+    const double X[3] = {E.xw[0], E.xw[1], E.xw[2]};
+    double p[3];
+    q_rotate(s.r, X, p);
+    for (int i = 0; i < 3; i++) p[i] = p[i] + s.t[i];
+    const double x = p[0], y = p[1], invz = 1.0 / p[2], invz_2 = invz * invz;
+    J[0][0] = x * y * invz_2 * c.fx;  J[0][1] = -(1 + (x * x * invz_2)) * c.fx; J[0][2] = y * invz * c.fx;
+    J[0][3] = -invz * c.fx;           J[0][4] = 0;                              J[0][5] = x * invz_2 * c.fx;
+    J[1][0] = (1 + y * y * invz_2) * c.fy; J[1][1] = -x * y * invz_2 * c.fy; J[1][2] = -x * invz * c.fy;
+    J[1][3] = 0;                           J[1][4] = -invz * c.fy;           J[1][5] = y * invz_2 * c.fy;
+    J[2][0] = J[0][0] - c.bf * y * invz_2; J[2][1] = J[0][1] + c.bf * x * invz_2; J[2][2] = J[0][2];
+    J[2][3] = J[0][3];                     J[2][4] = 0;                           J[2][5] = J[0][5] - c.bf * invz_2;
+}
+double chi2_of(const double e[3], int D, double w)        // _error.dot(information() * _error)
+{
+    double s = e[0] * (w * e[0]) + e[1] * (w * e[1]);
+    if (D == 3) s = s + e[2] * (w * e[2]);
+    return s;
+}
+
+// ---- the pivoted LDL^T of Eigen::LDLT (lower storage) and its solve; returns isPositive() ----
+bool ldlt_solve(double A[6][6], const double b[6], double x[6])
+{
+    int tr[6];
+    int sign = 0;                                         // 0 ZeroSign, 1 PositiveSemiDef, 2 NegativeSemiDef, 3 Indefinite
+    bool found_zero = false, ret = true;
+    double temp[6];
+    for (int k = 0; k < 6; k++) {
+        int p = k;
+        double big = std::fabs(A[k][k]);
+        for (int i = k + 1; i < 6; i++) if (std::fabs(A[i][i]) > big) { big = std::fabs(A[i][i]); p = i; }
+        tr[k] = p;
+        if (p != k) {
+            double t;
+            for (int j = 0; j < k; j++) { t = A[k][j]; A[k][j] = A[p][j]; A[p][j] = t; }
+            t = A[k][k]; A[k][k] = A[p][p]; A[p][p] = t;
+            for (int i = k + 1; i < p; i++) { t = A[i][k]; A[i][k] = A[p][i]; A[p][i] = t; }
+            for (int i = p + 1; i < 6; i++) { t = A[i][k]; A[i][k] = A[i][p]; A[i][p] = t; }
+        }
+        if (k > 0) {
+            for (int j = 0; j < k; j++) temp[j] = A[j][j] * A[k][j];
+            double s = 0;
+            for (int j = 0; j < k; j++) s = j == 0 ? A[k][j] * temp[j] : s + A[k][j] * temp[j];
+            A[k][k] -= s;
+            for (int i = k + 1; i < 6; i++) {
+                double r = 0;
+                for (int j = 0; j < k; j++) r = j == 0 ? A[i][j] * temp[j] : r + A[i][j] * temp[j];
+                A[i][k] -= r;
+            }
+        }
+        const double akk = A[k][k];
+        const bool valid = std::fabs(akk) > 0;
+        if (k < 5 && valid) for (int i = k + 1; i < 6; i++) A[i][k] /= akk;
+        else if (k < 5) for (int i = k + 1; i < 6; i++) ret = ret && A[i][k] == 0;
+        if (found_zero && valid) ret = false;
+        else if (!valid) found_zero = true;
+        if (sign == 1) { if (akk < 0) sign = 3; }
+        else if (sign == 2) { if (akk > 0) sign = 3; }
+        else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = 2; }
+    }
+    (void)ret;
+    for (int i = 0; i < 6; i++) x[i] = b[i];
+    for (int k = 0; k < 6; k++) { const double t = x[k]; x[k] = x[tr[k]]; x[tr[k]] = t; }
+    for (int i = 1; i < 6; i++) { double s = 0; for (int j = 0; j < i; j++) s = j == 0 ? A[i][j] * x[j] : s + A[i][j] * x[j]; x[i] -= s; }
+    for (int i = 0; i < 6; i++) { if (std::fabs(A[i][i]) > DBL_MIN) x[i] /= A[i][i]; else x[i] = 0; }
+    for (int i = 4; i >= 0; i--) { double s = 0; for (int j = i + 1; j < 6; j++) s = j == i + 1 ? A[j][i] * x[j] : s + A[j][i] * x[j]; x[i] -= s; }
+    for (int k = 5; k >= 0; k--) { const double t = x[k]; x[k] = x[tr[k]]; x[tr[k]] = t; }
+    return sign == 1 || sign == 0;
+}
+
+// ---- the problem ----
+struct Problem {
+    const Edge* E; int n; Cam c;
+    bool robust; bool f64_invz;
+    const uint8_t* level;                                 // 0 = active (level 0), 1 = outlier
+};
+// computeActiveErrors + activeRobustChi2 at pose s (sums in edge order)
+double active_chi(const Problem& P, const SE3& s)
+{
+    const double dM = (double)(float)std::sqrt(5.991), dS = (double)(float)std::sqrt(7.815);
+    double chi = 0;
+    for (int i = 0; i < P.n; i++) {
+        if (P.level[i]) continue;
+        double e[3];
+        const int D = edge_error(P.E[i], P.c, s, e, P.f64_invz);
+        const double c2 = chi2_of(e, D, (double)P.E[i].inv_sigma2);
+        if (P.robust) {
+            const double delta = D == 2 ? dM : dS, dsqr = delta * delta;
+            chi += c2 <= dsqr ? c2 : 2 * std::sqrt(c2) * delta - dsqr;
+        } else {
+            chi += c2;
+        }
+    }
+    return chi;
+}
+// buildSystem: H (lower triangle used) and b at pose s
+void build_system(const Problem& P, const SE3& s, double H[6][6], double b[6])
+{
+    const double dM = (double)(float)std::sqrt(5.991), dS = (double)(float)std::sqrt(7.815);
+    for (int i = 0; i < 6; i++) { b[i] = 0; for (int j = 0; j < 6; j++) H[i][j] = 0; }
+    for (int n = 0; n < P.n; n++) {
+        if (P.level[n]) continue;
+        double e[3], J[3][6];
+        const int D = edge_error(P.E[n], P.c, s, e, P.f64_invz);
+        edge_jacobian(P.E[n], P.c, s, J);
+        const double w = (double)P.E[n].inv_sigma2;
+        double rho1 = 1.0;
+        bool rk = P.robust;
+        if (rk) {
+            const double c2 = chi2_of(e, D, w), delta = D == 2 ? dM : dS, dsqr = delta * delta;
+            if (!(c2 <= dsqr)) rho1 = delta / std::sqrt(c2);
+        }
+        const double wo = rk ? rho1 * w : w;              // weightedOmega = rho[1] * information
+        for (int i = 0; i < 6; i++)
+            for (int j = 0; j <= i; j++) {
+                double h = (J[0][i] * wo) * J[0][j];
+                for (int k = 1; k < D; k++) h = h + (J[k][i] * wo) * J[k][j];
+                H[i][j] += h;
+            }
+        for (int i = 0; i < 6; i++) {
+            double g = rk ? ((rho1 * J[0][i]) * w) * e[0] : (J[0][i] * w) * e[0];
+            for (int k = 1; k < D; k++) g = g + (rk ? ((rho1 * J[k][i]) * w) * e[k] : (J[k][i] * w) * e[k]);
+            b[i] -= g;
+        }
+    }
+}
+
+struct RoundInfo { int iterations, lastRejected; };
+
+// SparseOptimizer::optimize(10) with OptimizationAlgorithmLevenberg; returns the final estimate and the pose of the last error pass
+int optimize(const Problem& P, SE3& est, SE3& errPose, RoundInfo& ri)
+{
+    ri.iterations = 0; ri.lastRejected = 0;
+    int nActive = 0;
+    for (int i = 0; i < P.n; i++) nActive += P.level[i] == 0;
+    if (nActive == 0) return -1;                          // no active vertex: "0 vertices to optimize"
+    double lambda = 0, x[6] = {0, 0, 0, 0, 0, 0};
+    int ni = 2, nBad = 0;
+    for (int it = 0; it < 10; it++) {
+        ri.iterations++;
+        double currentChi = active_chi(P, est);
+        errPose = est;
+        const double iniChi = currentChi;
+        double H[6][6], b[6];
+        build_system(P, est, H, b);
+        if (it == 0) {
+            double md = 0;
+            for (int j = 0; j < 6; j++) md = std::max(std::fabs(H[j][j]), md);
+            lambda = 1e-5 * md; ni = 2; nBad = 0;
+        }
+        double rho = 0;
+        int qmax = 0;
+        do {
+            const SE3 backup = est;
+            double A[6][6];
+            for (int i = 0; i < 6; i++) for (int j = 0; j < 6; j++) A[i][j] = H[i][j];
+            for (int i = 0; i < 6; i++) A[i][i] += lambda;
+            double xs[6];
+            const bool ok2 = ldlt_solve(A, b, xs);
+            if (ok2) for (int i = 0; i < 6; i++) x[i] = xs[i];
+            est = se3_mul(se3_exp(x), est);               // VertexSE3Expmap::oplusImpl
+            double tempChi = active_chi(P, est);
+            errPose = est;
+            if (!ok2) tempChi = DBL_MAX;
+            rho = currentChi - tempChi;
+            double scale = 0;
+            for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);
+            scale += 1e-3;
+            rho /= scale;
+            if (rho > 0 && std::isfinite(tempChi)) {
+                double alpha = 1. - std::pow((2 * rho - 1), 3);
+                alpha = std::min(alpha, 2. / 3.);
+                lambda *= std::max(1. / 3., alpha);
+                ni = 2;
+                currentChi = tempChi;
+                ri.lastRejected = 0;
+            } else {
+                lambda *= ni;
+                ni *= 2;
+                est = backup;
+                ri.lastRejected = 1;
+            }
+            qmax++;
+        } while (rho < 0 && qmax < 10);
+        if (qmax == 10 || rho == 0) break;               // Terminate
+        if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
+        if (nBad >= 3) break;
+    }
+    return ri.iterations;
+}
+
+}  // namespace
+
+// mode bit 0..7 = options of PoseOptimization (0 = the reference; the others are VARIANTS the tests use to show that a quirk matters):
+//   1: classification recomputes every error at the final estimate (no stale cache)   2: no restart from the input pose per round
+//   4: stereo invz in f64
+// mode 256: per-edge evaluation instead of a solve: pose = aux[0..6] (qx qy qz qw tx ty tz), delta = aux[7..12]; writes for edge i
+//   aux[13 + 21 i ..] = error at exp(delta) * pose (3), Jacobian at pose (3 x 6 row-major); option 4 applies.
+// PoseOptimization: edges [n_edges] in edge order, cam5 = fx fy cx cy mbf, Tcw [16] row-major in/out (untouched when < 3 edges),
+// outlier [n_edges] out, stats (nullable) [13] = rounds run, then per round (iterations, last trial rejected, nBad).  Returns
+// nInitialCorrespondences - nBad (0 with fewer than 3 edges).
+extern "C" int sd_pose_oracle(int mode, int n_edges, const void* edges, const float* cam5, float* Tcw, uint8_t* outlier, int32_t* stats,
+                              double* aux)
+{
+    const Edge* E = (const Edge*)edges;
+    const Cam c = {cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
+    const bool fresh = mode & 1, noRestart = mode & 2, f64z = mode & 4;
+    if (mode & 256) {
+        SE3 s;
+        s.r = {aux[0], aux[1], aux[2], aux[3]};
+        s.t[0] = aux[4]; s.t[1] = aux[5]; s.t[2] = aux[6];
+        const SE3 m = se3_mul(se3_exp(aux + 7), s);
+        for (int i = 0; i < n_edges; i++) {
+            double* o = aux + 13 + 21 * i;
+            double e[3], J[3][6];
+            edge_error(E[i], c, m, e, f64z);
+            edge_jacobian(E[i], c, s, J);
+            for (int k = 0; k < 3; k++) o[k] = e[k];
+            for (int k = 0; k < 18; k++) o[3 + k] = J[k / 6][k % 6];
+        }
+        return 0;
+    }
+    if (stats) for (int k = 0; k < 13; k++) stats[k] = 0;
+    for (int i = 0; i < n_edges; i++) outlier[i] = 0;     // mvbOutlier[i] = false for every edge
+    if (n_edges < 3) return 0;
+    const SE3 pose0 = to_se3quat(Tcw);
+    SE3 est = pose0;
+    uint8_t* level = new uint8_t[n_edges]();
+    Problem P{E, n_edges, c, true, f64z, level};
+    const float chi2Mono = 5.991f, chi2Stereo = 7.815f;
+    int nBad = 0;
+    for (int it = 0; it < 4; it++) {
+        if (!noRestart || it == 0) est = pose0;
+        SE3 errPose = est;
+        RoundInfo ri;
+        optimize(P, est, errPose, ri);
+        nBad = 0;
+        for (int i = 0; i < n_edges; i++) {               // mono edges, then stereo edges: independent per edge
+            double e[3];
+            const bool wasOut = outlier[i] != 0;
+            const int D = edge_error(E[i], c, (wasOut || fresh) ? est : errPose, e, f64z);
+            const float chi2 = (float)chi2_of(e, D, (double)E[i].inv_sigma2);
+            if (chi2 > (D == 2 ? chi2Mono : chi2Stereo)) { outlier[i] = 1; level[i] = 1; nBad++; }
+            else { outlier[i] = 0; level[i] = 0; }
+        }
+        if (it == 2) P.robust = false;
+        if (stats) { stats[0] = it + 1; stats[1 + 3 * it] = ri.iterations; stats[2 + 3 * it] = ri.lastRejected; stats[3 + 3 * it] = nBad; }
+        if (n_edges < 10) break;
+    }
+    delete[] level;
+    to_cvmat(est, Tcw);
+    return n_edges - nBad;
+}

@@ -1,0 +1,146 @@
+"""The PoseOptimization CPU oracle (tests/cpp/pose_oracle.cpp) against what Optimizer::PoseOptimization and the vendored g2o do
+(Optimizer.cc:239-451 with the vendored g2o): convergence on exact data, the analytic Jacobians, and constructed
+cases for the quirks."""
+import numpy as np
+
+import pose_cases as pc
+
+
+def _exact_problem(kind):
+    """Observations exactly representable in f32 at the true pose: a signed-permutation rotation, dyadic translation and points,
+    fx = fy = 512, bf = 256, depths 4 / 8 / 16 -- the optimum is the true pose itself."""
+    cam = dict(fx=np.float32(512), fy=np.float32(512), cx=np.float32(320), cy=np.float32(240), mbf=np.float32(256))
+    R = np.array([[0, 0, 1], [0, 1, 0], [-1, 0, 0]], np.float64)
+    t = np.array([0.25, -0.5, 1.0])
+    rng = np.random.default_rng(3)
+    n = 40
+    Z = rng.choice([4.0, 8.0, 16.0], n)
+    X = rng.integers(-64, 64, n) / 16.0; Y = rng.integers(-32, 32, n) / 16.0
+    Xc = np.stack([X, Y, Z], 1)
+    Xw = (Xc - t) @ R
+    e = np.zeros(n, pc.EDGE_DTYPE)
+    e["xw"] = Xw
+    e["u"] = 512 * X / Z + 320; e["v"] = 512 * Y / Z + 240
+    stereo = np.ones(n, bool) if kind == "stereo" else (np.zeros(n, bool) if kind == "mono" else np.arange(n) % 2 == 0)
+    e["ur"] = np.where(stereo, e["u"] - 256 / Z, -1.0)
+    e["inv_sigma2"] = 1.0
+    e["kp_index"] = np.arange(n)
+    assert np.array_equal(e["xw"].astype(np.float64), Xw)
+    return e, cam, pc.pose(R, t)
+
+
+def test_recovers_exact_pose_to_1e9():
+    for kind in ("mono", "stereo", "mixed"):
+        e, cam, T = _exact_problem(kind)
+        T0 = pc.perturb(T, np.random.default_rng(7), 2.0, 0.05)
+        r, Tout, out, st = pc.optimize(e, cam, T0)
+        assert r == len(e) and not out.any(), kind
+        assert np.max(np.abs(Tout.astype(np.float64) - T)) <= 1e-9, (kind, np.max(np.abs(Tout - T)))
+
+
+def _num_jac(e, q, t, mode, h=1e-6):
+    J = np.zeros((len(e), 3, 6))
+    for k in range(6):
+        d = np.zeros(6); d[k] = h
+        ep, _ = pc.evaluate(e, pc.CAM, q, t, d, mode)
+        em, _ = pc.evaluate(e, pc.CAM, q, t, -d, mode)
+        J[:, :, k] = (ep - em) / (2 * h)
+    return J
+
+
+def test_jacobians_match_central_differences():
+    """linearizeOplus (types_six_dof_expmap.cpp:266-364) = d computeError(exp(d) * T) / d d at 0, for both edge types.  The stereo
+    edge's f32 invz makes its error a staircase at this step size, so its derivative is taken with invz in f64 (MODE_F64_INVZ)."""
+    rng = np.random.default_rng(11)
+    for kind, mode in (("mono", 0), ("stereo", pc.MODE_F64_INVZ)):
+        e, T, _ = pc.make_problem(rng, 25, kind, noise=0.0)
+        q = _quat(T[:3, :3])
+        _, Ja = pc.evaluate(e, pc.CAM, q, T[:3, 3], np.zeros(6), mode)
+        Jn = _num_jac(e, q, T[:3, 3], mode)
+        rows = np.where((e["ur"] >= 0)[:, None], [True, True, True], [True, True, False])       # the third row exists for stereo edges
+        rel = np.abs(Ja - Jn) / np.maximum(1.0, np.abs(Ja))
+        assert rel[rows].max() <= 1e-6, (kind, rel[rows].max())
+        assert kind == "mono" or (e["ur"] >= 0).sum() > 10
+
+
+def _quat(R):
+    w = np.sqrt(max(0.0, 1 + R[0, 0] + R[1, 1] + R[2, 2])) / 2
+    return np.array([(R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w), w])
+
+
+def test_each_round_restarts_from_the_input_pose():
+    """vSE3->setEstimate(toSE3Quat(pFrame->mTcw)) every round (Optimizer.cc:374): rounds 1 - 3 start over from the prior, so they
+    take as many LM iterations as a fresh solve; a variant that continues from the last estimate converges at once and ends elsewhere."""
+    rng = np.random.default_rng(4)
+    e, T, _ = pc.make_problem(rng, 120, "mixed", 0.2, noise=1.0)
+    T0 = pc.perturb(T, rng, 10.0, 0.5)
+    r0, A, o0, s0 = pc.optimize(e, pc.CAM, T0)
+    r1, B, o1, s1 = pc.optimize(e, pc.CAM, T0, pc.MODE_NO_RESTART)
+    assert s0[0] == 4 and min(s0[1 + 3 * k] for k in range(1, 4)) >= 5
+    assert s1[1 + 3 * 3] < s0[1 + 3 * 3] and not np.array_equal(A, B)
+
+
+def test_classification_after_a_rejected_last_trial():
+    """optimize() can end on a rejected trial (10 failed trials, or rho == 0: Terminate); pop() restores the estimate but not the
+    edges' cached _error, and the inlier classification reads that cache (Optimizer.cc:380-395).  The oracle (and the kernel) keep the
+    pose of the last error pass for this.  What this case shows is only that a round does end on a rejected trial; it does NOT show a
+    classification that differs from fresh errors: after the lambda escalation that rejected step is ~2^-45 of the first, and no case
+    tried made the two differ, so the quirk is reproduced but not covered by a differing case."""
+    rng = np.random.default_rng(2)
+    e, T, bad = pc.make_problem(rng, 60, "mixed", 0.2, noise=1.0)
+    T0 = pc.perturb(T, rng, 10.0, 0.5)
+    r, Tout, out, st = pc.optimize(e, pc.CAM, T0)
+    rf, Tf, outf, stf = pc.optimize(e, pc.CAM, T0, pc.MODE_FRESH_ERRORS)
+    assert any(st[2 + 3 * k] for k in range(st[0])), st               # some round ended on a rejected trial
+    # the rejected trial's step is tiny after the lambda escalation, so cached and fresh errors classify alike here
+    assert r == rf and np.array_equal(out, outf) and np.array_equal(Tout, Tf)
+
+
+def test_fewer_than_10_edges_run_one_round():
+    rng = np.random.default_rng(5)
+    for n, rounds in ((9, 1), (10, 4)):
+        e, T, _ = pc.make_problem(rng, n, "mixed", noise=0.5)
+        r, _, _, st = pc.optimize(e, pc.CAM, pc.perturb(T, rng, 2.0, 0.05))
+        assert st[0] == rounds, (n, st)
+
+
+def test_fewer_than_3_edges_return_0_with_flags_reset_and_pose_untouched():
+    rng = np.random.default_rng(6)
+    for n in (0, 1, 2):
+        e, T, _ = pc.make_problem(rng, n, "mixed")
+        T0 = pc.perturb(T, rng, 2.0, 0.05).astype(np.float32)
+        r, Tout, out, st = pc.optimize(e, pc.CAM, T0)                # the wrapper pre-fills the flags with 7
+        assert r == 0 and not out.any() and Tout.tobytes() == T0.tobytes() and st[0] == 0
+
+
+def test_all_outlier_round_is_a_no_op_at_the_input_pose():
+    """Every edge an outlier after round 0: rounds 1 - 3 have no active vertex (optimize returns -1), the classification recomputes
+    every error at the input pose, and the returned pose is the prior."""
+    rng = np.random.default_rng(8)
+    e, T, _ = pc.make_problem(rng, 30, "mixed", outlier_ratio=1.0, noise=0.0, gross=150.0)     # every edge moved >= 150 px
+    T0 = T.astype(np.float32)
+    r, Tout, out, st = pc.optimize(e, pc.CAM, T0)
+    assert out.all() and r == 0 and st[0] == 4
+    assert all(st[1 + 3 * k] == 0 for k in (1, 2, 3))
+    assert np.max(np.abs(Tout - T0)) <= 1e-6
+
+
+def test_stereo_projection_rounds_invz_to_f32():
+    """EdgeStereoSE3ProjectXYZOnlyPose::cam_project: `const float invz = 1.0f/trans_xyz[2]`; the mono edge stays in f64."""
+    rng = np.random.default_rng(9)
+    e, T, _ = pc.make_problem(rng, 50, "stereo", noise=0.0)
+    q = _quat(T[:3, :3])
+    e = e[e["ur"] >= 0]
+    a, _ = pc.evaluate(e, pc.CAM, q, T[:3, 3], np.zeros(6))
+    b, _ = pc.evaluate(e, pc.CAM, q, T[:3, 3], np.zeros(6), pc.MODE_F64_INVZ)
+    assert len(e) > 20 and np.any(a != b)
+    Xc = e["xw"].astype(np.float64) @ T[:3, :3].T + T[:3, 3]
+    iz = (1.0 / Xc[:, 2]).astype(np.float32).astype(np.float64)
+    fx, cx, bf = float(pc.CAM["fx"]), float(pc.CAM["cx"]), float(pc.CAM["mbf"])
+    u = Xc[:, 0] * iz * fx + cx
+    assert np.max(np.abs(a[:, 0] - (e["u"].astype(np.float64) - u))) <= 1e-9
+    assert np.max(np.abs(a[:, 2] - (e["ur"].astype(np.float64) - (u - bf * iz)))) <= 1e-9
+    m, T2, _ = pc.make_problem(rng, 20, "mono", noise=0.0)
+    am, _ = pc.evaluate(m, pc.CAM, _quat(T2[:3, :3]), T2[:3, 3], np.zeros(6))
+    bm, _ = pc.evaluate(m, pc.CAM, _quat(T2[:3, :3]), T2[:3, 3], np.zeros(6), pc.MODE_F64_INVZ)
+    assert np.array_equal(am, bm)
