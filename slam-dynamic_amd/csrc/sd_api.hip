@@ -9,6 +9,8 @@
 #include <cmath>
 #include <string>
 #include <vector>
+#include <map>
+#include <memory>
 #include <mutex>
 #include "k_extract.h"
 #include "k_frame.h"
@@ -23,6 +25,20 @@
 
 static thread_local std::string g_err;
 int sd_set_err(int code, const std::string& msg) { g_err = msg; return code; }
+
+hipError_t sd_raise_lds_limit(const void* kernel, int bytes)
+{
+    if (bytes <= 64 * 1024) return hipSuccess;
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, int> limits;      // (device, kernel) -> the highest limit set so far
+    std::lock_guard<std::mutex> lk(mu);
+    int& limit = limits[{dev, kernel}];
+    if (bytes > limit && (e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) == hipSuccess) limit = bytes;
+    return e;
+}
 
 struct sd_extractor {
     SdParams prm;
@@ -40,90 +56,90 @@ struct SdPyrTiles { int tilesX = 0, tilesY = 0, srcRowBytes = 0, srcRowsMax = 0,
 
 struct sd_batch {
     std::vector<SdPyrTiles> pyrTiles;      // per level: tile grid of k_pyr_level_tiles
-    int* d_pyrExt = nullptr;
-    int* d_blurTiles = nullptr; int nBlurTiles = 0;      // k_blur_wide: tile list of one image
+    SdDevBuf<int> d_pyrExt;
+    SdDevBuf<int> d_blurTiles; int nBlurTiles = 0;      // k_blur_wide: tile list of one image
     sd_extractor* ex = nullptr;
     SdPlan plan;
     SdDevPlan hplan;
     int maxImages = 0;
     int nExtracted = 0;       // images processed by the last extract
     std::vector<uint8_t> slotValid;   // slot holds frame results (extracted or carried over)
-    int2* d_pairIdx = nullptr;
+    SdDevBuf<int2> d_pairIdx;
     int nStereo = 0;
     hipStream_t stream = nullptr;
     hipStream_t lastStream = nullptr;
     // device buffers
-    SdDevPlan* d_plan = nullptr;
-    SdCell* d_cells = nullptr;
-    SdFastCell* d_fcells = nullptr; int fastListCap = 0, fastMaxCap = 0;   // k_fast_cells_staged: per-cell descriptors, list sizes
-    int16_t* d_tabs = nullptr;
-    uint8_t* d_pyr = nullptr;
-    uint8_t* d_blur = nullptr;
-    uint32_t* d_cellList = nullptr;
-    int* d_cellCount = nullptr;
-    uint32_t* d_cand = nullptr;
-    uint16_t* d_nodeOf = nullptr;
-    int* d_lvlCount = nullptr;
-    int* d_candCount = nullptr;
-    uint32_t* d_lvlKp = nullptr;
-    float2* d_rot = nullptr;
-    sd_keypoint* d_kp = nullptr;
-    sd_keypoint* d_kpUn = nullptr; sd_keypoint* d_kpDUn = nullptr; SdDistortion dist; bool hasDist = false; int* d_unSlots = nullptr;   // mvKeysUn / mvdynKeysUn (sd_batch_set_distortion)
-    uint8_t* d_desc = nullptr;
-    int* d_count = nullptr;
-    int* d_err = nullptr;
+    SdDevBuf<SdDevPlan> d_plan;
+    SdDevBuf<SdCell> d_cells;
+    SdDevBuf<SdFastCell> d_fcells; int fastListCap = 0, fastMaxCap = 0;   // k_fast_cells_staged: per-cell descriptors, list sizes
+    SdDevBuf<int16_t> d_tabs;
+    SdDevBuf<uint8_t> d_pyr;
+    SdDevBuf<uint8_t> d_blur;
+    SdDevBuf<uint32_t> d_cellList;
+    SdDevBuf<int> d_cellCount;
+    SdDevBuf<uint32_t> d_cand;
+    SdDevBuf<uint16_t> d_nodeOf;
+    SdDevBuf<int> d_lvlCount;
+    SdDevBuf<int> d_candCount;
+    SdDevBuf<uint32_t> d_lvlKp;
+    SdDevBuf<float2> d_rot;
+    SdDevBuf<sd_keypoint> d_kp;
+    SdDevBuf<sd_keypoint> d_kpUn; SdDevBuf<sd_keypoint> d_kpDUn; SdDistortion dist; bool hasDist = false; SdDevBuf<int> d_unSlots;   // mvKeysUn / mvdynKeysUn (sd_batch_set_distortion)
+    SdDevBuf<uint8_t> d_desc;
+    SdDevBuf<int> d_count;
+    SdDevBuf<int> d_err;
     bool cullOk = true;              // the per-key-point LDS tables of k_box_separate / k_separate fit this workspace's capacity
-    float* d_uright = nullptr;
-    float* d_depth = nullptr;
-    int* d_sad = nullptr;
-    unsigned short* d_rowIdx = nullptr;   // right keypoints bucketed by row (stereo)
-    int* d_rowStart = nullptr;
-    short* d_cellOf = nullptr;      // grid cell of every keypoint
-    unsigned short* d_sortedIdx = nullptr;   // keypoint indices sorted by (cell, index)
-    unsigned short* d_cellStart = nullptr;   // [maxImages][3072 + 8]
+    SdDevBuf<float> d_uright;
+    SdDevBuf<float> d_depth;
+    SdDevBuf<int> d_sad;
+    SdDevBuf<unsigned short> d_rowIdx;   // right keypoints bucketed by row (stereo)
+    SdDevBuf<int> d_rowStart;
+    SdDevBuf<short> d_cellOf;      // grid cell of every keypoint
+    SdDevBuf<unsigned short> d_sortedIdx;   // keypoint indices sorted by (cell, index)
+    SdDevBuf<unsigned short> d_cellStart;   // [maxImages][3072 + 8]
     int gridSortN = 0;
-    float* d_xw = nullptr;          // map-point world positions [maxImages][cap][3]
-    uint8_t* d_flags = nullptr;     // bit0: has map point (not outlier); bit1: Observations() > 0
-    unsigned short* d_pcand = nullptr;
-    uint8_t* d_pncand = nullptr;
+    SdDevBuf<float> d_xw;          // map-point world positions [maxImages][cap][3]
+    SdDevBuf<uint8_t> d_flags;     // bit0: has map point (not outlier); bit1: Observations() > 0
+    SdDevBuf<unsigned short> d_pcand;
+    SdDevBuf<uint8_t> d_pncand;
     // bag of words (per image): per-feature word / weight / node, FeatureVector (sorted) + runs, BowVector
-    unsigned* d_bowWordF = nullptr; double* d_bowWF = nullptr; unsigned* d_bowNidF = nullptr; unsigned* d_fvNode = nullptr; unsigned* d_fvFeat = nullptr;
-    int* d_fvRunStart = nullptr; unsigned* d_fvRunNode = nullptr; unsigned* d_bowWord = nullptr; double* d_bowVal = nullptr; int* d_bowMeta = nullptr;
-    int* d_bowImg = nullptr; std::vector<uint8_t> bowValid;
-    float* d_moPts = nullptr; SdMotionNorm* d_moNorm = nullptr; int* d_moCounts = nullptr; double* d_moModels = nullptr; uint8_t* d_moMaskH = nullptr; uint8_t* d_moMaskF = nullptr;
-    SdMotionResult* d_moRes = nullptr; int nMotion = 0;      // TrackHomo model fit
-    unsigned* d_lmCand = nullptr; uint8_t* d_lmN = nullptr; uint8_t* d_lmOvf = nullptr; int* d_lmIdx = nullptr; int lmCap = 0;   // local-map search scratch
-    int* d_match = nullptr;
-    int* d_pairs = nullptr;
-    int* d_npairs = nullptr;
-    int* d_nmatch = nullptr;
-    float* d_pose = nullptr;        // staging for host poses: [2][maxImages][16]
+    SdDevBuf<unsigned> d_bowWordF; SdDevBuf<double> d_bowWF; SdDevBuf<unsigned> d_bowNidF; SdDevBuf<unsigned> d_fvNode; SdDevBuf<unsigned> d_fvFeat;
+    SdDevBuf<int> d_fvRunStart; SdDevBuf<unsigned> d_fvRunNode; SdDevBuf<unsigned> d_bowWord; SdDevBuf<double> d_bowVal; SdDevBuf<int> d_bowMeta;
+    SdDevBuf<int> d_bowImg; std::vector<uint8_t> bowValid;
+    SdDevBuf<float> d_moPts; SdDevBuf<SdMotionNorm> d_moNorm; SdDevBuf<int> d_moCounts; SdDevBuf<double> d_moModels; SdDevBuf<uint8_t> d_moMaskH; SdDevBuf<uint8_t> d_moMaskF;
+    SdDevBuf<SdMotionResult> d_moRes; int nMotion = 0;      // TrackHomo model fit
+    SdDevBuf<unsigned> d_lmCand; SdDevBuf<uint8_t> d_lmN; SdDevBuf<uint8_t> d_lmOvf; SdDevBuf<int> d_lmIdx; int lmCap = 0;   // local-map search scratch
+    SdDevBuf<int> d_match;
+    SdDevBuf<int> d_pairs;
+    SdDevBuf<int> d_npairs;
+    SdDevBuf<int> d_nmatch;
+    SdDevBuf<float> d_pose;        // staging for host poses: [2][maxImages][16]
     // PoseOptimization per projection pair (sd_batch_pose_optimize), allocated on first use: edges [maxImages][cap], edge ranges,
     // pose in / out, mvbOutlier per edge, return value, camera, whether it ran; pairCam = the camera each pair was matched with
-    sd_pose_edge* d_poseEdges = nullptr; int* d_poseFirst = nullptr; int* d_poseLast = nullptr; float* d_poseT = nullptr;
-    uint8_t* d_poseOut = nullptr; int* d_poseGood = nullptr; sd_camera* d_poseCam = nullptr; int* d_poseMap = nullptr; int* d_poseRan = nullptr;
-    float* d_poseTin = nullptr;
+    SdDevBuf<sd_pose_edge> d_poseEdges; SdDevBuf<int> d_poseFirst; SdDevBuf<int> d_poseLast; SdDevBuf<float> d_poseT;
+    SdDevBuf<uint8_t> d_poseOut; SdDevBuf<int> d_poseGood; SdDevBuf<sd_camera> d_poseCam; SdDevBuf<int> d_poseMap; SdDevBuf<int> d_poseRan;
+    SdDevBuf<float> d_poseTin;
     std::vector<sd_camera> pairCam, hPoseCam; std::vector<int32_t> hPoseMap;
     int nPairs = 0;
     int dlPairs = 0;          // pairs sd_batch_download_matches may read (the tracker also keeps pairs at [n_lanes, 2 * n_lanes))
     // dynamic-object cull
-    SdFrameBoxes* d_fb = nullptr;
-    SdFrameBoxes* d_fbStage = nullptr;     // one upload per sd_batch_first_separate call
-    int* d_boxItems = nullptr;
-    sd_keypoint* d_kpT = nullptr; uint8_t* d_descT = nullptr; float* d_urT = nullptr; float* d_depT = nullptr;
-    sd_keypoint* d_kpD = nullptr; uint8_t* d_descD = nullptr; float* d_urD = nullptr; float* d_depD = nullptr;
-    int* d_slots = nullptr;
-    float* d_HorF = nullptr; int* d_sepFlag = nullptr; int* d_lastIdx = nullptr; int* d_lastStatus = nullptr; int* d_nLast = nullptr;
-    int* d_dynStart = nullptr; int* d_dynStatus = nullptr; int* d_sepMatches = nullptr; int* d_sepRet = nullptr;
-    int2* d_sepPairs = nullptr;
-    int2* d_copyPairs = nullptr;
-    unsigned long long* d_cloudBits = nullptr; int* d_cloudRows = nullptr; double* d_cloudT = nullptr; int* d_cloudSlots = nullptr; size_t cloudCap = 0;
+    SdDevBuf<SdFrameBoxes> d_fb;
+    SdDevBuf<SdFrameBoxes> d_fbStage;     // one upload per sd_batch_first_separate call
+    SdDevBuf<int> d_boxItems;
+    SdDevBuf<sd_keypoint> d_kpT; SdDevBuf<uint8_t> d_descT; SdDevBuf<float> d_urT; SdDevBuf<float> d_depT;
+    SdDevBuf<sd_keypoint> d_kpD; SdDevBuf<uint8_t> d_descD; SdDevBuf<float> d_urD; SdDevBuf<float> d_depD;
+    SdDevBuf<int> d_slots;
+    SdDevBuf<float> d_HorF; SdDevBuf<int> d_sepFlag; SdDevBuf<int> d_lastIdx; SdDevBuf<int> d_lastStatus; SdDevBuf<int> d_nLast;
+    SdDevBuf<int> d_dynStart; SdDevBuf<int> d_dynStatus; SdDevBuf<int> d_sepMatches; SdDevBuf<int> d_sepRet;
+    SdDevBuf<int2> d_sepPairs;
+    SdDevBuf<int2> d_copyPairs;
+    SdDevBuf<unsigned long long> d_cloudBits; SdDevBuf<int> d_cloudRows; SdDevBuf<double> d_cloudT; SdDevBuf<int> d_cloudSlots; size_t cloudCap = 0;
     int itemsCap = 0;
     int nSepPairs = 0;
     const int* sepActive = nullptr;          // active mask of the last separate (tracker mode), applied by update_frame too
     std::vector<SdFrameBoxes> hostBoxes;     // staging that must outlive the async uploads
     std::vector<int2> hostPairs, hostCopyPairs;
-    uint8_t* d_stage = nullptr;    // staging for host-image uploads
+    SdDevBuf<uint8_t> d_stage;    // staging for host-image uploads
     size_t stageBytes = 0;
     int qtMN = 0, qtSortP = 0;
     size_t qtLds = 0;
@@ -134,6 +150,12 @@ struct sd_batch {
     std::vector<hipEvent_t> pool;
     double totalMs[K_COUNT] = {0};
     int64_t launches[K_COUNT] = {0};
+    ~sd_batch()
+    {
+        for (auto& r : pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
+        for (auto e : pool) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
 // mvKeysUn of the batch: the key points themselves unless a distortion was set (Frame.cc:814-818)
@@ -228,47 +250,17 @@ int sd_extractor_level_size(const sd_extractor* ex, int width, int height, int l
     return SD_OK;
 }
 
-static void batch_free(sd_batch* b)
-{
-    if (!b) return;
-    void* ptrs[] = {b->d_plan, b->d_cells, b->d_fcells, b->d_blurTiles, b->d_tabs, b->d_pyr, b->d_blur, b->d_cellList, b->d_cellCount, b->d_cand,
-                    b->d_nodeOf, b->d_lvlCount, b->d_candCount, b->d_lvlKp, b->d_rot, b->d_kp, b->d_desc, b->d_count,
-                    b->d_err, b->d_uright, b->d_depth, b->d_sad, b->d_stage, b->d_cellOf, b->d_xw, b->d_flags,
-                    b->d_pcand, b->d_pncand, b->d_match, b->d_pairs, b->d_npairs, b->d_nmatch, b->d_pose, b->d_pairIdx, b->d_sortedIdx, b->d_cellStart,
-                    b->d_fb, b->d_fbStage, b->d_boxItems, b->d_kpT, b->d_descT, b->d_urT, b->d_depT, b->d_slots, b->d_HorF, b->d_sepFlag,
-                    b->d_lastIdx, b->d_lastStatus, b->d_nLast, b->d_dynStart, b->d_dynStatus, b->d_sepMatches, b->d_sepRet,
-                    b->d_sepPairs, b->d_kpD, b->d_descD, b->d_urD, b->d_depD, b->d_rowIdx, b->d_rowStart,
-                    b->d_lmCand, b->d_lmN, b->d_lmOvf, b->d_lmIdx, b->d_bowWordF, b->d_bowWF, b->d_bowNidF, b->d_fvNode, b->d_fvFeat,
-                    b->d_fvRunStart, b->d_fvRunNode, b->d_bowWord, b->d_bowVal, b->d_bowMeta, b->d_bowImg,
-                    b->d_moPts, b->d_moNorm, b->d_moCounts, b->d_moModels, b->d_moMaskH, b->d_moMaskF, b->d_moRes, b->d_pyrExt, b->d_copyPairs, b->d_kpUn, b->d_kpDUn, b->d_unSlots, b->d_cloudBits, b->d_cloudRows, b->d_cloudT, b->d_cloudSlots,
-                    b->d_poseEdges, b->d_poseFirst, b->d_poseLast, b->d_poseT, b->d_poseOut, b->d_poseGood, b->d_poseCam, b->d_poseMap, b->d_poseRan, b->d_poseTin};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& r : b->pending) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
-    for (auto e : b->pool) (void)hipEventDestroy(e);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
-}
-
-static int batch_create_impl(sd_batch** out, sd_extractor* ex, int width, int height, int max_images, int minKpCap);
-int sd_batch_create(sd_batch** out, sd_extractor* ex, int width, int height, int max_images) { return batch_create_impl(out, ex, width, height, max_images, 0); }
-
 // minKpCap: row stride of the per-image result arrays at least this (a tracker whose lanes switch between two extractors)
-static int batch_create_impl(sd_batch** out, sd_extractor* ex, int width, int height, int max_images, int minKpCap)
+static int batch_create_impl(std::unique_ptr<sd_batch>& out, sd_extractor* ex, int width, int height, int max_images, int minKpCap)
 {
-    if (!out) return SD_ERR_INVALID;
-    *out = nullptr;
     if (!ex || width < 1 || height < 1 || max_images < 1) return set_err(SD_ERR_INVALID, "bad batch arguments");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return set_err(SD_ERR_NO_DEVICE, "no HIP device: the front end has no CPU fallback");
-    sd_batch* b = new sd_batch();
+    std::unique_ptr<sd_batch> b(new sd_batch());
     b->ex = ex;
     b->maxImages = max_images;
-    if (!sd_plan_build(b->plan, ex->prm, width, height, minKpCap)) {
-        std::string e = b->plan.error;
-        delete b;
-        return set_err(SD_ERR_UNSUPPORTED, e);
-    }
+    if (!sd_plan_build(b->plan, ex->prm, width, height, minKpCap)) return set_err(SD_ERR_UNSUPPORTED, b->plan.error);
     const SdPlan& P = b->plan;
     SdDevPlan& D = b->hplan;
     memset(&D, 0, sizeof(D));
@@ -290,85 +282,75 @@ static int batch_create_impl(sd_batch** out, sd_extractor* ex, int width, int he
     while (sortP < MN) sortP <<= 1;
     size_t lds = (size_t)sortP * 8 + (size_t)MN * (8 + 8 + 4 * 4 + 16 * 2 + 2 * 3) + 64;
     if (lds > 160 * 1024 - 256 || MN > 30000)
-        { delete b; return set_err(SD_ERR_UNSUPPORTED, "per-level feature quota too large for the LDS quadtree (nfeatures too high)"); }
+        return set_err(SD_ERR_UNSUPPORTED, "per-level feature quota too large for the LDS quadtree (nfeatures too high)");
     b->qtMN = MN; b->qtSortP = sortP; b->qtLds = lds;
 
-#define ALLOC(ptr, bytes)                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipMalloc((void**)&(ptr), (bytes));                                   \
-        if (e_ != hipSuccess) {                                                               \
-            std::string m = std::string("hipMalloc(" #ptr "): ") + hipGetErrorString(e_);     \
-            batch_free(b);                                                                    \
-            return set_err(SD_ERR_HIP, m);                                                    \
-        }                                                                                     \
-    } while (0)
     const size_t nI = (size_t)max_images;
-    ALLOC(b->d_plan, sizeof(SdDevPlan));
-    ALLOC(b->d_cells, sizeof(SdCell) * P.cells.size());
-    ALLOC(b->d_fcells, sizeof(SdFastCell) * P.cells.size());
-    ALLOC(b->d_tabs, sizeof(int16_t) * P.tabs.size());
-    ALLOC(b->d_pyr, nI * P.pyrImageBytes + 4096);
-    ALLOC(b->d_blur, nI * P.blurImageBytes + 4096);
-    ALLOC(b->d_cellList, nI * P.cellListCap * 4 + 64);
-    ALLOC(b->d_cellCount, nI * P.cells.size() * 4);
-    ALLOC(b->d_cand, nI * P.cellListCap * 4 + 64);
-    ALLOC(b->d_nodeOf, nI * P.cellListCap * 2 + 64);
-    ALLOC(b->d_lvlCount, nI * P.nlevels * 4 + SD_MAX_LEVELS * 4);      // + padding: sd_level_counts loads SD_MAX_LEVELS entries
-    ALLOC(b->d_candCount, nI * P.nlevels * 4);
-    ALLOC(b->d_lvlKp, nI * P.kpCapLevels * 4);
-    ALLOC(b->d_rot, nI * P.kpCapLevels * sizeof(float2));
-    ALLOC(b->d_kp, nI * P.kpCap * sizeof(sd_keypoint));
-    ALLOC(b->d_desc, nI * P.kpCap * 32);
-    ALLOC(b->d_count, nI * 4);
-    ALLOC(b->d_err, 4);
-    ALLOC(b->d_uright, nI * P.kpCap * 4);
-    ALLOC(b->d_depth, nI * P.kpCap * 4);
-    ALLOC(b->d_sad, nI * P.kpCap * 4);
-    ALLOC(b->d_rowIdx, nI * P.kpCap * 2);
-    ALLOC(b->d_rowStart, nI * (size_t)(P.lv[0].H + 8) * 4);
-    ALLOC(b->d_cellOf, nI * P.kpCap * 2);
-    ALLOC(b->d_sortedIdx, nI * P.kpCap * 2);
-    ALLOC(b->d_cellStart, nI * (SD_GRID_CELLS + 8) * 2);
+    HIPCHK(b->d_plan.alloc(sizeof(SdDevPlan)));
+    HIPCHK(b->d_cells.alloc(sizeof(SdCell) * P.cells.size()));
+    HIPCHK(b->d_fcells.alloc(sizeof(SdFastCell) * P.cells.size()));
+    HIPCHK(b->d_tabs.alloc(sizeof(int16_t) * P.tabs.size()));
+    HIPCHK(b->d_pyr.alloc(nI * P.pyrImageBytes + 4096));
+    HIPCHK(b->d_blur.alloc(nI * P.blurImageBytes + 4096));
+    HIPCHK(b->d_cellList.alloc(nI * P.cellListCap * 4 + 64));
+    HIPCHK(b->d_cellCount.alloc(nI * P.cells.size() * 4));
+    HIPCHK(b->d_cand.alloc(nI * P.cellListCap * 4 + 64));
+    HIPCHK(b->d_nodeOf.alloc(nI * P.cellListCap * 2 + 64));
+    HIPCHK(b->d_lvlCount.alloc(nI * P.nlevels * 4 + SD_MAX_LEVELS * 4));      // + padding: sd_level_counts loads SD_MAX_LEVELS entries
+    HIPCHK(b->d_candCount.alloc(nI * P.nlevels * 4));
+    HIPCHK(b->d_lvlKp.alloc(nI * P.kpCapLevels * 4));
+    HIPCHK(b->d_rot.alloc(nI * P.kpCapLevels * sizeof(float2)));
+    HIPCHK(b->d_kp.alloc(nI * P.kpCap * sizeof(sd_keypoint)));
+    HIPCHK(b->d_desc.alloc(nI * P.kpCap * 32));
+    HIPCHK(b->d_count.alloc(nI * 4));
+    HIPCHK(b->d_err.alloc(4));
+    HIPCHK(b->d_uright.alloc(nI * P.kpCap * 4));
+    HIPCHK(b->d_depth.alloc(nI * P.kpCap * 4));
+    HIPCHK(b->d_sad.alloc(nI * P.kpCap * 4));
+    HIPCHK(b->d_rowIdx.alloc(nI * P.kpCap * 2));
+    HIPCHK(b->d_rowStart.alloc(nI * (size_t)(P.lv[0].H + 8) * 4));
+    HIPCHK(b->d_cellOf.alloc(nI * P.kpCap * 2));
+    HIPCHK(b->d_sortedIdx.alloc(nI * P.kpCap * 2));
+    HIPCHK(b->d_cellStart.alloc(nI * (SD_GRID_CELLS + 8) * 2));
     { int sn = 1; while (sn < P.kpCap) sn <<= 1; b->gridSortN = sn; }
-    ALLOC(b->d_xw, nI * P.kpCap * 12);
-    ALLOC(b->d_flags, nI * P.kpCap);
-    ALLOC(b->d_pcand, nI * P.kpCap * SD_PROJ_K * 2);
-    ALLOC(b->d_pncand, nI * P.kpCap);
-    ALLOC(b->d_match, nI * P.kpCap * 4);
-    ALLOC(b->d_pairs, nI * P.kpCap * 8);
-    ALLOC(b->d_npairs, nI * 4);
-    ALLOC(b->d_nmatch, nI * 4);
-    ALLOC(b->d_pose, nI * 2 * 16 * 4);
+    HIPCHK(b->d_xw.alloc(nI * P.kpCap * 12));
+    HIPCHK(b->d_flags.alloc(nI * P.kpCap));
+    HIPCHK(b->d_pcand.alloc(nI * P.kpCap * SD_PROJ_K * 2));
+    HIPCHK(b->d_pncand.alloc(nI * P.kpCap));
+    HIPCHK(b->d_match.alloc(nI * P.kpCap * 4));
+    HIPCHK(b->d_pairs.alloc(nI * P.kpCap * 8));
+    HIPCHK(b->d_npairs.alloc(nI * 4));
+    HIPCHK(b->d_nmatch.alloc(nI * 4));
+    HIPCHK(b->d_pose.alloc(nI * 2 * 16 * 4));
     b->itemsCap = 2 * P.kpCap;
-    ALLOC(b->d_fb, nI * sizeof(SdFrameBoxes));
-    ALLOC(b->d_fbStage, nI * sizeof(SdFrameBoxes));
-    ALLOC(b->d_boxItems, nI * b->itemsCap * 4);
-    ALLOC(b->d_kpT, nI * P.kpCap * sizeof(sd_keypoint));
-    ALLOC(b->d_descT, nI * P.kpCap * 32);
-    ALLOC(b->d_urT, nI * P.kpCap * 4);
-    ALLOC(b->d_depT, nI * P.kpCap * 4);
-    ALLOC(b->d_kpD, nI * P.kpCap * sizeof(sd_keypoint));
-    ALLOC(b->d_descD, nI * P.kpCap * 32);
-    ALLOC(b->d_urD, nI * P.kpCap * 4);
-    ALLOC(b->d_depD, nI * P.kpCap * 4);
-    ALLOC(b->d_slots, nI * 4);
-    ALLOC(b->d_HorF, nI * 9 * 4);
-    ALLOC(b->d_sepFlag, nI * 4);
-    ALLOC(b->d_lastIdx, nI * SD_MAXB * 4);
-    ALLOC(b->d_lastStatus, nI * SD_MAXB * 4);
-    ALLOC(b->d_nLast, nI * 4);
-    ALLOC(b->d_dynStart, nI * (SD_MAXB + 1) * 4);
-    ALLOC(b->d_dynStatus, nI * b->itemsCap * 4);
-    ALLOC(b->d_sepMatches, nI * b->itemsCap * 8);
-    ALLOC(b->d_sepRet, nI * 4);
-    ALLOC(b->d_sepPairs, nI * sizeof(int2));
-    ALLOC(b->d_copyPairs, nI * sizeof(int2));
-    ALLOC(b->d_pairIdx, nI * sizeof(int2));
+    HIPCHK(b->d_fb.alloc(nI * sizeof(SdFrameBoxes)));
+    HIPCHK(b->d_fbStage.alloc(nI * sizeof(SdFrameBoxes)));
+    HIPCHK(b->d_boxItems.alloc(nI * b->itemsCap * 4));
+    HIPCHK(b->d_kpT.alloc(nI * P.kpCap * sizeof(sd_keypoint)));
+    HIPCHK(b->d_descT.alloc(nI * P.kpCap * 32));
+    HIPCHK(b->d_urT.alloc(nI * P.kpCap * 4));
+    HIPCHK(b->d_depT.alloc(nI * P.kpCap * 4));
+    HIPCHK(b->d_kpD.alloc(nI * P.kpCap * sizeof(sd_keypoint)));
+    HIPCHK(b->d_descD.alloc(nI * P.kpCap * 32));
+    HIPCHK(b->d_urD.alloc(nI * P.kpCap * 4));
+    HIPCHK(b->d_depD.alloc(nI * P.kpCap * 4));
+    HIPCHK(b->d_slots.alloc(nI * 4));
+    HIPCHK(b->d_HorF.alloc(nI * 9 * 4));
+    HIPCHK(b->d_sepFlag.alloc(nI * 4));
+    HIPCHK(b->d_lastIdx.alloc(nI * SD_MAXB * 4));
+    HIPCHK(b->d_lastStatus.alloc(nI * SD_MAXB * 4));
+    HIPCHK(b->d_nLast.alloc(nI * 4));
+    HIPCHK(b->d_dynStart.alloc(nI * (SD_MAXB + 1) * 4));
+    HIPCHK(b->d_dynStatus.alloc(nI * b->itemsCap * 4));
+    HIPCHK(b->d_sepMatches.alloc(nI * b->itemsCap * 8));
+    HIPCHK(b->d_sepRet.alloc(nI * 4));
+    HIPCHK(b->d_sepPairs.alloc(nI * sizeof(int2)));
+    HIPCHK(b->d_copyPairs.alloc(nI * sizeof(int2)));
+    HIPCHK(b->d_pairIdx.alloc(nI * sizeof(int2)));
     b->slotValid.assign(nI, 0);
-#undef ALLOC
-    hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMemcpy(b->d_plan, &D, sizeof(D), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(b->d_cells, P.cells.data(), sizeof(SdCell) * P.cells.size(), hipMemcpyHostToDevice);
+    HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+    HIPCHK(hipMemcpy(b->d_plan, &D, sizeof(D), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->d_cells, P.cells.data(), sizeof(SdCell) * P.cells.size(), hipMemcpyHostToDevice));
     {
         std::vector<SdFastCell> fc(P.cells.size());
         for (size_t i = 0; i < P.cells.size(); i++) {
@@ -382,37 +364,38 @@ static int batch_create_impl(sd_batch** out, sd_extractor* ex, int width, int he
             b->fastMaxCap = std::max(b->fastMaxCap, c.cap);
         }
         b->fastListCap = (b->fastListCap + 7) & ~7;
-        if (e == hipSuccess) e = hipMemcpy(b->d_fcells, fc.data(), sizeof(SdFastCell) * fc.size(), hipMemcpyHostToDevice);
+        HIPCHK(hipMemcpy(b->d_fcells, fc.data(), sizeof(SdFastCell) * fc.size(), hipMemcpyHostToDevice));
     }
-    if (e == hipSuccess) e = hipMemcpy(b->d_tabs, P.tabs.data(), sizeof(int16_t) * P.tabs.size(), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(b->d_err, 0, 4);
-    if (e == hipSuccess) e = hipMemset(b->d_fb, 0, nI * sizeof(SdFrameBoxes));
-    // the dynamic-object kernels keep per-key-point tables in LDS: sized by this workspace's capacity, the limit only ever raised (workspaces of
-    // different capacities share the kernels: a monocular tracker's 2 x nFeatures initialisation workspace beside the regular one)
-    {
-        static int ldsSeparate = 0, ldsBoxSeparate = 0;
-        const int needSep = (int)sd_separate_lds(P.kpCap), needBox = (int)sd_box_separate_lds(P.kpCap);
-        b->cullOk = needSep <= 160 * 1024 && needBox <= 160 * 1024;       // otherwise sd_batch_first_separate / sd_batch_separate refuse (extraction and matching are not affected)
-        if (b->cullOk && e == hipSuccess && needSep > ldsSeparate) { e = hipFuncSetAttribute((const void*)k_separate, hipFuncAttributeMaxDynamicSharedMemorySize, needSep); ldsSeparate = needSep; }
-        if (b->cullOk && e == hipSuccess && needBox > ldsBoxSeparate && needBox > 64 * 1024) { e = hipFuncSetAttribute((const void*)k_box_separate, hipFuncAttributeMaxDynamicSharedMemorySize, needBox); ldsBoxSeparate = needBox; }
+    HIPCHK(hipMemcpy(b->d_tabs, P.tabs.data(), sizeof(int16_t) * P.tabs.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(b->d_err, 0, 4));
+    HIPCHK(hipMemset(b->d_fb, 0, nI * sizeof(SdFrameBoxes)));
+    // the dynamic-object kernels keep per-key-point tables in LDS, sized by this workspace's capacity
+    const int needSep = (int)sd_separate_lds(P.kpCap), needBox = (int)sd_box_separate_lds(P.kpCap);
+    b->cullOk = needSep <= 160 * 1024 && needBox <= 160 * 1024;       // otherwise sd_batch_first_separate / sd_batch_separate refuse (extraction and matching are not affected)
+    if (b->cullOk) {
+        HIPCHK(sd_raise_lds_limit((const void*)k_separate, needSep));
+        HIPCHK(sd_raise_lds_limit((const void*)k_box_separate, needBox));
     }
-    if (e == hipSuccess) e = hipMemset(b->d_count, 0, nI * 4);
-    if (e == hipSuccess) e = hipMemset(b->d_lvlCount, 0, nI * P.nlevels * 4);
-    if (e == hipSuccess && lds > 64 * 1024)
-        e = hipFuncSetAttribute((const void*)k_quadtree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-        std::string m = std::string("batch setup: ") + hipGetErrorString(e);
-        batch_free(b);
-        return set_err(SD_ERR_HIP, m);
-    }
+    HIPCHK(hipMemset(b->d_count, 0, nI * 4));
+    HIPCHK(hipMemset(b->d_lvlCount, 0, nI * P.nlevels * 4));
+    HIPCHK(sd_raise_lds_limit((const void*)k_quadtree, (int)lds));
     b->lastStream = b->stream;
-    *out = b;
+    out = std::move(b);
     return SD_OK;
+}
+
+int sd_batch_create(sd_batch** out, sd_extractor* ex, int width, int height, int max_images)
+{
+    if (!out) return SD_ERR_INVALID;
+    std::unique_ptr<sd_batch> b;
+    int rc = batch_create_impl(b, ex, width, height, max_images, 0);
+    *out = b.release();
+    return rc;
 }
 
 int sd_batch_destroy(sd_batch* b)
 {
-    if (b) { (void)hipDeviceSynchronize(); batch_free(b); }
+    if (b) { (void)hipDeviceSynchronize(); delete b; }
     return SD_OK;
 }
 
@@ -479,6 +462,74 @@ int sd_batch_extract_pixels_device(sd_batch* b, const uint8_t* d_src, size_t str
     return extract_impl(b, d_src, stride, image_pitch, n_images, stream_, channels == 1 ? 0 : (channels == 3 ? 1 : 3) + (rgb_order ? 1 : 0));
 }
 
+// Once per workspace: the LDS extents of k_pyr_level_tiles per level (or the per-thread kernel as a fallback) and the tiles' source origins
+static int ensure_pyr_tiles(sd_batch* b)
+{
+    if (!b->pyrTiles.empty()) return SD_OK;
+    const SdPlan& P = b->plan;
+    const int nl = P.nlevels;
+    std::vector<SdPyrTiles> tiles(nl);
+    auto refl = [](int p, int len) { if (p < 0) p = -p; if (p >= len) p = 2 * (len - 1) - p; return p; };
+    std::vector<int> ext;             // per level: source column origin of every tile column, (row origin, rows) of every tile row
+    for (int l = 1; l < nl; l++) {
+        const SdLevel& g = P.lv[l];
+        const int16_t* ct = &P.tabs[4 * (size_t)g.tabOffset];
+        const int16_t* rt = ct + 4 * (size_t)g.W;
+        const int PW = g.W + 2 * SD_EDGE, HPl = g.H + 2 * SD_EDGE, sH = P.lv[l - 1].H;
+        SdPyrTiles t;
+        t.tilesX = (PW + SD_PT_XSHIFT + SD_PT_TW - 1) / SD_PT_TW; t.tilesY = (HPl + SD_PT_TH - 1) / SD_PT_TH;
+        t.extOff = (int)ext.size();
+        int spanX = 0, spanY = 0;
+        for (int tx = 0; tx < t.tilesX; tx++) {
+            int lo = 1 << 30, hi = -1;
+            for (int k = 0; k < SD_PT_TW; k++) {
+                const int sx = ct[4 * refl(std::min(std::max(tx * SD_PT_TW - SD_PT_XSHIFT + k, 0), PW - 1) - SD_EDGE, g.W)];
+                lo = std::min(lo, sx); hi = std::max(hi, sx);
+            }
+            spanX = std::max(spanX, hi - lo + 2);
+            ext.push_back(lo);
+        }
+        for (int ty = 0; ty < t.tilesY; ty++) {
+            int lo = 1 << 30, hi = -1;
+            for (int k = 0; k < SD_PT_TH; k++) {
+                const int sy = rt[4 * refl(std::min(ty * SD_PT_TH + k, HPl - 1) - SD_EDGE, g.H)];
+                lo = std::min(lo, std::min(std::max(sy, 0), sH - 1)); hi = std::max(hi, std::min(std::max(sy + 1, 0), sH - 1));
+            }
+            spanY = std::max(spanY, hi - lo + 1);
+            ext.push_back(lo); ext.push_back(hi - lo + 1);
+        }
+        t.srcRowBytes = (spanX + 16 + 15) & ~15; t.srcRowsMax = spanY;
+        t.lds = (size_t)t.srcRowsMax * t.srcRowBytes + (size_t)t.srcRowsMax * SD_PT_TW * 2;
+        t.use = t.lds <= 48 * 1024 && g.W >= 40 && g.H >= 40;
+        tiles[l] = t;
+    }
+    SdDevBuf<int> d_ext;
+    if (!ext.empty()) {
+        HIPCHK(d_ext.alloc(ext.size() * 4));
+        HIPCHK(hipMemcpy(d_ext, ext.data(), ext.size() * 4, hipMemcpyHostToDevice));
+    }
+    b->d_pyrExt = std::move(d_ext);
+    b->pyrTiles = std::move(tiles);
+    return SD_OK;
+}
+
+// Once per workspace: the non-empty 128 x SD_BLUR_TR tiles of one image, level by level (k_blur_wide)
+static int ensure_blur_tiles(sd_batch* b)
+{
+    if (b->d_blurTiles) return SD_OK;
+    const SdPlan& P = b->plan;
+    std::vector<int> t;
+    for (int l = 0; l < P.nlevels; l++)
+        for (int ty = 0; ty * SD_BLUR_TR < P.lv[l].H; ty++)
+            for (int tx = 0; tx * 128 < P.lv[l].W; tx++) t.push_back(l | (tx << 8) | (ty << 16));
+    SdDevBuf<int> d_tiles;
+    HIPCHK(d_tiles.alloc(t.size() * 4));
+    HIPCHK(hipMemcpy(d_tiles, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    b->d_blurTiles = std::move(d_tiles);
+    b->nBlurTiles = (int)t.size();
+    return SD_OK;
+}
+
 // colorMode 0: 8-bit gray input; 1 / 2: 3-channel BGR / RGB, 3 / 4: 4-channel BGRA / RGBA input converted on the way into level 0
 static int extract_impl(sd_batch* b, const uint8_t* d_gray, size_t stride, size_t image_pitch, int n_images, void* stream_, int colorMode)
 {
@@ -493,6 +544,9 @@ static int extract_impl(sd_batch* b, const uint8_t* d_gray, size_t stride, size_
     const int bpp = colorMode == 0 ? 1 : (colorMode <= 2 ? 3 : 4), rgbOrder = (colorMode == 2 || colorMode == 4) ? 1 : 0;
     if (stride < (size_t)P.W * bpp) return set_err(SD_ERR_INVALID, "stride smaller than width");
     const int nl = P.nlevels;
+    int rc = ensure_pyr_tiles(b);                 // the per-workspace tile tables, built by the first extract
+    if (rc == SD_OK) rc = ensure_blur_tiles(b);
+    if (rc != SD_OK) return rc;
     {
         ProfScope ps(b, s, K_PYR0);
         const SdLevel& g = P.lv[0];
@@ -513,57 +567,16 @@ static int extract_impl(sd_batch* b, const uint8_t* d_gray, size_t stride, size_
         }
     }
     LAUNCH_CHECK("k_pyr_level0");
-    if (b->pyrTiles.empty()) {          // once per batch: LDS extents of k_pyr_level_tiles per level, or the per-thread kernel as a fallback
-        b->pyrTiles.assign(nl, SdPyrTiles());
-        auto refl = [](int p, int len) { if (p < 0) p = -p; if (p >= len) p = 2 * (len - 1) - p; return p; };
-        std::vector<int> ext;             // per level: source column origin of every tile column, (row origin, rows) of every tile row
-        for (int l = 1; l < nl; l++) {
-            const SdLevel& g = P.lv[l];
-            const int16_t* ct = &P.tabs[4 * (size_t)g.tabOffset];
-            const int16_t* rt = ct + 4 * (size_t)g.W;
-            const int PW = g.W + 2 * SD_EDGE, HPl = g.H + 2 * SD_EDGE, sH = P.lv[l - 1].H;
-            SdPyrTiles t;
-            t.tilesX = (PW + SD_PT_XSHIFT + SD_PT_TW - 1) / SD_PT_TW; t.tilesY = (HPl + SD_PT_TH - 1) / SD_PT_TH;
-            t.extOff = (int)ext.size();
-            int spanX = 0, spanY = 0;
-            for (int tx = 0; tx < t.tilesX; tx++) {
-                int lo = 1 << 30, hi = -1;
-                for (int k = 0; k < SD_PT_TW; k++) {
-                    const int sx = ct[4 * refl(std::min(std::max(tx * SD_PT_TW - SD_PT_XSHIFT + k, 0), PW - 1) - SD_EDGE, g.W)];
-                    lo = std::min(lo, sx); hi = std::max(hi, sx);
-                }
-                spanX = std::max(spanX, hi - lo + 2);
-                ext.push_back(lo);
-            }
-            for (int ty = 0; ty < t.tilesY; ty++) {
-                int lo = 1 << 30, hi = -1;
-                for (int k = 0; k < SD_PT_TH; k++) {
-                    const int sy = rt[4 * refl(std::min(ty * SD_PT_TH + k, HPl - 1) - SD_EDGE, g.H)];
-                    lo = std::min(lo, std::min(std::max(sy, 0), sH - 1)); hi = std::max(hi, std::min(std::max(sy + 1, 0), sH - 1));
-                }
-                spanY = std::max(spanY, hi - lo + 1);
-                ext.push_back(lo); ext.push_back(hi - lo + 1);
-            }
-            t.srcRowBytes = (spanX + 16 + 15) & ~15; t.srcRowsMax = spanY;
-            t.lds = (size_t)t.srcRowsMax * t.srcRowBytes + (size_t)t.srcRowsMax * SD_PT_TW * 2;
-            t.use = t.lds <= 48 * 1024 && g.W >= 40 && g.H >= 40;
-            b->pyrTiles[l] = t;
-        }
-        if (!ext.empty()) {
-            HIPCHK(hipMalloc((void**)&b->d_pyrExt, ext.size() * 4));
-            HIPCHK(hipMemcpy(b->d_pyrExt, ext.data(), ext.size() * 4, hipMemcpyHostToDevice));
-        }
-    }
     for (int l = 1; l < nl; l++) {
         ProfScope ps(b, s, K_PYR);
         const SdLevel& g = P.lv[l];
         const SdPyrTiles& t = b->pyrTiles[l];
         if (t.use) {
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pyr_level_tiles<SD_PT_TW, SD_PT_TH>), dim3(t.tilesX, t.tilesY, n_images), dim3(256), t.lds, s, b->d_pyr,
-                               (const short4*)b->d_tabs, b->d_plan, l, t.srcRowBytes, t.srcRowsMax, b->d_pyrExt + t.extOff);
+                               (const short4*)b->d_tabs.get(), b->d_plan, l, t.srcRowBytes, t.srcRowsMax, b->d_pyrExt + t.extOff);
         } else {                         // resize ratios too large for the LDS tile: one thread per 4 pixels x 4 rows
             dim3 blk(64, 4), grd(((g.W + 39 + 3) / 4 + 63) / 64, (g.H + 2 * SD_EDGE + 4 * SD_PYR_ROWS - 1) / (4 * SD_PYR_ROWS), n_images);
-            hipLaunchKernelGGL(k_pyr_level, grd, blk, 0, s, b->d_pyr, (const short4*)b->d_tabs, b->d_plan, l);
+            hipLaunchKernelGGL(k_pyr_level, grd, blk, 0, s, b->d_pyr, (const short4*)b->d_tabs.get(), b->d_plan, l);
         }
     }
     LAUNCH_CHECK("k_pyr_level");
@@ -572,15 +585,6 @@ static int extract_impl(sd_batch* b, const uint8_t* d_gray, size_t stride, size_
         // FAST so that it runs beside the quadtree both kernels stretch (0.45 + 0.35 ms -> 0.73 ms together): +0.8 % frames/s,
         // not worth a second stream and overlapped per-kernel timings — everything stays on one stream.)
         ProfScope ps(b, s, K_BLUR);
-        if (!b->d_blurTiles) {                                // once per batch: the non-empty 128 x SD_BLUR_TR tiles of one image, level by level
-            std::vector<int> t;
-            for (int l = 0; l < nl; l++)
-                for (int ty = 0; ty * SD_BLUR_TR < P.lv[l].H; ty++)
-                    for (int tx = 0; tx * 128 < P.lv[l].W; tx++) t.push_back(l | (tx << 8) | (ty << 16));
-            b->nBlurTiles = (int)t.size();
-            HIPCHK(hipMalloc((void**)&b->d_blurTiles, t.size() * 4));
-            HIPCHK(hipMemcpy(b->d_blurTiles, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-        }
         dim3 grd((unsigned)b->nBlurTiles * (unsigned)((n_images + 7) / 8 * 8));
         unsigned tapSum = 0;
         for (int i = 0; i < 7; i++) tapSum += b->hplan.taps[i];
@@ -655,9 +659,8 @@ int sd_batch_extract_host(sd_batch* b, const uint8_t* gray, size_t stride, size_
     const size_t tight = (size_t)P.W * P.H;
     const size_t need = tight * n_images;
     if (b->stageBytes < need) {
-        if (b->d_stage) (void)hipFree(b->d_stage);
-        b->d_stage = nullptr; b->stageBytes = 0;
-        HIPCHK(hipMalloc((void**)&b->d_stage, need));
+        b->stageBytes = 0;
+        HIPCHK(b->d_stage.alloc(need));
         b->stageBytes = need;
     }
     for (int i = 0; i < n_images; i++)
@@ -1105,7 +1108,7 @@ static int search_by_projection_impl(sd_batch* b, int pairBase, int n_pairs, con
         const size_t capA = (size_t)((cap + 15) & ~15);
         size_t lds = capA * (4 + 4 + 4 + 2 + 1 + 1 + 1) + 16;
         if (lds > 160 * 1024 - 256) return set_err(SD_ERR_UNSUPPORTED, "too many keypoints per image for the projection matcher's LDS tables");
-        if (lds > 64 * 1024) HIPCHK(hipFuncSetAttribute((const void*)k_proj_resolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(sd_raise_lds_limit((const void*)k_proj_resolve, (int)lds));
         hipLaunchKernelGGL(k_proj_resolve, dim3(n_pairs), dim3(64), lds, s, KPUN(b), b->d_count, b->d_flags, b->d_pcand + pOff * SD_PROJ_K, b->d_pncand + pOff,
                            d_occupied, b->d_match + pOff, b->d_pairs + pOff * 2, b->d_npairs + pairBase, b->d_nmatch + pairBase, b->d_plan, checkOrientation,
                            dIdx, d_active, redoBelow, b->d_err);
@@ -1115,6 +1118,21 @@ static int search_by_projection_impl(sd_batch* b, int pairBase, int n_pairs, con
     b->dlPairs = std::max(pairBase + n_pairs, pairBase ? b->dlPairs : 0);
     if (b->pairCam.size() != (size_t)b->maxImages) b->pairCam.assign(b->maxImages, sd_camera());
     for (int p = 0; p < n_pairs; p++) b->pairCam[pairBase + p] = *cam;
+    return SD_OK;
+}
+
+// The scratch of sd_batch_search_local_map: frame / offset table, and candidates that grow with the largest local map seen (old ones freed first)
+static int ensure_local_map(sd_batch* b, int total, hipStream_t s)
+{
+    if (!b->d_lmIdx) HIPCHK(b->d_lmIdx.alloc((size_t)(2 * b->maxImages + 2) * sizeof(int)));
+    if (total <= b->lmCap) return SD_OK;
+    HIPCHK(hipStreamSynchronize(s));
+    const int want = std::max(total, 2 * b->lmCap);
+    b->lmCap = 0; b->d_lmCand.reset(); b->d_lmN.reset(); b->d_lmOvf.reset();
+    SdDevBuf<unsigned> cand; SdDevBuf<uint8_t> n, ovf;
+    HIPCHK(cand.alloc((size_t)want * SD_PROJ_K * 4)); HIPCHK(n.alloc((size_t)want)); HIPCHK(ovf.alloc((size_t)want));
+    b->d_lmCand = std::move(cand); b->d_lmN = std::move(n); b->d_lmOvf = std::move(ovf);
+    b->lmCap = want;
     return SD_OK;
 }
 
@@ -1142,16 +1160,8 @@ int sd_batch_search_local_map(sd_batch* b, int n_frames, const int32_t* frame_in
     if (b->plan.kpCap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
     hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
     b->lastStream = s;
-    if (total > b->lmCap) {                       // candidate scratch grows with the largest local map seen
-        HIPCHK(hipStreamSynchronize(s));
-        if (b->d_lmCand) { (void)hipFree(b->d_lmCand); (void)hipFree(b->d_lmN); (void)hipFree(b->d_lmOvf); b->d_lmCand = nullptr; b->d_lmN = b->d_lmOvf = nullptr; }
-        const int want = std::max(total, 2 * b->lmCap);
-        HIPCHK(hipMalloc((void**)&b->d_lmCand, (size_t)want * SD_PROJ_K * 4));
-        HIPCHK(hipMalloc((void**)&b->d_lmN, (size_t)want));
-        HIPCHK(hipMalloc((void**)&b->d_lmOvf, (size_t)want));
-        b->lmCap = want;
-    }
-    if (!b->d_lmIdx) HIPCHK(hipMalloc((void**)&b->d_lmIdx, (size_t)(2 * b->maxImages + 2) * sizeof(int)));
+    int rc = ensure_local_map(b, total, s);
+    if (rc != SD_OK) return rc;
     int* dFrameOf = b->d_lmIdx;
     int* dOff = b->d_lmIdx + b->maxImages;
     HIPCHK(hipMemcpyAsync(dFrameOf, frame_index, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
@@ -1192,9 +1202,9 @@ static int vocab_from_lines(sd_vocab** out, const SdVocabLines& lines)
     if (!vocab_pack(lines, blob)) return set_err(SD_ERR_INVALID, "vocabulary: a node names a parent that does not precede it");
     sd_vocab* v = new sd_vocab();
     memcpy(&v->h, blob.data(), sizeof(SdVocabHeader));
-    if (hipMalloc(&v->d_blob, blob.size()) != hipSuccess) { delete v; return set_err(SD_ERR_HIP, "hipMalloc(vocabulary)"); }
-    v->owned = true;
-    if (hipMemcpy(v->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(v->d_blob); delete v; return set_err(SD_ERR_HIP, "hipMemcpy(vocabulary)"); }
+    if (v->owned.alloc(blob.size()) != hipSuccess) { delete v; return set_err(SD_ERR_HIP, "hipMalloc(vocabulary)"); }
+    v->d_blob = v->owned;
+    if (hipMemcpy(v->d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess) { delete v; return set_err(SD_ERR_HIP, "hipMemcpy(vocabulary)"); }
     vocab_bind(v);
     *out = v;
     return SD_OK;
@@ -1241,18 +1251,13 @@ int sd_vocab_from_packed_device(sd_vocab** out, void* d_blob, size_t bytes)
         chk.offWordId != h.offWordId || chk.offDesc != h.offDesc)
         return set_err(SD_ERR_INVALID, "not a packed vocabulary");
     sd_vocab* v = new sd_vocab();
-    v->h = h; v->d_blob = d_blob; v->owned = false;
+    v->h = h; v->d_blob = d_blob;
     vocab_bind(v);
     *out = v;
     return SD_OK;
 }
 
-void sd_vocab_destroy(sd_vocab* v)
-{
-    if (!v) return;
-    if (v->owned && v->d_blob) (void)hipFree(v->d_blob);
-    delete v;
-}
+void sd_vocab_destroy(sd_vocab* v) { delete v; }
 
 int sd_vocab_info(const sd_vocab* v, int* k, int* L, int* scoring, int* weighting, int* n_nodes, int* n_words)
 {
@@ -1294,18 +1299,19 @@ int sd_vocab_download_nodes(const sd_vocab* v, int32_t* parent, int32_t* n_child
     return SD_OK;
 }
 
-static int bow_alloc(sd_batch* b)
+static int ensure_bow(sd_batch* b)
 {
     if (b->d_bowWordF) return SD_OK;
     const size_t nI = b->maxImages, cap = b->plan.kpCap;
-    HIPCHK(hipMalloc((void**)&b->d_bowWordF, nI * cap * 4)); HIPCHK(hipMalloc((void**)&b->d_bowWF, nI * cap * 8));
-    HIPCHK(hipMalloc((void**)&b->d_bowNidF, nI * cap * 4)); HIPCHK(hipMalloc((void**)&b->d_fvNode, nI * cap * 4));
-    HIPCHK(hipMalloc((void**)&b->d_fvFeat, nI * cap * 4)); HIPCHK(hipMalloc((void**)&b->d_fvRunStart, nI * (cap + 1) * 4));
-    HIPCHK(hipMalloc((void**)&b->d_fvRunNode, nI * cap * 4)); HIPCHK(hipMalloc((void**)&b->d_bowWord, nI * cap * 4));
-    HIPCHK(hipMalloc((void**)&b->d_bowVal, nI * cap * 8)); HIPCHK(hipMalloc((void**)&b->d_bowMeta, nI * 4 * 4));
-    HIPCHK(hipMalloc((void**)&b->d_bowImg, nI * 4));
-    HIPCHK(hipMemset(b->d_bowMeta, 0, nI * 16));
+    SdDevBuf<unsigned> wordF, nidF, fvNode, fvFeat, fvRunNode, word; SdDevBuf<double> wF, val; SdDevBuf<int> fvRunStart, meta, img;
+    HIPCHK(wordF.alloc(nI * cap * 4)); HIPCHK(wF.alloc(nI * cap * 8)); HIPCHK(nidF.alloc(nI * cap * 4)); HIPCHK(fvNode.alloc(nI * cap * 4));
+    HIPCHK(fvFeat.alloc(nI * cap * 4)); HIPCHK(fvRunStart.alloc(nI * (cap + 1) * 4)); HIPCHK(fvRunNode.alloc(nI * cap * 4)); HIPCHK(word.alloc(nI * cap * 4));
+    HIPCHK(val.alloc(nI * cap * 8)); HIPCHK(meta.alloc(nI * 4 * 4)); HIPCHK(img.alloc(nI * 4));
+    HIPCHK(hipMemset(meta, 0, nI * 16));
+    b->d_bowWF = std::move(wF); b->d_bowNidF = std::move(nidF); b->d_fvNode = std::move(fvNode); b->d_fvFeat = std::move(fvFeat); b->d_fvRunStart = std::move(fvRunStart);
+    b->d_fvRunNode = std::move(fvRunNode); b->d_bowWord = std::move(word); b->d_bowVal = std::move(val); b->d_bowMeta = std::move(meta); b->d_bowImg = std::move(img);
     b->bowValid.assign(nI, 0);
+    b->d_bowWordF = std::move(wordF);           // last: it marks the group as present
     return SD_OK;
 }
 
@@ -1320,7 +1326,7 @@ int sd_batch_compute_bow(sd_batch* b, const sd_vocab* v, int n_images, const int
     int sortN = 256;                     // LDS capacity of k_bow_finalize's sort: its per-image sort size starts at 256 too
     while (sortN < cap) sortN <<= 1;
     if (sortN > 8192) return set_err(SD_ERR_UNSUPPORTED, "compute_bow: more than 8192 keypoints per image");
-    int rc = bow_alloc(b);
+    int rc = ensure_bow(b);
     if (rc != SD_OK) return rc;
     hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
     b->lastStream = s;
@@ -1348,7 +1354,7 @@ int sd_batch_bow_device(sd_batch* b, uint32_t** d_bow_word, double** d_bow_value
                         int32_t** d_meta, int* cap)
 {
     if (!b) return SD_ERR_INVALID;
-    int rc = bow_alloc(b);
+    int rc = ensure_bow(b);
     if (rc != SD_OK) return rc;
     if (d_bow_word) *d_bow_word = b->d_bowWord; if (d_bow_value) *d_bow_value = b->d_bowVal;
     if (d_fv_node) *d_fv_node = b->d_fvNode; if (d_fv_feature) *d_fv_feature = b->d_fvFeat;
@@ -1418,6 +1424,20 @@ int sd_batch_search_by_bow(sd_batch* b, int n_pairs, const int32_t* kf_index, co
     return SD_OK;
 }
 
+// The model-fit buffers of sd_batch_estimate_motion (a tracker allocates them at creation)
+static int ensure_motion(sd_batch* b)
+{
+    if (b->d_moPts) return SD_OK;
+    const size_t nI = b->maxImages, cap = b->plan.kpCap;
+    SdDevBuf<float> pts; SdDevBuf<SdMotionNorm> norm; SdDevBuf<int> counts; SdDevBuf<double> models; SdDevBuf<uint8_t> maskH, maskF; SdDevBuf<SdMotionResult> res;
+    HIPCHK(pts.alloc(nI * cap * 16)); HIPCHK(norm.alloc(nI * sizeof(SdMotionNorm))); HIPCHK(counts.alloc(nI * SD_MOTION_K * 4));
+    HIPCHK(models.alloc(nI * SD_MOTION_K * 72)); HIPCHK(maskH.alloc(nI * cap)); HIPCHK(maskF.alloc(nI * cap)); HIPCHK(res.alloc(nI * sizeof(SdMotionResult)));
+    b->d_moNorm = std::move(norm); b->d_moCounts = std::move(counts); b->d_moModels = std::move(models); b->d_moMaskH = std::move(maskH);
+    b->d_moMaskF = std::move(maskF); b->d_moRes = std::move(res);
+    b->d_moPts = std::move(pts);                // last: it marks the group as present
+    return SD_OK;
+}
+
 // The model fit of Tracking::TrackHomo (src/Tracking.cc:1026-1075) for every pair of the preceding
 // sd_batch_search_by_projection: points_last / points_current -> H, F, inlier masks, the choice 1 (H) / 2 (F) / 0.
 static int estimate_motion_impl(sd_batch* b, int n_pairs, void* stream_, const int* d_active, int minMatches);
@@ -1431,12 +1451,9 @@ static int estimate_motion_impl(sd_batch* b, int n_pairs, void* stream_, const i
     if (n_pairs <= 0) return set_err(SD_ERR_STATE, "estimate_motion: no preceding sd_batch_search_by_projection");
     hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
     b->lastStream = s;
-    const size_t nI = b->maxImages, cap = b->plan.kpCap;
-    if (!b->d_moPts) {
-        HIPCHK(hipMalloc((void**)&b->d_moPts, nI * cap * 16)); HIPCHK(hipMalloc((void**)&b->d_moNorm, nI * sizeof(SdMotionNorm)));
-        HIPCHK(hipMalloc((void**)&b->d_moCounts, nI * SD_MOTION_K * 4)); HIPCHK(hipMalloc((void**)&b->d_moModels, nI * SD_MOTION_K * 72)); HIPCHK(hipMalloc((void**)&b->d_moMaskH, nI * cap));
-        HIPCHK(hipMalloc((void**)&b->d_moMaskF, nI * cap)); HIPCHK(hipMalloc((void**)&b->d_moRes, nI * sizeof(SdMotionResult)));
-    }
+    const size_t cap = b->plan.kpCap;
+    int rc = ensure_motion(b);
+    if (rc != SD_OK) return rc;
     {
         ProfScope ps(b, s, K_MOTION_P);
         hipLaunchKernelGGL(k_motion_prepare, dim3(n_pairs), dim3(256), cap * 16, s, KPUN(b), b->d_pairs, b->d_npairs, b->d_pairIdx, (int)cap, b->d_moPts, b->d_moNorm,
@@ -1520,11 +1537,11 @@ int sd_batch_set_distortion(sd_batch* b, const float* K4, const float* dist5)
 {
     if (!b || !K4 || !dist5) return SD_ERR_INVALID;
     if (dist5[0] == 0.0f) { b->hasDist = false; return SD_OK; }       // mDistCoef.at<float>(0) == 0.0 -> mvKeysUn = mvKeys (Frame.cc:814-818)
-    const size_t nI = b->maxImages, cap = b->plan.kpCap;
     if (!b->d_kpUn) {
-        HIPCHK(hipMalloc((void**)&b->d_kpUn, nI * cap * sizeof(sd_keypoint)));
-        HIPCHK(hipMalloc((void**)&b->d_kpDUn, nI * cap * sizeof(sd_keypoint)));
-        HIPCHK(hipMalloc((void**)&b->d_unSlots, nI * 4));
+        const size_t nI = b->maxImages, cap = b->plan.kpCap;
+        SdDevBuf<sd_keypoint> kpUn, kpDUn; SdDevBuf<int> slots;
+        HIPCHK(kpUn.alloc(nI * cap * sizeof(sd_keypoint))); HIPCHK(kpDUn.alloc(nI * cap * sizeof(sd_keypoint))); HIPCHK(slots.alloc(nI * 4));
+        b->d_kpDUn = std::move(kpDUn); b->d_unSlots = std::move(slots); b->d_kpUn = std::move(kpUn);      // d_kpUn last: it marks the group as present
     }
     b->dist = to_distortion(K4, dist5);
     b->hasDist = true;
@@ -1611,7 +1628,7 @@ int sd_batch_copy_frame(sd_batch* b, int src, int dst, void* stream_)
     hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
     b->lastStream = s;
     const size_t cap = b->plan.kpCap;
-#define CP(ptr, elemBytes) do { if (nseg < 24) { segs.src[nseg] = (const char*)(ptr) + src * cap * (elemBytes); segs.dst[nseg] = (char*)(ptr) + dst * cap * (elemBytes); segs.bytes[nseg] = (unsigned)(cap * (elemBytes)); nseg++; } } while (0)
+#define CP(ptr, elemBytes) do { if (nseg < 24) { segs.src[nseg] = (const char*)(ptr).get() + src * cap * (elemBytes); segs.dst[nseg] = (char*)(ptr).get() + dst * cap * (elemBytes); segs.bytes[nseg] = (unsigned)(cap * (elemBytes)); nseg++; } } while (0)
     SdCopySegs segs;
     int nseg = 0;
     CP(b->d_kp, sizeof(sd_keypoint)); CP(b->d_desc, 32); CP(b->d_uright, 4); CP(b->d_depth, 4); CP(b->d_sad, 4);
@@ -1669,8 +1686,8 @@ int sd_batch_download_matches(sd_batch* b, int pair, int32_t* match, int32_t* pa
 #define SD_POSE_CAM_RING 8
 #define SD_POSE_MAX_DEVICES 64
 namespace {
-struct PoseCamRing { sd_camera* d[SD_POSE_CAM_RING] = {}; size_t cap[SD_POSE_CAM_RING] = {}; hipEvent_t done[SD_POSE_CAM_RING] = {}; int next = 0; };
-PoseCamRing g_poseCams[SD_POSE_MAX_DEVICES];
+struct PoseCamRing { SdDevBuf<sd_camera> d[SD_POSE_CAM_RING]; size_t cap[SD_POSE_CAM_RING] = {}; hipEvent_t done[SD_POSE_CAM_RING] = {}; int next = 0; };
+PoseCamRing* const g_poseCams = new PoseCamRing[SD_POSE_MAX_DEVICES];     // never destroyed: no device call after the runtime has shut down at exit
 std::mutex g_poseCamsMu;
 }
 
@@ -1697,9 +1714,8 @@ int sd_pose_optimize_device(int n_problems, const int32_t* d_edge_offset, const 
     if (C.done[k]) HIPCHK(hipEventSynchronize(C.done[k]));     // the launch that last used this table has read it
     else HIPCHK(hipEventCreateWithFlags(&C.done[k], hipEventDisableTiming));
     if (C.cap[k] < (size_t)n_problems) {
-        if (C.d[k]) HIPCHK(hipFree(C.d[k]));
-        C.d[k] = nullptr; C.cap[k] = 0;
-        HIPCHK(hipMalloc((void**)&C.d[k], (size_t)n_problems * sizeof(sd_camera)));
+        C.cap[k] = 0;
+        HIPCHK(C.d[k].alloc((size_t)n_problems * sizeof(sd_camera)));
         C.cap[k] = (size_t)n_problems;
     }
     HIPCHK(hipMemcpyAsync(C.d[k], cams, (size_t)n_problems * sizeof(sd_camera), hipMemcpyHostToDevice, s));
@@ -1724,46 +1740,33 @@ int sd_pose_optimize_host(int n_problems, const int32_t* edge_offset, const sd_p
     if (nE > 0 && (!edges || !outlier)) return set_err(SD_ERR_INVALID, "bad pose_optimize arguments");
     int rc = require_device();
     if (rc != SD_OK) return rc;
-    int32_t* d_off = nullptr; sd_pose_edge* d_e = nullptr; float* d_T = nullptr; uint8_t* d_o = nullptr; int32_t* d_g = nullptr;
-    hipError_t e = hipMalloc((void**)&d_off, (size_t)(n_problems + 1) * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_e, std::max<size_t>(nE, 1) * sizeof(sd_pose_edge));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_T, (size_t)n_problems * 64);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_o, std::max<size_t>(nE, 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&d_g, (size_t)n_problems * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_off, edge_offset, (size_t)(n_problems + 1) * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && nE) e = hipMemcpy(d_e, edges, nE * sizeof(sd_pose_edge), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_T, Tcw, (size_t)n_problems * 64, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = sd_pose_optimize_device(n_problems, d_off, d_e, cams, d_T, d_o, d_g, nullptr);
-        if (rc == SD_OK) e = hipStreamSynchronize(nullptr);
-        if (rc == SD_OK && e == hipSuccess) e = hipMemcpy(Tcw, d_T, (size_t)n_problems * 64, hipMemcpyDeviceToHost);
-        if (rc == SD_OK && e == hipSuccess && nE) e = hipMemcpy(outlier, d_o, nE, hipMemcpyDeviceToHost);
-        if (rc == SD_OK && e == hipSuccess) e = hipMemcpy(n_good, d_g, (size_t)n_problems * 4, hipMemcpyDeviceToHost);
-    }
-    for (void* p : {(void*)d_off, (void*)d_e, (void*)d_T, (void*)d_o, (void*)d_g}) if (p) (void)hipFree(p);
+    SdDevBuf<int32_t> d_off, d_g; SdDevBuf<sd_pose_edge> d_e; SdDevBuf<float> d_T; SdDevBuf<uint8_t> d_o;
+    HIPCHK(d_off.alloc((size_t)(n_problems + 1) * 4)); HIPCHK(d_e.alloc(std::max<size_t>(nE, 1) * sizeof(sd_pose_edge)));
+    HIPCHK(d_T.alloc((size_t)n_problems * 64)); HIPCHK(d_o.alloc(std::max<size_t>(nE, 1))); HIPCHK(d_g.alloc((size_t)n_problems * 4));
+    HIPCHK(hipMemcpy(d_off, edge_offset, (size_t)(n_problems + 1) * 4, hipMemcpyHostToDevice));
+    if (nE) HIPCHK(hipMemcpy(d_e, edges, nE * sizeof(sd_pose_edge), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_T, Tcw, (size_t)n_problems * 64, hipMemcpyHostToDevice));
+    rc = sd_pose_optimize_device(n_problems, d_off, d_e, cams, d_T, d_o, d_g, nullptr);
     if (rc != SD_OK) return rc;
-    HIPCHK(e);
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(Tcw, d_T, (size_t)n_problems * 64, hipMemcpyDeviceToHost));
+    if (nE) HIPCHK(hipMemcpy(outlier, d_o, nE, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n_good, d_g, (size_t)n_problems * 4, hipMemcpyDeviceToHost));
     return SD_OK;
 }
 
-static int pose_alloc(sd_batch* b)
+static int ensure_pose(sd_batch* b)
 {
     if (b->d_poseEdges) return SD_OK;
     const size_t nI = b->maxImages, cap = b->plan.kpCap;
-    HIPCHK(hipMalloc((void**)&b->d_poseEdges, nI * cap * sizeof(sd_pose_edge)));
-    HIPCHK(hipMalloc((void**)&b->d_poseFirst, nI * 4));
-    HIPCHK(hipMalloc((void**)&b->d_poseLast, nI * 4));
-    HIPCHK(hipMalloc((void**)&b->d_poseT, nI * 64));
-    HIPCHK(hipMalloc((void**)&b->d_poseOut, nI * cap));
-    HIPCHK(hipMalloc((void**)&b->d_poseGood, nI * 4));
-    HIPCHK(hipMalloc((void**)&b->d_poseCam, nI * sizeof(sd_camera)));
-    HIPCHK(hipMalloc((void**)&b->d_poseMap, nI * 4));
-    HIPCHK(hipMalloc((void**)&b->d_poseRan, nI * 4));
-    HIPCHK(hipMalloc((void**)&b->d_poseTin, nI * 64));
-    HIPCHK(hipMemset(b->d_poseFirst, 0, nI * 4));
-    HIPCHK(hipMemset(b->d_poseLast, 0, nI * 4));
-    HIPCHK(hipMemset(b->d_poseGood, 0, nI * 4));
-    HIPCHK(hipMemset(b->d_poseRan, 0, nI * 4));
+    SdDevBuf<sd_pose_edge> edges; SdDevBuf<int> first, last, good, map, ran; SdDevBuf<float> T, Tin; SdDevBuf<uint8_t> out; SdDevBuf<sd_camera> cam;
+    HIPCHK(edges.alloc(nI * cap * sizeof(sd_pose_edge))); HIPCHK(first.alloc(nI * 4)); HIPCHK(last.alloc(nI * 4)); HIPCHK(T.alloc(nI * 64));
+    HIPCHK(out.alloc(nI * cap)); HIPCHK(good.alloc(nI * 4)); HIPCHK(cam.alloc(nI * sizeof(sd_camera))); HIPCHK(map.alloc(nI * 4));
+    HIPCHK(ran.alloc(nI * 4)); HIPCHK(Tin.alloc(nI * 64));
+    HIPCHK(hipMemset(first, 0, nI * 4)); HIPCHK(hipMemset(last, 0, nI * 4)); HIPCHK(hipMemset(good, 0, nI * 4)); HIPCHK(hipMemset(ran, 0, nI * 4));
+    b->d_poseFirst = std::move(first); b->d_poseLast = std::move(last); b->d_poseT = std::move(T); b->d_poseOut = std::move(out); b->d_poseGood = std::move(good);
+    b->d_poseCam = std::move(cam); b->d_poseMap = std::move(map); b->d_poseRan = std::move(ran); b->d_poseTin = std::move(Tin);
+    b->d_poseEdges = std::move(edges);          // last: it marks the group as present
     return SD_OK;
 }
 
@@ -1779,7 +1782,7 @@ static int batch_pose_impl(sd_batch* b, int n_pairs, const int32_t* pair_index, 
         if (pair_index[k] < 0 || pair_index[k] >= b->dlPairs) return set_err(SD_ERR_STATE, "pose_optimize: pair holds no projection matches");
         if (seen[pair_index[k]]++) return set_err(SD_ERR_INVALID, "pose_optimize: a pair is listed twice");
     }
-    int rc = pose_alloc(b);
+    int rc = ensure_pose(b);
     if (rc != SD_OK) return rc;
     b->lastStream = s;
     b->hPoseMap.assign(pair_index, pair_index + n_pairs);
@@ -1994,7 +1997,7 @@ static_assert(sizeof(sd_frame_boxes) == sizeof(SdFrameBoxes) && offsetof(sd_fram
 int sd_batch_boxes_device(sd_batch* b, sd_frame_boxes** d_frame_boxes)
 {
     if (!b || !d_frame_boxes) return SD_ERR_INVALID;
-    *d_frame_boxes = (sd_frame_boxes*)b->d_fb;
+    *d_frame_boxes = (sd_frame_boxes*)b->d_fb.get();
     return SD_OK;
 }
 
@@ -2200,6 +2203,20 @@ int sd_batch_reset_kernel_times(sd_batch* b)
     return SD_OK;
 }
 
+// The scratch of sd_batch_backproject_dense: `need` 64-bit words of point marks, grown as needed (the old group is freed first)
+static int ensure_cloud(sd_batch* b, size_t need, int rows3, hipStream_t s)
+{
+    if (b->cloudCap >= need) return SD_OK;
+    HIPCHK(hipStreamSynchronize(s));
+    b->cloudCap = 0; b->d_cloudBits.reset(); b->d_cloudRows.reset(); b->d_cloudT.reset(); b->d_cloudSlots.reset();
+    SdDevBuf<unsigned long long> bits; SdDevBuf<int> rows, slots; SdDevBuf<double> T;
+    HIPCHK(bits.alloc(need * 8)); HIPCHK(rows.alloc((size_t)b->maxImages * rows3 * 2 * 4));
+    HIPCHK(T.alloc((size_t)b->maxImages * 16 * 8)); HIPCHK(slots.alloc((size_t)b->maxImages * 4));
+    b->d_cloudBits = std::move(bits); b->d_cloudRows = std::move(rows); b->d_cloudT = std::move(T); b->d_cloudSlots = std::move(slots);
+    b->cloudCap = need;
+    return SD_OK;
+}
+
 // PointCloudMapping::generatePointCloud (src/pointcloudmapping.cc:59-103) for frame slots of the batch
 int sd_batch_backproject_dense(sd_batch* b, int n_frames, const int32_t* slots, const uint8_t* d_color, size_t color_stride,
                                size_t color_pitch, const uint16_t* d_depth, size_t depth_stride_elems, size_t depth_pitch_elems,
@@ -2218,15 +2235,8 @@ int sd_batch_backproject_dense(sd_batch* b, int n_frames, const int32_t* slots, 
     if (n_frames == 0) return SD_OK;
     for (int f = 0; f < n_frames; f++) if (!slot_ok(b, slots[f])) return set_err(SD_ERR_STATE, "backproject_dense: slot holds no frame");
     const size_t need = (size_t)b->maxImages * rows3 * words;
-    if (b->cloudCap < need) {
-        HIPCHK(hipStreamSynchronize(s));
-        if (b->d_cloudBits) { (void)hipFree(b->d_cloudBits); (void)hipFree(b->d_cloudRows); (void)hipFree(b->d_cloudT); (void)hipFree(b->d_cloudSlots); b->d_cloudBits = nullptr; b->d_cloudRows = nullptr; b->d_cloudT = nullptr; b->d_cloudSlots = nullptr; }
-        HIPCHK(hipMalloc((void**)&b->d_cloudBits, need * 8));
-        HIPCHK(hipMalloc((void**)&b->d_cloudRows, (size_t)b->maxImages * rows3 * 2 * 4));
-        HIPCHK(hipMalloc((void**)&b->d_cloudT, (size_t)b->maxImages * 16 * 8));
-        HIPCHK(hipMalloc((void**)&b->d_cloudSlots, (size_t)b->maxImages * 4));
-        b->cloudCap = need;
-    }
+    int rc = ensure_cloud(b, need, rows3, s);
+    if (rc != SD_OK) return rc;
     HIPCHK(hipMemcpyAsync(b->d_cloudT, Twc_host, (size_t)n_frames * 128, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(b->d_cloudSlots, slots, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
     SdCloudArgs A;

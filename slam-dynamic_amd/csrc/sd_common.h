@@ -1,5 +1,5 @@
 // Internal helpers shared by the translation units of libsd_frontend.so (sd_api.hip: front end + tracker; sd_yolo_api.hip: detector):
-// the thread-local error text behind sd_last_error() and the two return-on-error macros.
+// the thread-local error text behind sd_last_error(), the two return-on-error macros, the owning device buffer and the dynamic-LDS limit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string>
@@ -7,6 +7,27 @@
 
 int sd_set_err(int code, const std::string& msg);        // defined in sd_api.hip
 #define set_err sd_set_err
+
+// Raises the dynamic-LDS limit of `kernel` on the current device to `bytes`: nothing to do at or below the 64 KB default, and the limit only
+// ever grows (workspaces and detectors of different sizes share the kernels).  Defined in sd_api.hip.
+hipError_t sd_raise_lds_limit(const void* kernel, int bytes);
+
+// Device memory owned by one object: hipFree on destruction, move-only, read as a plain T* wherever a pointer is expected.
+template <typename T>
+class SdDevBuf {
+public:
+    SdDevBuf() = default;
+    SdDevBuf(SdDevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }        // declaring the moves deletes the copies
+    SdDevBuf& operator=(SdDevBuf&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    ~SdDevBuf() { reset(); }
+    // frees what the buffer held, then allocates `bytes`; on failure the buffer stays empty
+    hipError_t alloc(size_t bytes) { reset(); void* p = nullptr; hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) p_ = (T*)p; return e; }
+    void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; }
+    T* get() const { return p_; }
+    operator T*() const { return p_; }
+private:
+    T* p_ = nullptr;
+};
 
 #define HIPCHK(call)                                                                                      \
     do {                                                                                                  \

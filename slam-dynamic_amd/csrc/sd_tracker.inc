@@ -9,7 +9,7 @@
 
 struct sd_tracker {
     sd_tracker_params p;
-    sd_batch* b = nullptr;
+    std::unique_ptr<sd_batch> b;
     int S = 0, ipl = 1, nCur = 0, R = 0, ring0 = 0;
     struct QE { double t; int slot; int hasBoxes; int frameId; };
     struct Lane {
@@ -21,19 +21,19 @@ struct sd_tracker {
         double lastObjects[SD_MAXB][4]; int lastIdx[SD_MAXB]; uint8_t lastOmit[SD_MAXB]; double lastVel[SD_MAXB][2];
     };
     std::vector<Lane> lanes;
-    int* d_want = nullptr; int* d_active = nullptr; int* d_activeLast = nullptr; int* d_slotList = nullptr;
-    SdLaneSummary* d_sum = nullptr;
+    SdDevBuf<int> d_want, d_active, d_activeLast, d_slotList;
+    SdDevBuf<SdLaneSummary> d_sum;
     SdLaneSummary* h_sum = nullptr;        // pinned
-    uint8_t* d_hostImg = nullptr; uint16_t* d_hostDepth = nullptr;      // staging of sd_tracker_track_host
+    SdDevBuf<uint8_t> d_hostImg; SdDevBuf<uint16_t> d_hostDepth;      // staging of sd_tracker_track_host
     // host staging (must outlive the asynchronous uploads of a call)
     std::vector<double> hBoxes; std::vector<int32_t> hNb, hIdx, hSlots, hCur, hRef, hLast, hWant, hActiveLast, hResetSlots;
     std::vector<uint8_t> hOmit; std::vector<double> hVel;
     std::vector<float> hI, hTcw, hTrw, hTlw, hTwc;
     std::vector<std::vector<float>> poseOfSlot;   // Tcw of the frame kept in a ring slot
     // monocular: mpIniORBextractor (Tracking.cc:127-128) and its workspace; the lanes' results are moved into `b` (same row stride)
-    sd_extractor* exIni = nullptr; sd_batch* bIni = nullptr;
+    std::unique_ptr<sd_extractor> exIni; std::unique_ptr<sd_batch> bIni;
     // time-batched mode (sd_tracker_prefetch): the history-free part of up to 2 x lookahead frames per lane lives in `bp`
-    sd_batch* bp[2] = {nullptr, nullptr};                                              // one workspace per outstanding block
+    std::unique_ptr<sd_batch> bp[2];                                                   // one workspace per outstanding block
     struct Block { int n = 0, next = 0; hipEvent_t ready = nullptr; };                 // frames of the block, `next` consumed so far
     Block blocks[2]; int blockHead = 0, blockCount = 0;
     // caller-owned SLAM state (sd_tracker_set_state); empty = the automatic rule of the sharded batch mode
@@ -44,21 +44,13 @@ struct sd_tracker {
     bool notInitialised(int l) const { return state.empty() ? lanes[l].frameNo == 0 : !(state[l] & 1); }         // mState == NOT_INITIALIZED on entry to Track_new
     bool useIniExtractor(int l) const { return bIni && (state.empty() ? lanes[l].frameNo < 2 : !(state[l] & 1)); } // GrabImageMonocular, Tracking.cc:335-338
     bool canTrackHomo(int l) const { return state.empty() ? lanes[l].frameNo >= 2 : (state[l] & 2) != 0; }       // mState==OK && !mVelocity.empty(), Tracking.cc:971
+    ~sd_tracker()
+    {
+        if (b) (void)hipDeviceSynchronize();
+        if (h_sum) (void)hipHostFree(h_sum);
+        for (auto& bl : blocks) if (bl.ready) (void)hipEventDestroy(bl.ready);
+    }
 };
-
-static void tracker_free(sd_tracker* t)
-{
-    if (!t) return;
-    void* ptrs[] = {t->d_want, t->d_active, t->d_activeLast, t->d_slotList, t->d_sum, t->d_hostImg, t->d_hostDepth};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (t->h_sum) (void)hipHostFree(t->h_sum);
-    if (t->b) { (void)hipDeviceSynchronize(); batch_free(t->b); }
-    if (t->bIni) batch_free(t->bIni);
-    for (sd_batch* q : t->bp) if (q) batch_free(q);
-    for (auto& bl : t->blocks) if (bl.ready) (void)hipEventDestroy(bl.ready);
-    delete t->exIni;
-    delete t;
-}
 
 static void tracker_reset_lanes(sd_tracker* t)
 {
@@ -76,7 +68,7 @@ int sd_tracker_create(sd_tracker** out, sd_extractor* ex, const sd_tracker_param
         (p->depth_type != SD_DEPTH_U16 && p->depth_type != SD_DEPTH_F32))
         return set_err(SD_ERR_INVALID, "bad tracker parameters");
     if (p->sensor != SD_SENSOR_MONOCULAR && !(p->cam.mbf > 0)) return set_err(SD_ERR_INVALID, "Camera.bf must be positive");
-    sd_tracker* t = new sd_tracker();
+    std::unique_ptr<sd_tracker> t(new sd_tracker());
     t->p = *p;
     t->S = p->n_lanes;
     t->ipl = p->sensor == SD_SENSOR_STEREO ? 2 : 1;
@@ -86,56 +78,43 @@ int sd_tracker_create(sd_tracker** out, sd_extractor* ex, const sd_tracker_param
     int minCap = 0;
     if (p->sensor == SD_SENSOR_MONOCULAR && p->ini_features > 0 && p->ini_features != ex->prm.nfeatures) {
         // mpIniORBextractor = new ORBextractor(2*nFeatures, fScaleFactor, nLevels, fIniThFAST, fMinThFAST) (Tracking.cc:127-128)
-        t->exIni = new sd_extractor(*ex);
+        t->exIni.reset(new sd_extractor(*ex));
         sd_params_init(t->exIni->prm, p->ini_features, (float)ex->prm.scaleFactor, ex->prm.nlevels, ex->prm.iniTh, ex->prm.minTh);
         memcpy(t->exIni->prm.blurTaps, ex->prm.blurTaps, sizeof(ex->prm.blurTaps));
         SdPlan a, c;
-        if (!sd_plan_build(a, ex->prm, p->width, p->height) || !sd_plan_build(c, t->exIni->prm, p->width, p->height)) {
-            const std::string m = a.error.empty() ? c.error : a.error;
-            delete t->exIni; delete t;
-            return set_err(SD_ERR_UNSUPPORTED, m);
-        }
+        if (!sd_plan_build(a, ex->prm, p->width, p->height) || !sd_plan_build(c, t->exIni->prm, p->width, p->height))
+            return set_err(SD_ERR_UNSUPPORTED, a.error.empty() ? c.error : a.error);
         minCap = a.kpCap > c.kpCap ? a.kpCap : c.kpCap;
     }
-    int rc = batch_create_impl(&t->b, ex, p->width, p->height, t->nCur + t->S * t->R, minCap);
-    if (rc == SD_OK && t->exIni) rc = batch_create_impl(&t->bIni, t->exIni, p->width, p->height, t->S, minCap);
-    for (int k = 0; k < 2 && rc == SD_OK && p->lookahead > 0; k++) rc = batch_create_impl(&t->bp[k], ex, p->width, p->height, p->lookahead * t->nCur, minCap);
-    if (rc != SD_OK) { if (t->b) batch_free(t->b); if (t->bIni) batch_free(t->bIni); for (sd_batch* q : t->bp) if (q) batch_free(q); delete t->exIni; delete t; return rc; }
-    sd_batch* b = t->b;
-    const size_t nI = b->maxImages, cap = b->plan.kpCap;
+    int rc = batch_create_impl(t->b, ex, p->width, p->height, t->nCur + t->S * t->R, minCap);
+    if (rc == SD_OK && t->exIni) rc = batch_create_impl(t->bIni, t->exIni.get(), p->width, p->height, t->S, minCap);
+    for (int k = 0; k < 2 && rc == SD_OK && p->lookahead > 0; k++) rc = batch_create_impl(t->bp[k], ex, p->width, p->height, p->lookahead * t->nCur, minCap);
+    if (rc != SD_OK) return rc;
+    sd_batch* b = t->b.get();
     {
         const float K4[4] = {p->cam.fx, p->cam.fy, p->cam.cx, p->cam.cy};
         rc = sd_batch_set_distortion(b, K4, p->dist);              // Camera.k1 != 0 (TUM1 / TUM2 / EuRoC): mvKeysUn becomes a second array
-        for (sd_batch* q : t->bp) if (rc == SD_OK && q) rc = sd_batch_set_distortion(q, K4, p->dist);
-        if (rc != SD_OK) { tracker_free(t); return rc; }
+        for (auto& q : t->bp) if (rc == SD_OK && q) rc = sd_batch_set_distortion(q.get(), K4, p->dist);
+        if (rc == SD_OK) rc = ensure_motion(b);           // the model-fit buffers now, not inside the first step
+        if (rc != SD_OK) return rc;
     }
-    hipError_t e = hipMalloc((void**)&t->d_want, (size_t)t->S * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->d_active, (size_t)t->S * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->d_activeLast, (size_t)t->S * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&t->d_slotList, (size_t)t->S * 4);
+    HIPCHK(t->d_want.alloc((size_t)t->S * 4));
+    HIPCHK(t->d_active.alloc((size_t)t->S * 4));
+    HIPCHK(t->d_activeLast.alloc((size_t)t->S * 4));
+    HIPCHK(t->d_slotList.alloc((size_t)t->S * 4));
     const size_t sumBytes = (size_t)t->S * (sizeof(SdLaneSummary) + sizeof(SdPoseSummary));   // lane summaries, then the pose tail's
-    if (e == hipSuccess) e = hipMalloc((void**)&t->d_sum, sumBytes);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&t->h_sum, sumBytes, hipHostMallocDefault);
-    for (auto& bl : t->blocks) if (e == hipSuccess && t->bp[0]) e = hipEventCreateWithFlags(&bl.ready, hipEventDisableTiming);
-    if (e == hipSuccess && !b->d_moPts) {                 // the model-fit buffers (lazily allocated by sd_batch_estimate_motion otherwise)
-        e = hipMalloc((void**)&b->d_moPts, nI * cap * 16);
-        if (e == hipSuccess) e = hipMalloc((void**)&b->d_moNorm, nI * sizeof(SdMotionNorm));
-        if (e == hipSuccess) e = hipMalloc((void**)&b->d_moCounts, nI * SD_MOTION_K * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&b->d_moModels, nI * SD_MOTION_K * 72);
-        if (e == hipSuccess) e = hipMalloc((void**)&b->d_moMaskH, nI * cap);
-        if (e == hipSuccess) e = hipMalloc((void**)&b->d_moMaskF, nI * cap);
-        if (e == hipSuccess) e = hipMalloc((void**)&b->d_moRes, nI * sizeof(SdMotionResult));
-    }
-    if (e != hipSuccess) { std::string m = std::string("tracker setup: ") + hipGetErrorString(e); tracker_free(t); return set_err(SD_ERR_HIP, m); }
-    t->poseOfSlot.assign(nI, std::vector<float>());
+    HIPCHK(t->d_sum.alloc(sumBytes));
+    HIPCHK(hipHostMalloc((void**)&t->h_sum, sumBytes, hipHostMallocDefault));
+    for (auto& bl : t->blocks) if (t->bp[0]) HIPCHK(hipEventCreateWithFlags(&bl.ready, hipEventDisableTiming));
+    t->poseOfSlot.assign(b->maxImages, std::vector<float>());
     t->hI.assign((size_t)t->S * 16, 0.f);
     for (int s = 0; s < t->S; s++) for (int k = 0; k < 4; k++) t->hI[(size_t)s * 16 + 5 * k] = 1.f;
-    tracker_reset_lanes(t);
-    *out = t;
+    tracker_reset_lanes(t.get());
+    *out = t.release();
     return SD_OK;
 }
 
-int sd_tracker_destroy(sd_tracker* t) { tracker_free(t); return SD_OK; }
+int sd_tracker_destroy(sd_tracker* t) { delete t; return SD_OK; }
 
 int sd_tracker_reset(sd_tracker* t)
 {
@@ -184,7 +163,7 @@ int sd_tracker_prefetch(sd_tracker* t, const uint8_t* d_images, size_t stride, s
     const int slot = (t->blockHead + t->blockCount) & 1;
     sd_tracker::Block& B = t->blocks[slot];
     B.n = n_frames; B.next = 0;
-    sd_batch* bp = t->bp[slot];
+    sd_batch* bp = t->bp[slot].get();
     hipStream_t s = stream_ ? (hipStream_t)stream_ : bp->stream;
     int rc = tracker_front_half(t, bp, n_frames, d_images, stride, image_pitch, d_depth, depth_stride_elems, depth_pitch_elems, s);
     if (rc != SD_OK) return rc;
@@ -226,7 +205,7 @@ int sd_tracker_export_prefetched(sd_tracker* t, int first_frame, int n_frames, v
     sd_tracker::Block& B = t->blocks[slot];
     if (first_frame + n_frames > B.n) return set_err(SD_ERR_INVALID, "export_prefetched: frames beyond the block");
     if (!record_stride_ok(t, record_stride)) return set_err(SD_ERR_INVALID, "export_prefetched: record stride below the record size or not a multiple of 16");
-    sd_batch* bp = t->bp[slot];
+    sd_batch* bp = t->bp[slot].get();
     hipStream_t s = stream_ ? (hipStream_t)stream_ : bp->stream;
     HIPCHK(hipStreamWaitEvent(s, B.ready, 0));
     SdRecordTable T = record_table(t, bp);
@@ -245,7 +224,7 @@ int sd_tracker_import_prefetched(sd_tracker* t, const void* d_records, size_t re
     if (!record_stride_ok(t, record_stride)) return set_err(SD_ERR_INVALID, "import_prefetched: record stride below the record size or not a multiple of 16");
     const int slot = (t->blockHead + t->blockCount) & 1;
     sd_tracker::Block& B = t->blocks[slot];
-    sd_batch* bp = t->bp[slot];
+    sd_batch* bp = t->bp[slot].get();
     hipStream_t s = stream_ ? (hipStream_t)stream_ : bp->stream;
     SdRecordTable T = record_table(t, bp);
     T.recordBytes = (unsigned)record_stride;
@@ -277,7 +256,7 @@ int sd_tracker_set_state(sd_tracker* t, const int32_t* state)
 int sd_tracker_set_mappoints(sd_tracker* t, const float* xw, const uint8_t* flags, const int32_t* n)
 {
     if (!t || !xw || !flags || !n) return set_err(SD_ERR_INVALID, "bad set_mappoints arguments");
-    sd_batch* b = t->b;
+    sd_batch* b = t->b.get();
     const size_t cap = b->plan.kpCap;
     hipStream_t s = b->lastStream;
     for (int l = 0; l < t->S; l++) {
@@ -298,7 +277,7 @@ int sd_tracker_set_mappoints(sd_tracker* t, const float* xw, const uint8_t* flag
 int sd_tracker_batch(sd_tracker* t, sd_batch** b)
 {
     if (!t || !b) return SD_ERR_INVALID;
-    *b = t->b;
+    *b = t->b.get();
     return SD_OK;
 }
 
@@ -307,7 +286,7 @@ static SdCopyTable copy_table(sd_batch* b)
     SdCopyTable T;
     int n = 0;
     const size_t cap = b->plan.kpCap;
-#define SEG(ptr, bytes) do { T.base[n] = (char*)(ptr); T.slotBytes[n] = (unsigned)(bytes); n++; } while (0)
+#define SEG(ptr, bytes) do { T.base[n] = (char*)(ptr).get(); T.slotBytes[n] = (unsigned)(bytes); n++; } while (0)
     SEG(b->d_kp, cap * sizeof(sd_keypoint)); SEG(b->d_desc, cap * 32); SEG(b->d_uright, cap * 4); SEG(b->d_depth, cap * 4); SEG(b->d_sad, cap * 4);
     SEG(b->d_cellOf, cap * 2); SEG(b->d_xw, cap * 12); SEG(b->d_flags, cap); SEG(b->d_sortedIdx, cap * 2);
     SEG(b->d_kpD, cap * sizeof(sd_keypoint)); SEG(b->d_descD, cap * 32); SEG(b->d_urD, cap * 4); SEG(b->d_depD, cap * 4);
@@ -355,7 +334,7 @@ static int tracker_peek_candidate(const sd_tracker::Lane& L, double t, int from)
 // One round of TrackHomo + Separate + UpdateFrame for the lanes whose hWant entry is set (pair index = lane).
 static int tracker_dynamic_round(sd_tracker* t, const float* Tcw, hipStream_t s)
 {
-    sd_batch* b = t->b;
+    sd_batch* b = t->b.get();
     const int S = t->S;
     const sd_camera* cam = &t->p.cam;
     const float th = t->p.sensor == SD_SENSOR_STEREO ? 7.0f : 15.0f;           // Tracking.cc:990-994
@@ -380,7 +359,7 @@ static int tracker_dynamic_round(sd_tracker* t, const float* Tcw, hipStream_t s)
 // (the redoBelow path TrackHomo uses), then PoseOptimization of the lanes with >= 20 matches (Tracking.cc:1741-1759)
 static int tracker_last_matcher(sd_tracker* t, const int32_t* cur, const int32_t* last, const float* Tcw, hipStream_t s)
 {
-    sd_batch* b = t->b;
+    sd_batch* b = t->b.get();
     const int S = t->S, bMono = t->p.sensor == SD_SENSOR_MONOCULAR;
     const float th = t->p.sensor == SD_SENSOR_STEREO ? 7.0f : 15.0f;           // Tracking.cc:1727-1731
     TRK(search_by_projection_impl(b, S, S, cur, last, Tcw, t->hTlw.data(), &t->p.cam, th, bMono, 1, nullptr, nullptr, s, t->d_activeLast, 0, 1));
@@ -395,7 +374,7 @@ static int tracker_last_matcher(sd_tracker* t, const int32_t* cur, const int32_t
 
 static int tracker_summary(sd_tracker* t, int haveLast, hipStream_t s)
 {
-    sd_batch* b = t->b;
+    sd_batch* b = t->b.get();
     b->lastStream = s;
     hipLaunchKernelGGL(k_lane_summary, dim3(t->S), dim3(64), 0, s, b->d_fb, b->d_count, b->d_moRes, b->d_sepRet, b->d_nmatch, b->d_npairs, t->S, t->ipl,
                        haveLast, t->d_sum);
@@ -421,7 +400,7 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
     if (!fromPool && t->blockCount > 0) return set_err(SD_ERR_STATE, "prefetched frames are outstanding: consume them (d_images == NULL) first");
     if (!fromPool && t->p.sensor == SD_SENSOR_RGBD && !d_depth) return set_err(SD_ERR_INVALID, "RGB-D tracking needs a depth image");
     if ((Tcw_in == nullptr) != (Twc_in == nullptr)) return set_err(SD_ERR_INVALID, "give both Tcw and Twc or neither");
-    sd_batch* b = t->b;
+    sd_batch* b = t->b.get();
     const int S = t->S, ipl = t->ipl;
     hipStream_t s = stream_ ? (hipStream_t)stream_ : b->stream;
     const sd_camera* cam = &t->p.cam;
@@ -459,12 +438,12 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
         // frame `next` of the oldest outstanding block: its left slots (key points, descriptors, mvKeysUn, mvuRight / mvDepth, level counts)
         // move to the lanes' current slots in one launch; nothing downstream reads the right eye's slot or the pyramid again
         sd_tracker::Block& B = t->blocks[t->blockHead];
-        sd_batch* bp = t->bp[t->blockHead];
+        sd_batch* bp = t->bp[t->blockHead].get();
         HIPCHK(hipStreamWaitEvent(s, B.ready, 0));
         SdCopyTableX T;
         int n = 0;
         const size_t cap = b->plan.kpCap;
-#define SEGX(field, bytes) do { T.src[n] = (const char*)(bp->field); T.dst[n] = (char*)(b->field); T.slotBytes[n] = (unsigned)(bytes); n++; } while (0)
+#define SEGX(field, bytes) do { T.src[n] = (const char*)bp->field.get(); T.dst[n] = (char*)b->field.get(); T.slotBytes[n] = (unsigned)(bytes); n++; } while (0)
         SEGX(d_kp, cap * sizeof(sd_keypoint)); SEGX(d_desc, cap * 32); SEGX(d_uright, cap * 4); SEGX(d_depth, cap * 4); SEGX(d_sad, cap * 4);
         SEGX(d_count, 4); SEGX(d_lvlCount, (size_t)b->plan.nlevels * 4);
         if (b->hasDist) SEGX(d_kpUn, cap * sizeof(sd_keypoint));
@@ -480,7 +459,7 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
         for (int l = 0; l < S; l++) nIni += t->useIniExtractor(l) ? 1 : 0;
         if (nIni < S) TRK(sd_batch_extract_pixels_device(b, d_images, stride, image_pitch, t->p.channels, t->p.rgb_order, t->nCur, s));
         if (nIni > 0) {                                            // monocular lanes that are not initialised: mpIniORBextractor (Tracking.cc:335-338)
-            sd_batch* bi = t->bIni;
+            sd_batch* bi = t->bIni.get();
             TRK(sd_batch_extract_pixels_device(bi, d_images, stride, image_pitch, t->p.channels, t->p.rgb_order, S, s));
             const size_t cap = b->plan.kpCap, nl = (size_t)b->plan.nlevels;
             for (int l0 = 0; l0 < S;) {                            // runs of consecutive lanes: one copy per array
@@ -716,7 +695,7 @@ int sd_tracker_set_pose_optimization(sd_tracker* t, int enable)
     if (!t) return set_err(SD_ERR_INVALID, "null tracker");
     if (enable && !t->p.track_last) return set_err(SD_ERR_STATE, "pose optimisation needs track_last");
     if (enable) {                                              // the pose buffers now, not inside the first step
-        int rc = pose_alloc(t->b);
+        int rc = ensure_pose(t->b.get());
         if (rc != SD_OK) return rc;
     }
     t->poseOpt = enable != 0;
@@ -741,7 +720,7 @@ int sd_tracker_track_host(sd_tracker* t, const uint8_t* const* images, size_t st
     const size_t row = (size_t)W * ch, img = row * H;
     if (stride < row) return set_err(SD_ERR_INVALID, "stride smaller than a row");
     hipStream_t s = t->b->stream;
-    if (!t->d_hostImg) HIPCHK(hipMalloc((void**)&t->d_hostImg, img * t->nCur));
+    if (!t->d_hostImg) HIPCHK(t->d_hostImg.alloc(img * t->nCur));
     for (int i = 0; i < t->nCur; i++) {
         if (!images[i]) return set_err(SD_ERR_INVALID, "null image");
         HIPCHK(hipMemcpy2DAsync(t->d_hostImg + img * i, row, images[i], stride, row, H, hipMemcpyHostToDevice, s));
@@ -749,10 +728,10 @@ int sd_tracker_track_host(sd_tracker* t, const uint8_t* const* images, size_t st
     if (t->p.sensor == SD_SENSOR_RGBD) {
         if (!depth || depth_stride_elems < (size_t)W) return set_err(SD_ERR_INVALID, "RGB-D tracking needs depth images");
         const size_t eb = t->p.depth_type == SD_DEPTH_F32 ? 4 : 2;
-        if (!t->d_hostDepth) HIPCHK(hipMalloc((void**)&t->d_hostDepth, (size_t)W * H * eb * t->S));
+        if (!t->d_hostDepth) HIPCHK(t->d_hostDepth.alloc((size_t)W * H * eb * t->S));
         for (int l = 0; l < t->S; l++) {
             if (!depth[l]) return set_err(SD_ERR_INVALID, "null depth image");
-            HIPCHK(hipMemcpy2DAsync((char*)t->d_hostDepth + (size_t)W * H * eb * l, (size_t)W * eb, depth[l], depth_stride_elems * eb, (size_t)W * eb, H, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpy2DAsync((char*)t->d_hostDepth.get() + (size_t)W * H * eb * l, (size_t)W * eb, depth[l], depth_stride_elems * eb, (size_t)W * eb, H, hipMemcpyHostToDevice, s));
         }
     }
     return sd_tracker_track(t, t->d_hostImg, row, img, t->d_hostDepth, (size_t)W, (size_t)W * H, boxes, n_boxes, timestamps, Tcw, Twc, results, s);

@@ -7,11 +7,12 @@
 #include <string>
 #include <vector>
 #include "k_bow.h"
+#include "sd_common.h"
 
 struct sd_vocab {
     SdVocabHeader h = {};
     void* d_blob = nullptr;        // packed buffer in HBM
-    bool owned = false;            // false: adopted from the caller (a broadcast target)
+    SdDevBuf<uint8_t> owned;       // the library's copy behind d_blob; empty: adopted from the caller (a broadcast target)
     SdVocabDev dev = {};
 };
 

@@ -11,34 +11,35 @@
 #include "k_yolo32.h"
 #include "k_yolo32w.h"
 #include "k_yolo32b.h"
+#include "sd_common.h"
 
 struct sd_yolo {
     std::vector<sd_yolo_layer> L;
     struct Rt { int H = 0, W = 0, C = 0; int cinPad = 0, coutPad = 0; size_t wOff = 0, bOff = 0; _Float16* out = nullptr; int outC = 0; bool alias = false;
+                SdDevBuf<_Float16> own;                      // output storage allocated for this layer; `out` may point into another layer's (alias)
                 bool wino = false; size_t wOffW = 0;
                 bool b3 = false, b3flat = false; int b3wm = 2; size_t wOffB = 0; };          // SD_YOLO_F32X3: this layer runs on bf16 limbs (k_yolo32b.h), its split weights at d_wgtB + wOffB (16-byte units)        // SD_YOLO_F32W: this layer runs as Winograd F(2x2, 3x3), its transformed weights at d_wgtW + wOffW
     std::vector<Rt> R;
     int netW = 0, netH = 0, classes = 80, maxBatch = 0, nconv = 0;
     int f32 = 0;                   // SD_YOLO_F32: activations / weights / arithmetic in f32 (k_yolo32.h); the `out` pointers then hold floats
-    float* d_blob8 = nullptr; float* d_wgt32 = nullptr; bool attrF32 = false, attrNms = false;
+    SdDevBuf<float> d_blob8; SdDevBuf<float> d_wgt32;
     int wino = 0;                  // SD_YOLO_F32W (k_yolo32w.h): f32 mode with the eligible 3 x 3 stride-1 layers as Winograd F(2x2, 3x3)
-    float* d_wgtW = nullptr; float* d_V = nullptr; size_t wTotalW = 0; bool attrWino = false;
+    SdDevBuf<float> d_wgtW; SdDevBuf<float> d_V; size_t wTotalW = 0;
     int b3 = 0;                    // SD_YOLO_F32X3 (k_yolo32b.h): f32 mode with the >= 128-filter layers on three bf16 limbs per operand
-    uint4* d_wgtB = nullptr; size_t wTotalB = 0; bool attrB3 = false;
+    SdDevBuf<uint4> d_wgtB; size_t wTotalB = 0;
     double mfmaFlopsBf16 = 0;      // per image: bf16 MFMA FLOPs executed by the limb kernels (six limb products per product)
     double mfmaFlops = 0;          // per image, as executed (Winograd layers: 16 multiplies per 2 x 2 block instead of 36)
     float anchors[18];
-    _Float16* d_blob4 = nullptr;   // network input, NHWC f16 x 4 channels
-    _Float16* d_wgt = nullptr; float* d_bias = nullptr; _Float16* d_zero = nullptr;
-    short4* d_ct = nullptr; short4* d_rt = nullptr;
-    SdDet* d_dets = nullptr; int* d_ndet = nullptr; float* d_raw = nullptr;
-    uint8_t* d_hostImg = nullptr; size_t hostImgCap = 0; uint8_t* d_hostMask = nullptr; size_t hostMaskCap = 0;      // sd_yolo_forward_host / mask_host
-    double* d_nmsBoxes = nullptr; int* d_nmsCls = nullptr; float* d_nmsConf = nullptr; int* d_nmsN = nullptr;      // sd_yolo_boxes_batch
+    SdDevBuf<_Float16> d_blob4;   // network input, NHWC f16 x 4 channels
+    SdDevBuf<_Float16> d_wgt; SdDevBuf<float> d_bias; SdDevBuf<_Float16> d_zero;
+    SdDevBuf<short4> d_ct; SdDevBuf<short4> d_rt;
+    SdDevBuf<SdDet> d_dets; SdDevBuf<int> d_ndet; SdDevBuf<float> d_raw;
+    SdDevBuf<uint8_t> d_hostImg; size_t hostImgCap = 0; SdDevBuf<uint8_t> d_hostMask; size_t hostMaskCap = 0;      // sd_yolo_forward_host / mask_host
+    SdDevBuf<double> d_nmsBoxes; SdDevBuf<int> d_nmsCls; SdDevBuf<float> d_nmsConf; SdDevBuf<int> d_nmsN;      // sd_yolo_boxes_batch
     int detCap = 0, totalRows = 0;
     int tabW = 0, tabH = 0;
     size_t wTotal = 0, bTotal = 0;
     bool weightsLoaded = false;
-    bool attrGlds = false, attrFlat3 = false;      // dynamic-LDS limits of the convolution kernels raised on this device
     int lastN = 0;
     hipStream_t stream = nullptr;
     // overlap mode (sd_yolo_set_overlap, f32-class modes): blobFromImage of a pass on sPre, the region decodes on sPost, ordered against the convolution
@@ -46,9 +47,12 @@ struct sd_yolo {
     bool overlap = false, haveL0 = false, haveDecoded = false, haveNms = false;
     hipStream_t sPre = nullptr, sPost = nullptr;
     hipEvent_t evBlob = nullptr, evL0 = nullptr, evHead[3] = {nullptr, nullptr, nullptr}, evDecoded = nullptr, evNms = nullptr;
-    // 2-input [route]s whose second input is written in place by its producer (f32-class modes): only the up-sampled half is copied
-    std::vector<void*> owned;
     double convFlops = 0;     // per image
+    ~sd_yolo()
+    {
+        for (hipStream_t q : {stream, sPre, sPost}) if (q) (void)hipStreamDestroy(q);
+        for (hipEvent_t e : {evBlob, evL0, evHead[0], evHead[1], evHead[2], evDecoded, evNms}) if (e) (void)hipEventDestroy(e);
+    }
 };
 
 static const float kYoloV3Anchors[18] = {10, 13, 16, 30, 33, 23, 30, 61, 62, 45, 59, 119, 116, 90, 156, 198, 373, 326};

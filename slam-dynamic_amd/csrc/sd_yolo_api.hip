@@ -7,6 +7,7 @@
 #include <cstddef>
 #include <cmath>
 #include <string>
+#include <memory>
 #include <vector>
 #include "sd_common.h"
 #include "sd_yolo.h"
@@ -28,18 +29,40 @@ int sd_yolo_v3_layers(sd_yolo_layer* layers, int cap, int* n, float anchors[18])
     return SD_OK;
 }
 
-static void yolo_free(sd_yolo* y)
+// dynamic LDS of k_conv_glds<8, *> / k_conv_glds<4, *>
+static const int kGldsLds8 = 3 * (512 * 64 + SD_G3_WBYTES), kGldsLds4 = 3 * (256 * 64 + SD_G3_WBYTES);
+
+// The dynamic-LDS limits of the kernels the detector's mode launches, raised once at creation
+static int yolo_raise_lds_limits(const sd_yolo* y)
 {
-    if (!y) return;
-    for (void* p : y->owned) if (p) (void)hipFree(p);
-    if (y->d_hostImg) (void)hipFree(y->d_hostImg);
-    if (y->d_hostMask) (void)hipFree(y->d_hostMask);
-    if (y->stream) (void)hipStreamDestroy(y->stream);
-    if (y->sPre) (void)hipStreamDestroy(y->sPre);
-    if (y->sPost) (void)hipStreamDestroy(y->sPost);
-    hipEvent_t evs[] = {y->evBlob, y->evL0, y->evHead[0], y->evHead[1], y->evHead[2], y->evDecoded, y->evNms};
-    for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
-    delete y;
+    if (y->f32) {
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<32, 2, 2, 8>, SD_F32_LDS(32, 2, 2, 8)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<32, 2, 2, 4>, SD_F32_LDS(32, 2, 2, 4)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 1, 2, 8>, SD_F32_LDS(16, 1, 2, 8)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 1, 1, 8>, SD_F32_LDS(16, 1, 1, 8)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<8, 1, 1, 8>, SD_F32_LDS(8, 1, 1, 8)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 1, 2, 4>, SD_F32_LDS(16, 1, 2, 4)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 1, 1, 4>, SD_F32_LDS(16, 1, 1, 4)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 2, 2, 4>, SD_F32_LDS(16, 2, 2, 4)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_wino_gemm_f32<16, 2>, SD_WINO_LDS(16, 2)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_b3<1>, SD_B3_LDS(1)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_b3<2>, SD_B3_LDS(2)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3<3, 2, 2>, SD_B3F_LDS(160, 128)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3<4, 2, 2>, SD_B3F_LDS(160, 128)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3<5, 2, 2>, SD_B3F_LDS(160, 128)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3<8, 2, 2>, SD_B3F_LDS(160, 128)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3c<5>, SD_B3C_LDS(80)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3c<6>, SD_B3C_LDS(80)));
+    } else {
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_glds<8, 1>, kGldsLds8));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_glds<4, 1>, kGldsLds4));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_glds<8, 3>, kGldsLds8));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv_glds<4, 3>, kGldsLds4));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_glds<80>, SD_G3_LDS(80)));
+        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_glds<160>, SD_G3_LDS(160)));
+    }
+    HIPCHK(sd_raise_lds_limit((const void*)k_yolo_nms, SD_NMS_LDS));
+    return SD_OK;
 }
 
 int sd_yolo_create(sd_yolo** out, const sd_yolo_layer* layers, int n_layers, const float anchors[18], int classes, int net_w,
@@ -59,7 +82,7 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
         return set_err(SD_ERR_INVALID, "bad detector arguments (classes must be 80, net size a multiple of 32)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_err(SD_ERR_NO_DEVICE, "no HIP device: the detector has no CPU fallback");
-    sd_yolo* y = new sd_yolo();
+    std::unique_ptr<sd_yolo> y(new sd_yolo());
     y->L.assign(layers, layers + n_layers);
     y->R.resize(n_layers);
     y->netW = net_w; y->netH = net_h; y->classes = classes; y->maxBatch = max_batch;
@@ -76,11 +99,11 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
         const sd_yolo_layer& l = y->L[i];
         sd_yolo::Rt& r = y->R[i];
         if (l.type == SD_YOLO_CONV) {
-            if ((l.size != 1 && l.size != 3) || (l.stride != 1 && l.stride != 2) || l.filters < 1) { delete y; return set_err(SD_ERR_UNSUPPORTED, "convolution size/stride not supported"); }
-            if (i == 0 && (l.size != 3 || l.stride != 1 || l.filters > 32)) { delete y; return set_err(SD_ERR_UNSUPPORTED, "first convolution must be 3x3, stride 1, <= 32 filters"); }
+            if ((l.size != 1 && l.size != 3) || (l.stride != 1 && l.stride != 2) || l.filters < 1) return set_err(SD_ERR_UNSUPPORTED, "convolution size/stride not supported");
+            if (i == 0 && (l.size != 3 || l.stride != 1 || l.filters > 32)) return set_err(SD_ERR_UNSUPPORTED, "first convolution must be 3x3, stride 1, <= 32 filters");
             const int cinReal = i == 0 ? 3 : C;
             r.cinPad = i == 0 ? 32 : C;
-            if (r.cinPad % 32) { delete y; return set_err(SD_ERR_UNSUPPORTED, "input channels must be a multiple of 32"); }
+            if (r.cinPad % 32) return set_err(SD_ERR_UNSUPPORTED, "input channels must be a multiple of 32");
             const int pad = l.size / 2;
             r.H = (H + 2 * pad - l.size) / l.stride + 1; r.W = (W + 2 * pad - l.size) / l.stride + 1; r.C = l.filters;
             r.outC = (l.filters + 31) / 32 * 32;            // stored channel count (255 -> 256)
@@ -107,61 +130,58 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
             y->nconv++;
         } else if (l.type == SD_YOLO_SHORTCUT) {
             const int f = yolo_resolve(i, l.from[0]);
-            if (f < 0 || f >= i || y->R[f].H != H || y->R[f].W != W || y->R[f].C != C) { delete y; return set_err(SD_ERR_INVALID, "bad shortcut"); }
+            if (f < 0 || f >= i || y->R[f].H != H || y->R[f].W != W || y->R[f].C != C) return set_err(SD_ERR_INVALID, "bad shortcut");
             r.H = H; r.W = W; r.C = C; r.outC = C;
         } else if (l.type == SD_YOLO_ROUTE) {
             const int f0 = yolo_resolve(i, l.from[0]);
-            if (f0 < 0 || f0 >= i) { delete y; return set_err(SD_ERR_INVALID, "bad route"); }
+            if (f0 < 0 || f0 >= i) return set_err(SD_ERR_INVALID, "bad route");
             r.H = y->R[f0].H; r.W = y->R[f0].W; r.C = y->R[f0].C;
             if (l.nfrom == 2) {
                 const int f1 = yolo_resolve(i, l.from[1]);
-                if (f1 < 0 || f1 >= i || y->R[f1].H != r.H || y->R[f1].W != r.W) { delete y; return set_err(SD_ERR_INVALID, "bad route"); }
+                if (f1 < 0 || f1 >= i || y->R[f1].H != r.H || y->R[f1].W != r.W) return set_err(SD_ERR_INVALID, "bad route");
                 r.C += y->R[f1].C;
             }
             r.outC = r.C;
         } else if (l.type == SD_YOLO_UPSAMPLE) {
             r.H = 2 * H; r.W = 2 * W; r.C = C; r.outC = C;
         } else if (l.type == SD_YOLO_YOLO) {
-            if (C != 3 * (5 + classes)) { delete y; return set_err(SD_ERR_INVALID, "[yolo] input must have 3*(5+classes) channels"); }
+            if (C != 3 * (5 + classes)) return set_err(SD_ERR_INVALID, "[yolo] input must have 3*(5+classes) channels");
             r.H = H; r.W = W; r.C = C; r.outC = C;
             y->totalRows += H * W * 3;
-        } else { delete y; return set_err(SD_ERR_INVALID, "unknown layer type"); }
+        } else return set_err(SD_ERR_INVALID, "unknown layer type");
         H = r.H; W = r.W; C = r.C;
-        if ((l.type == SD_YOLO_CONV) && (r.C % 4) && r.C != 3 * (5 + classes)) { delete y; return set_err(SD_ERR_UNSUPPORTED, "filters must be a multiple of 4"); }
+        if ((l.type == SD_YOLO_CONV) && (r.C % 4) && r.C != 3 * (5 + classes)) return set_err(SD_ERR_UNSUPPORTED, "filters must be a multiple of 4");
     }
     y->wTotal = wOff; y->bTotal = bOff; y->wTotalW = wOffW; y->wTotalB = wOffB;
     y->detCap = 8192;
     // ---- device memory
-    auto alloc = [&](void** p, size_t bytes) -> bool {
-        if (hipMalloc(p, bytes) != hipSuccess) return false;
-        y->owned.push_back(*p);
-        return true;
-    };
     bool ok = true;
+    auto alloc = [&](auto& buf, size_t bytes) { ok = ok && buf.alloc(bytes) == hipSuccess; };
     const size_t nB = (size_t)max_batch;
-    if (y->f32) ok = ok && alloc((void**)&y->d_blob8, nB * net_h * net_w * 8 * 4);
-    else ok = ok && alloc((void**)&y->d_blob4, nB * net_h * net_w * 4 * 2);
-    ok = ok && alloc((void**)&y->d_zero, 256);
+    if (y->f32) alloc(y->d_blob8, nB * net_h * net_w * 8 * 4);
+    else alloc(y->d_blob4, nB * net_h * net_w * 4 * 2);
+    alloc(y->d_zero, 256);
     if (ok) ok = hipMemset(y->d_zero, 0, 256) == hipSuccess;
 
     if (!y->f32) {
-        ok = ok && alloc((void**)&y->d_wgt, wOff * 2 + 64);                             // f16 weights: the f16 mode only
+        alloc(y->d_wgt, wOff * 2 + 64);                             // f16 weights: the f16 mode only
     } else {
-        ok = ok && alloc((void**)&y->d_wgt32, wOff * 4 + 64);
-        if (y->wino && wOffW) { ok = ok && alloc((void**)&y->d_wgtW, wOffW * 4 + 64); ok = ok && alloc((void**)&y->d_V, nB * vMax * 4 + 64); }
-        if (y->b3 && wOffB) ok = ok && alloc((void**)&y->d_wgtB, wOffB * 16 + 65536);  // slack: the kernels request weight fragments up to two steps past a tile's last
+        alloc(y->d_wgt32, wOff * 4 + 64);
+        if (y->wino && wOffW) { alloc(y->d_wgtW, wOffW * 4 + 64); alloc(y->d_V, nB * vMax * 4 + 64); }
+        if (y->b3 && wOffB) alloc(y->d_wgtB, wOffB * 16 + 65536);  // slack: the kernels request weight fragments up to two steps past a tile's last
     }
-    ok = ok && alloc((void**)&y->d_bias, bOff * 4 + 64);
-    ok = ok && alloc((void**)&y->d_dets, nB * y->detCap * sizeof(SdDet));
-    ok = ok && alloc((void**)&y->d_ndet, nB * 4);
-    ok = ok && alloc((void**)&y->d_raw, (size_t)y->totalRows * (5 + classes) * 4 + 64);
-    ok = ok && alloc((void**)&y->d_ct, 8 * 8192);
-    ok = ok && alloc((void**)&y->d_rt, 8 * 8192);
+    alloc(y->d_bias, bOff * 4 + 64);
+    alloc(y->d_dets, nB * y->detCap * sizeof(SdDet));
+    alloc(y->d_ndet, nB * 4);
+    alloc(y->d_raw, (size_t)y->totalRows * (5 + classes) * 4 + 64);
+    alloc(y->d_ct, 8 * 8192);
+    alloc(y->d_rt, 8 * 8192);
     for (int i = 0; ok && i < n_layers; i++) {
         const sd_yolo_layer& l = y->L[i];
         sd_yolo::Rt& r = y->R[i];
         if (l.type == SD_YOLO_CONV) {
-            ok = alloc((void**)&r.out, nB * r.H * r.W * r.outC * eb + 64);
+            alloc(r.own, nB * r.H * r.W * r.outC * eb + 64);
+            r.out = r.own;
             if (ok && r.outC != r.C) ok = hipMemset(r.out, 0, nB * r.H * r.W * r.outC * eb) == hipSuccess;
         } else if (l.type == SD_YOLO_SHORTCUT) {
             // fused into the preceding convolution's epilogue when that output has no other consumer
@@ -173,15 +193,16 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
                     for (int k = 0; k < o.nfrom; k++) if (yolo_resolve(j, o.from[k]) == i - 1) fuse = false;
             }
             if (fuse) { r.out = y->R[i - 1].out; r.alias = true; }
-            else ok = alloc((void**)&r.out, nB * r.H * r.W * r.outC * eb + 64);
+            else { alloc(r.own, nB * r.H * r.W * r.outC * eb + 64); r.out = r.own; }
         } else if (l.type == SD_YOLO_ROUTE && l.nfrom == 1) {
             r.out = y->R[yolo_resolve(i, l.from[0])].out; r.alias = true; r.outC = y->R[yolo_resolve(i, l.from[0])].outC;
         } else if (l.type == SD_YOLO_ROUTE) {
-            ok = alloc((void**)&r.out, nB * r.H * r.W * r.outC * eb + 64);
+            alloc(r.own, nB * r.H * r.W * r.outC * eb + 64);
+            r.out = r.own;
         } else if (l.type == SD_YOLO_UPSAMPLE) {
             // materialised only inside the following 2-input route (k_upsample_concat); stand-alone upsample unsupported
             if (!(i + 1 < n_layers && y->L[i + 1].type == SD_YOLO_ROUTE && y->L[i + 1].nfrom == 2 && yolo_resolve(i + 1, y->L[i + 1].from[0]) == i)) {
-                yolo_free(y); return set_err(SD_ERR_UNSUPPORTED, "[upsample] must feed a 2-input [route] as its first input");
+                return set_err(SD_ERR_UNSUPPORTED, "[upsample] must feed a 2-input [route] as its first input");
             }
         } else if (l.type == SD_YOLO_YOLO) {
             r.out = y->R[i - 1].out; r.alias = true; r.outC = y->R[i - 1].outC;
@@ -210,9 +231,10 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
         y->R[i].alias = true;                              // marks the route: its second input is already in place
     }
     if (ok) ok = hipStreamCreateWithFlags(&y->stream, hipStreamNonBlocking) == hipSuccess;
-    if (!ok) { yolo_free(y); return set_err(SD_ERR_HIP, "detector allocation failed"); }
-    *out = y;
-    return SD_OK;
+    if (!ok) return set_err(SD_ERR_HIP, "detector allocation failed");
+    const int rc = yolo_raise_lds_limits(y.get());
+    if (rc == SD_OK) *out = y.release();
+    return rc;
 }
 
 // Overlap mode (f32-class modes): blobFromImage runs on an internal stream ahead of the pass's first convolution, the three region decodes on
@@ -238,7 +260,7 @@ int sd_yolo_set_overlap(sd_yolo* y, int on)
     return SD_OK;
 }
 
-int sd_yolo_destroy(sd_yolo* y) { if (y) { (void)hipDeviceSynchronize(); yolo_free(y); } return SD_OK; }
+int sd_yolo_destroy(sd_yolo* y) { if (y) { (void)hipDeviceSynchronize(); delete y; } return SD_OK; }
 
 int sd_yolo_weight_count(const sd_yolo* y, size_t* n_floats)
 {
@@ -450,26 +472,6 @@ static int yolo_forward_f32(sd_yolo* y, const uint8_t* d_bgr, int width, int hei
     }
     int head = 0;
     bool headGuard = ov && y->haveDecoded;              // before the first head tensor is overwritten: the previous pass's decodes have read them
-    if (!y->attrF32) {
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_f32<32, 2, 2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_F32_LDS(32, 2, 2, 8)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_f32<32, 2, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_F32_LDS(32, 2, 2, 4)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_f32<16, 1, 2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_F32_LDS(16, 1, 2, 8)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_f32<16, 1, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_F32_LDS(16, 1, 1, 8)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_f32<8, 1, 1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_F32_LDS(8, 1, 1, 8)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_f32<16, 1, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_F32_LDS(16, 1, 2, 4)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_f32<16, 1, 1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_F32_LDS(16, 1, 1, 4)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_f32<16, 2, 2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_F32_LDS(16, 2, 2, 4)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_wino_gemm_f32<16, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_WINO_LDS(16, 2)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_b3<1>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_B3_LDS(1)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv_b3<2>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_B3_LDS(2)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_b3<3, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_B3F_LDS(160, 128)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_b3<4, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_B3F_LDS(160, 128)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_b3<5, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_B3F_LDS(160, 128)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_b3<8, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_B3F_LDS(160, 128)));
-HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_b3c<5>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_B3C_LDS(80)));
-        HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_b3c<6>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_B3C_LDS(80)));
-        y->attrF32 = true;
-    }
     // tile variant of the >= 128-filter layers: 3 (default) = 128 x 128 tiles on 4-wave workgroups with 16-channel K steps, 40 KB of LDS and 144
     // VGPRs: THREE independent workgroups per CU (3 waves per SIMD keep the MFMA pipe fed through each other's barriers and staging;
     // +3.3 % over variant 1 on every such layer at batch 128; four per CU -- 8-channel steps, 128 VGPRs without fragment prefetch, or 64 x 128 tiles --
@@ -486,7 +488,7 @@ HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_b3c<5>, hipFuncAttributeMaxDyn
         if (l.type == SD_YOLO_CONV && r.wino) {
             // Winograd F(2x2, 3x3), k_yolo32w.h: input transform into the scratch V, then one GEMM over K = 16 cin with the output transform folded in
             SdWinoArgs A;
-            A.V = y->d_V; A.U = y->d_wgtW + r.wOffW; A.bias = y->d_bias + r.bOff; A.res = nullptr; A.out = (float*)r.out; A.zero = (const float*)y->d_zero;
+            A.V = y->d_V; A.U = y->d_wgtW + r.wOffW; A.bias = y->d_bias + r.bOff; A.res = nullptr; A.out = (float*)r.out; A.zero = (const float*)y->d_zero.get();
             A.N = n; A.H = r.H; A.W = r.W; A.th = (r.H + 1) / 2; A.tw = (r.W + 1) / 2;
             A.cin = r.cinPad; A.cout = l.filters; A.outStride = r.outC; A.resStride = 0; A.leaky = l.leaky;
             if (i + 1 < y->L.size() && y->L[i + 1].type == SD_YOLO_SHORTCUT && y->R[i + 1].alias) {
@@ -507,7 +509,7 @@ HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_b3c<5>, hipFuncAttributeMaxDyn
         } else if (l.type == SD_YOLO_CONV) {
             if (headGuard && i + 1 < y->L.size() && y->L[i + 1].type == SD_YOLO_YOLO) { HIPCHK(hipStreamWaitEvent(s, y->evDecoded, 0)); headGuard = false; }
             SdConvArgsF A;
-            A.in = cur; A.wgt = y->d_wgt32 + r.wOff; A.bias = y->d_bias + r.bOff; A.res = nullptr; A.out = (float*)r.out; A.zero = (const float*)y->d_zero;
+            A.in = cur; A.wgt = y->d_wgt32 + r.wOff; A.bias = y->d_bias + r.bOff; A.res = nullptr; A.out = (float*)r.out; A.zero = (const float*)y->d_zero.get();
             A.N = n; A.H = H; A.W = W; A.cin = i == 0 ? 8 : r.cinPad; A.cinStride = Cs; A.pair = i == 0 ? 1 : 0;
             A.Ho = r.H; A.Wo = r.W; A.cout = l.filters; A.outStride = r.outC; A.resStride = 0;
             A.ksize = l.size; A.stride = l.stride; A.pad = l.size / 2; A.leaky = l.leaky;
@@ -650,29 +652,14 @@ int sd_yolo_forward_device(sd_yolo* y, const uint8_t* d_bgr, int width, int heig
             dim3 grd((npix + SD_CV_BN - 1) / SD_CV_BN, (l.filters + SD_CV_BM - 1) / SD_CV_BM);
             const bool flat3 = l.size == 3 && l.stride == 1 && W <= 160 && l.filters % SD_G3_BM == 0 && r.cinPad % 32 == 0 && npix >= SD_G3_BN;
             if (!flat3 && r.cinPad % 32 == 0 && npix >= 512 && (l.size == 1 || l.filters >= SD_G3_BM / 2)) {
-                bool& attr = y->attrGlds;          // per detector (= per device): function attributes are per device
-                const int lds8 = 3 * (512 * 64 + SD_G3_WBYTES), lds4 = 3 * (256 * 64 + SD_G3_WBYTES);
-                if (!attr) {
-                    HIPCHK(hipFuncSetAttribute((const void*)k_conv_glds<8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds8));
-                    HIPCHK(hipFuncSetAttribute((const void*)k_conv_glds<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4));
-                    HIPCHK(hipFuncSetAttribute((const void*)k_conv_glds<8, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds8));
-                    HIPCHK(hipFuncSetAttribute((const void*)k_conv_glds<4, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, lds4));
-                    attr = true;
-                }
                 const int ct = r.coutPad / SD_G3_BM;
                 const bool big = ((npix + 511) / 512) * ct >= 256;
                 const dim3 g8((npix + 511) / 512, ct), g4((npix + 255) / 256, ct);
-                if (l.size == 1 && big) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<8, 1>), g8, dim3(512), lds8, s, A);
-                else if (l.size == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<4, 1>), g4, dim3(256), lds4, s, A);
-                else if (big) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<8, 3>), g8, dim3(512), lds8, s, A);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<4, 3>), g4, dim3(256), lds4, s, A);
+                if (l.size == 1 && big) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<8, 1>), g8, dim3(512), kGldsLds8, s, A);
+                else if (l.size == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<4, 1>), g4, dim3(256), kGldsLds4, s, A);
+                else if (big) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<8, 3>), g8, dim3(512), kGldsLds8, s, A);
+                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<4, 3>), g4, dim3(256), kGldsLds4, s, A);
             } else if (flat3) {
-                bool& attr = y->attrFlat3;
-                if (!attr) {
-                    HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_glds<80>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_G3_LDS(80)));
-                    HIPCHK(hipFuncSetAttribute((const void*)k_conv3x3_glds<160>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_G3_LDS(160)));
-                    attr = true;
-                }
                 const dim3 g3((npix + SD_G3_BN - 1) / SD_G3_BN, l.filters / SD_G3_BM);
                 if (W <= 80) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3x3_glds<80>), g3, dim3(512), SD_G3_LDS(80), s, A);
                 else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3x3_glds<160>), g3, dim3(512), SD_G3_LDS(160), s, A);
@@ -831,9 +818,8 @@ int sd_yolo_forward_host(sd_yolo* y, const uint8_t* bgr, int width, int height, 
     if (!y || !bgr || width < 1 || height < 1 || stride < (size_t)width * 3) return set_err(SD_ERR_INVALID, "bad yolo_forward_host arguments");
     const size_t bytes = stride * (size_t)height;
     if (bytes > y->hostImgCap) {
-        if (y->d_hostImg) (void)hipFree(y->d_hostImg);
-        y->d_hostImg = nullptr; y->hostImgCap = 0;
-        HIPCHK(hipMalloc((void**)&y->d_hostImg, bytes));
+        y->hostImgCap = 0;
+        HIPCHK(y->d_hostImg.alloc(bytes));
         y->hostImgCap = bytes;
     }
     HIPCHK(hipMemcpyAsync(y->d_hostImg, bgr, bytes, hipMemcpyHostToDevice, y->stream));
@@ -846,9 +832,8 @@ int sd_yolo_mask_host(sd_yolo* y, int frame_cols, int frame_rows, float conf_thr
     if (!y || !mask || frame_cols < 1 || frame_rows < 1 || stride < (size_t)frame_cols) return set_err(SD_ERR_INVALID, "bad yolo_mask_host arguments");
     const size_t bytes = (size_t)frame_cols * frame_rows;
     if (bytes > y->hostMaskCap) {
-        if (y->d_hostMask) (void)hipFree(y->d_hostMask);
-        y->d_hostMask = nullptr; y->hostMaskCap = 0;
-        HIPCHK(hipMalloc((void**)&y->d_hostMask, bytes));
+        y->hostMaskCap = 0;
+        HIPCHK(y->d_hostMask.alloc(bytes));
         y->hostMaskCap = bytes;
     }
     int rc = sd_yolo_mask_device(y, 0, frame_cols, frame_rows, conf_threshold, nms_threshold, y->d_hostMask, (size_t)frame_cols, no_target, nullptr);
@@ -866,7 +851,6 @@ int sd_yolo_boxes_device(sd_yolo* y, int n_images, int frame_cols, int frame_row
         return set_err(SD_ERR_INVALID, "bad yolo_boxes_device arguments");
     if (n_images == 0) return SD_OK;
     hipStream_t s = stream_ ? (hipStream_t)stream_ : y->stream;
-    if (!y->attrNms) { HIPCHK(hipFuncSetAttribute((const void*)k_yolo_nms, hipFuncAttributeMaxDynamicSharedMemorySize, SD_NMS_LDS)); y->attrNms = true; }
     if (y->overlap && y->haveDecoded) HIPCHK(hipStreamWaitEvent(s, y->evDecoded, 0));      // the decodes of the last pass (internal stream)
     hipLaunchKernelGGL(k_yolo_nms, dim3(n_images), dim3(256), SD_NMS_LDS, s, y->d_dets, y->d_ndet, y->detCap, frame_cols, frame_rows, conf_threshold,
                        nms_threshold, d_boxes, d_class_ids, d_confidences, d_n_boxes);
@@ -881,10 +865,10 @@ int sd_yolo_boxes_batch(sd_yolo* y, int n_images, int frame_cols, int frame_rows
     if (!y || !boxes || !n_boxes || n_images < 0 || n_images > y->maxBatch) return set_err(SD_ERR_INVALID, "bad yolo_boxes_batch arguments");
     if (!y->d_nmsBoxes) {
         const size_t nB = (size_t)y->maxBatch;
-        HIPCHK(hipMalloc((void**)&y->d_nmsBoxes, nB * SD_MAX_BOXES * 4 * 8)); y->owned.push_back(y->d_nmsBoxes);
-        HIPCHK(hipMalloc((void**)&y->d_nmsCls, nB * SD_MAX_BOXES * 4)); y->owned.push_back(y->d_nmsCls);
-        HIPCHK(hipMalloc((void**)&y->d_nmsConf, nB * SD_MAX_BOXES * 4)); y->owned.push_back(y->d_nmsConf);
-        HIPCHK(hipMalloc((void**)&y->d_nmsN, nB * 4)); y->owned.push_back(y->d_nmsN);
+        SdDevBuf<double> boxesBuf; SdDevBuf<int> cls, nBuf; SdDevBuf<float> conf;
+        HIPCHK(boxesBuf.alloc(nB * SD_MAX_BOXES * 4 * 8)); HIPCHK(cls.alloc(nB * SD_MAX_BOXES * 4));
+        HIPCHK(conf.alloc(nB * SD_MAX_BOXES * 4)); HIPCHK(nBuf.alloc(nB * 4));
+        y->d_nmsCls = std::move(cls); y->d_nmsConf = std::move(conf); y->d_nmsN = std::move(nBuf); y->d_nmsBoxes = std::move(boxesBuf);    // boxes last: they mark the group
     }
     int rc = sd_yolo_boxes_device(y, n_images, frame_cols, frame_rows, conf_threshold, nms_threshold, y->d_nmsBoxes, y->d_nmsCls, y->d_nmsConf,
                                   y->d_nmsN, stream_);

@@ -19,21 +19,28 @@ def _boxes(synth, cfg, seq, t, extra):
     return np.concatenate([rects, extra]) if len(extra) else rects
 
 
-@pytest.fixture(scope="module", params=[0, 5000], ids=["settings", "5000-features-one-box-over-2048"])
+@pytest.fixture(scope="module", params=[0, 5000, -5000],
+                ids=["settings", "5000-features-one-box-over-2048", "5000-features-then-a-smaller-workspace"])
 def scene(request, gpu, fe, orc, synth):
     """params: 0 = the settings file's nFeatures (2000); 5000 = an extractor that yields more than 2048 key points per image AND a box that holds more
     than 2048 of them in both frames -- the reference has no bound here (Frame.cc:555-604 and Tracking.cc:1093-1239 work on std::vectors); rounds 1-3
     refused it (SD_ERR_UNSUPPORTED), since round 4 the key-point tables of k_box_separate / k_separate are sized by the workspace and a box's train
-    descriptors pass through LDS in chunks."""
+    descriptors pass through LDS in chunks.  -5000: the 5000-feature workspace, then a smaller one created after it and kept alive while the large
+    one runs -- the kernels' dynamic-LDS limits only ever grow, a later, smaller workspace must not lower them."""
     import torch
     cfg = dict(synth.KITTI03_RGBD)
-    big = request.param > 0
+    big = request.param != 0
     if big:
-        cfg["n_features"] = request.param
+        cfg["n_features"] = abs(request.param)
     ts = [0, 3]
     fr = _frames(synth, orc, cfg, 8, ts)
     ex = fe.ORBextractor(cfg["n_features"], cfg["scale_factor"], cfg["n_levels"], cfg["ini_th_fast"], cfg["min_th_fast"])
     b = fe.Batch(ex, cfg["width"], cfg["height"], 3)
+    small = None
+    if request.param < 0:
+        s = synth.KITTI03_RGBD
+        small = fe.Batch(fe.ORBextractor(s["n_features"], s["scale_factor"], s["n_levels"], s["ini_th_fast"], s["min_th_fast"]),
+                         s["width"], s["height"], 1)
     b.extract_host(np.stack([g for g, _ in fr]))
     factor = float(np.float32(1.0) / np.float32(cfg["depth_map_factor"]))
     d_dev = torch.from_numpy(np.stack([d for _, d in fr]).view(np.int16)).cuda()
@@ -63,6 +70,8 @@ def scene(request, gpu, fe, orc, synth):
             assert r["Ns"] + r["Nd"] > 2048 and np.diff(r["boxStart"]).max() > 2048, "the big case must put more than 2048 key points into one box (%d, %d)" % (r["Ns"] + r["Nd"], np.diff(r["boxStart"]).max())
     yield dict(b=b, cfg=cfg, ref=ref, ts=ts)
     b.close()
+    if small is not None:
+        small.close()
 
 
 def test_first_separate(scene, fe):
