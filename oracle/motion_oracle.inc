@@ -255,10 +255,15 @@ static inline bool orc_f_inlier(const double* F, double x1, double y1, double x2
 }
 
 // p1 = points_last, p2 = points_current (N x 2 f32).  Outputs: H, F (9 f64, zeros when not found), masks, counts,
-// HorF (9 f32) and the return value of TrackHomo's choice: 1 (H), 2 (F) or 0.
-int orc_estimate_motion(const float* p1, const float* p2, int N, double* Hout, double* Fout, uint8_t* maskH, uint8_t* maskF,
-                        int* nH, int* nF, float* HorF)
+// HorF (9 f32) and the return value of TrackHomo's choice: 1 (H), 2 (F) or 0.  info (6 ints or NULL) tells the tests which
+// branches a point set reached: the winning hypothesis of H and of F (index inside its model, -1 = none), whether the search
+// of H / of F stopped at its checkpoint (1) or ran the full hypothesis set (0), and how many of the hypotheses it looked at
+// were degenerate (the sampler found no 4 / 8 distinct pairs, or the minimal system was singular) for H / for F.
+int orc_estimate_motion_ex(const float* p1, const float* p2, int N, double* Hout, double* Fout, uint8_t* maskH, uint8_t* maskF,
+                           int* nH, int* nF, float* HorF, int* info /*[6]: bestH bestF stopH stopF degH degF*/)
 {
+    int stopH = 0, stopF = 0, degH = 0, degF = 0;
+    if (info) { info[0] = -1; info[1] = -1; for (int k = 2; k < 6; k++) info[k] = 0; }
     for (int k = 0; k < 9; k++) { Hout[k] = 0; Fout[k] = 0; HorF[k] = 0; }
     for (int i = 0; i < N; i++) { maskH[i] = 0; maskF[i] = 0; }
     *nH = 0; *nF = 0;
@@ -274,10 +279,10 @@ int orc_estimate_motion(const float* p1, const float* p2, int N, double* Hout, d
     int bestH = -1, bestHn = 0;
     double Hbest[9] = {0};
     for (int h = 0; h < ORC_MOTION_KH; h++) {
-        if (h == ORC_MOTION_KH0 && (double)bestHn >= ORC_MOTION_WH * (double)N) break;        // the checkpoint test
+        if (h == ORC_MOTION_KH0 && (double)bestHn >= ORC_MOTION_WH * (double)N) { stopH = 1; break; }        // the checkpoint test
         int idx[4];
         double Hn[9], H[9];
-        if (!orc_motion_sample(0, h, N, 4, idx) || !orc_h_from_4(n1.data(), n2.data(), idx, Hn)) continue;
+        if (!orc_motion_sample(0, h, N, 4, idx) || !orc_h_from_4(n1.data(), n2.data(), idx, Hn)) { degH++; continue; }
         orc_h_denormalize(Hn, a, b, H);
         int cnt = 0;
         for (int i = 0; i < N; i++) cnt += orc_h_inlier(H, p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]);
@@ -308,10 +313,10 @@ int orc_estimate_motion(const float* p1, const float* p2, int N, double* Hout, d
     int bestF = -1, bestFn = 0;
     double Fbest[9] = {0};
     for (int h = 0; h < ORC_MOTION_KF; h++) {
-        if (h == ORC_MOTION_KF0 && (double)bestFn >= ORC_MOTION_WF * (double)N) break;
+        if (h == ORC_MOTION_KF0 && (double)bestFn >= ORC_MOTION_WF * (double)N) { stopF = 1; break; }
         int idx[8];
         double Fn[9], F[9];
-        if (!orc_motion_sample(1, h, N, 8, idx) || !orc_f_from_8(n1.data(), n2.data(), idx, Fn)) continue;
+        if (!orc_motion_sample(1, h, N, 8, idx) || !orc_f_from_8(n1.data(), n2.data(), idx, Fn)) { degF++; continue; }
         orc_f_denormalize(Fn, a, b, F);
         int cnt = 0;
         for (int i = 0; i < N; i++) cnt += orc_f_inlier(F, p1[2 * i], p1[2 * i + 1], p2[2 * i], p2[2 * i + 1]);
@@ -322,6 +327,7 @@ int orc_estimate_motion(const float* p1, const float* p2, int N, double* Hout, d
         *nF = bestFn;
         memcpy(Fout, Fbest, sizeof(Fbest));
     }
+    if (info) { info[0] = bestH; info[1] = bestF; info[2] = stopH; info[3] = stopF; info[4] = degH; info[5] = degF; }
     // ---- Tracking.cc:1060-1072
     if (*nF > 10 || *nH > 10) {
         if (*nH > *nF) { for (int k = 0; k < 9; k++) HorF[k] = (float)Hout[k]; return 1; }
@@ -329,4 +335,10 @@ int orc_estimate_motion(const float* p1, const float* p2, int N, double* Hout, d
         return 2;
     }
     return 0;
+}
+
+int orc_estimate_motion(const float* p1, const float* p2, int N, double* Hout, double* Fout, uint8_t* maskH, uint8_t* maskF,
+                        int* nH, int* nF, float* HorF)
+{
+    return orc_estimate_motion_ex(p1, p2, N, Hout, Fout, maskH, maskF, nH, nF, HorF, nullptr);
 }

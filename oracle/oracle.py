@@ -399,6 +399,20 @@ def search_by_bow(kpKF, descKF, kf_valid, bowKF, kpF, descF, bowF, nnratio, chec
     return match, nm
 
 
+def estimate_motion_ex(points_last, points_current):
+    """estimate_motion plus the branches the search took: best_h / best_f (winning hypothesis inside its model, -1 = none),
+    stop_h / stop_f (the search stopped at its checkpoint), deg_h / deg_f (degenerate hypotheses among those looked at)."""
+    p1 = np.ascontiguousarray(points_last, np.float32).reshape(-1, 2); p2 = np.ascontiguousarray(points_current, np.float32).reshape(-1, 2)
+    N = len(p1)
+    H = np.zeros(9, np.float64); F = np.zeros(9, np.float64); mh = np.zeros(max(N, 1), np.uint8); mf = np.zeros(max(N, 1), np.uint8)
+    nh, nf = C.c_int(), C.c_int(); hf = np.zeros(9, np.float32); info = np.zeros(6, np.int32)
+    f = lib().orc_estimate_motion_ex
+    f.restype = C.c_int
+    flag = f(_p(p1), _p(p2), N, _p(H), _p(F), _p(mh), _p(mf), C.byref(nh), C.byref(nf), _p(hf), _p(info))
+    return dict(H=H.reshape(3, 3), F=F.reshape(3, 3), mask_h=mh[:N], mask_f=mf[:N], n_h=nh.value, n_f=nf.value, HorF=hf.reshape(3, 3), flag=flag,
+                best_h=int(info[0]), best_f=int(info[1]), stop_h=bool(info[2]), stop_f=bool(info[3]), deg_h=int(info[4]), deg_f=int(info[5]))
+
+
 def estimate_motion(points_last, points_current):
     """The H / F fit of Tracking::TrackHomo (spec Q13) -> dict(H, F, mask_h, mask_f, n_h, n_f, HorF, flag)."""
     p1 = np.ascontiguousarray(points_last, np.float32).reshape(-1, 2); p2 = np.ascontiguousarray(points_current, np.float32).reshape(-1, 2)

@@ -371,7 +371,13 @@ static int batch_create_impl(std::unique_ptr<sd_batch>& out, sd_extractor* ex, i
     HIPCHK(hipMemset(b->d_fb, 0, nI * sizeof(SdFrameBoxes)));
     // the dynamic-object kernels keep per-key-point tables in LDS, sized by this workspace's capacity
     const int needSep = (int)sd_separate_lds(P.kpCap), needBox = (int)sd_box_separate_lds(P.kpCap);
-    b->cullOk = needSep <= 160 * 1024 && needBox <= 160 * 1024;       // otherwise sd_batch_first_separate / sd_batch_separate refuse (extraction and matching are not affected)
+    // The kernels' static LDS (k_box_separate: 3 KB of per-box tables) counts against the same 160 KB: without it a capacity of
+    // 8,034 to 8,188 slots passed this test and the workspace could not be created at all -- raising the limit failed with
+    // "invalid argument" (tests/test_gpu_motion.py, the 8120-feature workspace).
+    hipFuncAttributes faSep, faBox;
+    HIPCHK(hipFuncGetAttributes(&faSep, (const void*)k_separate));
+    HIPCHK(hipFuncGetAttributes(&faBox, (const void*)k_box_separate));
+    b->cullOk = needSep + faSep.sharedSizeBytes <= 160 * 1024 && needBox + faBox.sharedSizeBytes <= 160 * 1024;       // otherwise sd_batch_first_separate / sd_batch_separate refuse (extraction and matching are not affected)
     if (b->cullOk) {
         HIPCHK(sd_raise_lds_limit((const void*)k_separate, needSep));
         HIPCHK(sd_raise_lds_limit((const void*)k_box_separate, needBox));

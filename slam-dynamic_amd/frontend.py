@@ -290,6 +290,13 @@ class Batch:
         check(lib().sd_batch_results_device(self.h, C.byref(kp), C.byref(desc), C.byref(cnt), C.byref(cap)))
         return kp.value, desc.value, cnt.value, cap.value
 
+    def matches_device(self):
+        """Device pointers of the projection matcher's per-pair arrays: (d_match, d_pairs, d_npairs, d_nmatches, cap)."""
+        m, pr, npr, nm = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        cap = C.c_int()
+        check(lib().sd_batch_matches_device(self.h, C.byref(m), C.byref(pr), C.byref(npr), C.byref(nm), C.byref(cap)))
+        return m.value, pr.value, npr.value, nm.value, cap.value
+
     # -- Frame::ComputeStereoMatches
     def stereo_match(self, n_frames, mbf, fx, stream=None):
         check(lib().sd_batch_stereo_match(self.h, n_frames, mbf, fx, C.c_void_p(stream or 0)))

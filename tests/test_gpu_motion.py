@@ -1,7 +1,11 @@
 """GPU parity of the TrackHomo model fit (spec Q13): H / F from the projection matcher's point pairs, inlier masks and
 the reference's choice between the two (Tracking.cc:1026-1075), against the oracle's independent restatement."""
+import collections
+
 import numpy as np
 import pytest
+
+import motion_cases as mc
 
 pytestmark = pytest.mark.gpu
 
@@ -89,3 +93,105 @@ def test_estimate_motion_below_the_checkpoints(gpu, fe, orc, synth):
         assert below_h > 0 and below_f > 0, "the case must exercise the full hypothesis sets"
     finally:
         b.close()
+
+
+# ---- crafted point sets (tests/motion_cases.py) written over the projection pairs of a workspace of their own
+
+N_SETS = 8                                                  # sets per launch: the workspaces hold 16 extracted images
+
+
+@pytest.fixture(scope="module")
+def kitti_ws(gpu, fe, synth):
+    ws = mc.Workspace(fe, synth, dict(synth.KITTI_STEREO), N_SETS)
+    yield ws
+    ws.close()
+
+
+@pytest.fixture(scope="module")
+def large_ws(gpu, fe, synth):
+    """The 5000-feature extractor of test_gpu_cull.py: kp_capacity above 4092, so k_motion_prepare stages more than 64 KB of
+    points in dynamic LDS, and sets above 2048 pairs take a second pass of k_motion_count."""
+    ws = mc.Workspace(fe, synth, dict(synth.KITTI03_RGBD, n_features=5000), N_SETS)
+    yield ws
+    ws.close()
+
+
+@pytest.fixture(scope="module")
+def bound_ws(gpu, fe, synth):
+    """8120 features: kp_capacity 8184, the largest the extractor's plan gives under the documented bound of 8188 slots
+    (include/sd_frontend.h, the dynamic-object tables) -- 131 KB of staged points in k_motion_prepare."""
+    ws = mc.Workspace(fe, synth, dict(synth.KITTI03_RGBD, n_features=8120), N_SETS)
+    yield ws
+    ws.close()
+
+
+@pytest.mark.parametrize("which", ["kitti_ws", "large_ws", "bound_ws"], ids=["kitti", "5000-features", "8120-features"])
+def test_crafted_sets_match_oracle(request, orc, which):
+    """All of motion_cases.suite() that fits the workspace, every size up to and including kp_capacity, eight sets per launch:
+    flag, counts and masks equal to the oracle, H and F within 1e-9 and HorF within 1e-6 of max|oracle|, all zero where the
+    oracle finds no fit.  Every mismatch is collected."""
+    ws = request.getfixturevalue(which)
+    if which == "large_ws":
+        assert ws.cap * 16 > 64 * 1024 and ws.cap > 4097, ws.cap
+    if which == "bound_ws":
+        assert 8188 - 8 < ws.cap <= 8188, ws.cap
+    sets = mc.suite(capacities=(ws.cap,), max_n=ws.cap)
+    got = mc.run_all(ws, [(p1, p2) for _, p1, p2 in sets])
+    bad, tally, dev_h, dev_f = [], collections.Counter(), 0.0, 0.0
+    for (name, p1, p2), g in zip(sets, got):
+        o = orc.estimate_motion_ex(p1, p2)
+        what, dh, df, same = mc.compare(g, o)
+        if what:
+            bad.append("%s: %s" % (name, "; ".join(what)))
+        dev_h, dev_f = max(dev_h, dh), max(dev_f, df)
+        tally["flag %d" % o["flag"]] += 1; tally["bit-identical H, F, HorF"] += int(same); tally["over 2048 pairs"] += int(len(p1) > 2048)
+        tally["H checkpoint stops"] += int(o["stop_h"]); tally["F checkpoint stops"] += int(o["stop_f"])
+    print("\ncrafted sets on %s (kp_capacity %d): %d sets, %s, largest |gpu - oracle| / max|oracle|: H %.3g, F %.3g"
+          % (which, ws.cap, len(sets), dict(tally), dev_h, dev_f))
+    assert max(len(p1) for _, p1, _ in sets) == ws.cap
+    assert not bad, "%d of %d sets differ from the oracle, the first: %s" % (len(bad), len(sets), " | ".join(bad[:5]))
+
+
+def test_workspace_under_the_capacity_bound_refuses_only_the_cull(bound_ws, fe):
+    """kp_capacity 8184: 20 B per slot of k_box_separate's dynamic tables plus its 3 KB of static LDS exceed the 160 KB, so the
+    two dynamic-object calls refuse -- and nothing else does: sd_batch_create failed on such a workspace ("invalid argument" from
+    raising the kernel's LDS limit) while only the dynamic part was counted."""
+    with pytest.raises(fe.SdError) as e:
+        bound_ws.b.first_separate([0], [np.array([[10.0, 10.0, 100.0, 100.0]])], [np.array([1], np.int32)])
+    assert e.value.code == fe.SD_ERR_UNSUPPORTED
+
+
+_FIELDS = ("H", "F", "HorF", "mask_h", "mask_f")
+
+
+def _bytes(g):
+    return tuple(g[k].tobytes() for k in _FIELDS) + (g["n_h"], g["n_f"], g["flag"])
+
+
+def test_sets_do_not_depend_on_batch_position(large_ws):
+    """Sixteen sets of mixed sizes and kinds: in one batch (two launches), in reversed order, each alone, and the same batch
+    twice -- the same bytes every time."""
+    ws = large_ws
+    names = ("planar-30%-N0", "general-20%-N7", "planar-0%-N8", "planar-0%-N11", "noise_only-x-N65", "planar-55%-N257", "general-45%-N513",
+             "planar-30%-N1000", "general-20%-N2049", "planar-55%-N4097", "degenerate-same_y2-N50", "degenerate-collinear-N300", "all_inliers-N11",
+             "exact_share-N100-53", "scaled-10000-0.01-N600", "noise_only-x-N4096")
+    by_name = {n: (p1, p2) for n, p1, p2 in mc.suite()}
+    sets = [by_name[n] for n in names]
+    first = [_bytes(g) for g in mc.run_all(ws, sets)]
+    assert [_bytes(g) for g in mc.run_all(ws, sets)] == first, "the same batch twice"
+    rev = [_bytes(g) for g in mc.run_all(ws, sets[::-1])][::-1]
+    alone = [_bytes(mc.run_sets(ws, [s])[0]) for s in sets]
+    for k, n in enumerate(names):
+        assert rev[k] == first[k], "%s differs in the reversed batch" % n
+        assert alone[k] == first[k], "%s differs when run alone" % n
+    assert len({f[:2] for f in first}) > 8                   # the sets did produce different models
+
+
+def test_randomised_motion_sets(gpu):
+    """24 fixed draws of tools/fuzz_motion.py on the 5000-feature workspace (pair count log-uniform in [0, kp_capacity], planar /
+    general / unrelated scenes, outlier share up to 0.7, noise up to 2 px, one draw in ten a degeneracy): identical to the oracle, H / F / HorF byte for byte.  (600 draws were run when written: none differs; 301 / 6 / 293
+    with flag 0 / 1 / 2, 64 above 2048 pairs, 56 H and 110 F searches stopped at their checkpoint, 24 sets with degenerate hypotheses.)"""
+    import importlib.util, os
+    spec = importlib.util.spec_from_file_location("fuzz_motion", os.path.join(os.path.dirname(__file__), "..", "tools", "fuzz_motion.py"))
+    m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
+    assert m.run(24, 17, n_features=5000) == 0
