@@ -158,11 +158,16 @@ def depth_to_f32(depth_u16, factor):
     return out
 
 
-def stereo_from_rgbd(kp, depth_f32, mbf):
+def stereo_from_rgbd(kp, depth_f32, mbf, kp_un=None):
+    """kp_un: mvKeysUn (None: == kp).  The depth is read at kp, the subtraction uses kp_un's x (Frame.cc:1057-1069)."""
     kp = np.ascontiguousarray(kp); d = np.ascontiguousarray(depth_f32, np.float32)
     n = len(kp)
     ur = np.zeros(n, np.float32); dep = np.zeros(n, np.float32)
-    lib().orc_stereo_from_rgbd(_p(kp), n, _p(d), d.shape[1], d.shape[0], C.c_float(mbf), _p(ur), _p(dep))
+    if kp_un is not None:
+        kp_un = np.ascontiguousarray(kp_un)
+        assert len(kp_un) == n
+    lib().orc_stereo_from_rgbd_un(_p(kp), _p(kp_un) if kp_un is not None else None, n, _p(d), d.shape[1], d.shape[0], C.c_float(mbf),
+                                  _p(ur), _p(dep))
     return ur, dep
 
 
@@ -174,6 +179,28 @@ def stereo_matches(exL, exR, kpL, descL, kpR, descR, mbf, fx):
     nm = lib().orc_stereo_matches(exL.h, exR.h, _p(kpL), _p(descL), n, _p(kpR), _p(descR), len(kpR), C.c_float(mbf),
                                   C.c_float(fx), _p(ur), _p(dep), _p(bd))
     return ur, dep, bd, nm
+
+
+# outcome codes of stereo_matches_ex, in the order of the exits of Frame::ComputeStereoMatches
+(ST_NO_CANDIDATE, ST_MAXU_NEGATIVE, ST_HAMMING, ST_WINDOW, ST_EDGE_SHIFT, ST_DELTA, ST_DISPARITY, ST_CLAMPED, ST_MATCHED,
+ ST_REMOVED) = range(10)
+ST_NAMES = ("no_candidate", "maxU<0", "hamming>=75", "window", "edge_shift", "deltaR", "disparity", "clamped", "matched", "removed")
+
+
+def stereo_matches_ex(exL, exR, kpL, descL, kpR, descR, mbf, fx):
+    """stereo_matches plus where every left key point left the function: a dict with ur, dep, sad, nm and, per left key point,
+    outcome (ST_*), best_idx (-1: no admissible candidate under TH_HIGH), hamming, ties (admissible candidates at the best
+    distance), shift (-99: the SAD step was not reached); per frame median and th_dist (-1 without a match)."""
+    kpL = np.ascontiguousarray(kpL); kpR = np.ascontiguousarray(kpR)
+    descL = np.ascontiguousarray(descL, np.uint8); descR = np.ascontiguousarray(descR, np.uint8)
+    n = len(kpL)
+    ur = np.zeros(n, np.float32); dep = np.zeros(n, np.float32); bd = np.zeros(n, np.int32)
+    rep = [np.zeros(n, np.int32) for _ in range(5)]
+    fr = np.zeros(3, np.float32)
+    nm = lib().orc_stereo_matches_ex(exL.h, exR.h, _p(kpL), _p(descL), n, _p(kpR), _p(descR), len(kpR), C.c_float(mbf),
+                                     C.c_float(fx), _p(ur), _p(dep), _p(bd), *[_p(r) for r in rep], _p(fr))
+    return dict(ur=ur, dep=dep, sad=bd, nm=nm, outcome=rep[0], best_idx=rep[1], hamming=rep[2], ties=rep[3], shift=rep[4],
+                median=float(fr[1]), th_dist=float(fr[2]))
 
 
 def grid_cells(kp, cam10):

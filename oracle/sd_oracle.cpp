@@ -514,27 +514,49 @@ void orc_depth_to_f32(const uint16_t* src, int w, int h, int sstride_elems, floa
 }
 
 // Frame::ComputeStereoFromRGBD (Frame.cc:1051-1072); mvKeysUn == mvKeys (k1 == 0, Frame.cc:814-818)
-void orc_stereo_from_rgbd(const void* kps_, int N, const float* depth, int w, int /*h*/, float mbf, float* uRight,
-                          float* mvDepth)
+// kpsUn_ (may be null: == kps_) is mvKeysUn: the lookup is at mvKeys, the subtraction uses mvKeysUn (Frame.cc:1057-1069).
+void orc_stereo_from_rgbd_un(const void* kps_, const void* kpsUn_, int N, const float* depth, int w, int /*h*/, float mbf,
+                             float* uRight, float* mvDepth)
 {
     const KeyPoint* kps = (const KeyPoint*)kps_;
+    const KeyPoint* kpsUn = kpsUn_ ? (const KeyPoint*)kpsUn_ : kps;
     for (int i = 0; i < N; i++) {
         uRight[i] = -1; mvDepth[i] = -1;
         const float v = kps[i].y, u = kps[i].x;
         const float d = depth[(size_t)(int)v * w + (int)u];
-        if (d > 0) { mvDepth[i] = d; uRight[i] = kps[i].x - mbf / d; }
+        if (d > 0) { mvDepth[i] = d; uRight[i] = kpsUn[i].x - mbf / d; }
     }
+}
+void orc_stereo_from_rgbd(const void* kps_, int N, const float* depth, int w, int h, float mbf, float* uRight,
+                          float* mvDepth)
+{
+    orc_stereo_from_rgbd_un(kps_, 0, N, depth, w, h, mbf, uRight, mvDepth);
 }
 
 // Frame::ComputeStereoMatches (Frame.cc:874-1048).  hL/hR: extractors that processed the
 // left/right image (their mvImagePyramid is read at :971,:988).  Returns #matched before
 // the median filter; bestDist_out (optional) gets the SAD distance per left kp (-1 none).
-int orc_stereo_matches(void* hL, void* hR, const void* kL_, const uint8_t* dL, int N, const void* kR_, const uint8_t* dR,
-                       int Nr, float mbf, float fx, float* mvuRight, float* mvDepth, int* bestDist_out)
+// The _ex form also says, per left key point, where it left the function (the ORC_ST_* codes, in the order of the reference's
+// exits), the best right index (-1: no admissible candidate under TH_HIGH), the best Hamming distance, how many admissible
+// candidates had it, and the best shift (-99: the SAD step was not reached); frame_out = {matches, median, thDist}
+// (median = thDist = -1 without a match).  Every report pointer may be null.
+enum { ORC_ST_NO_CANDIDATE = 0, ORC_ST_MAXU_NEGATIVE = 1, ORC_ST_HAMMING = 2, ORC_ST_WINDOW = 3, ORC_ST_EDGE_SHIFT = 4,
+       ORC_ST_DELTA = 5, ORC_ST_DISPARITY = 6, ORC_ST_CLAMPED = 7, ORC_ST_MATCHED = 8, ORC_ST_REMOVED = 9 };
+int orc_stereo_matches_ex(void* hL, void* hR, const void* kL_, const uint8_t* dL, int N, const void* kR_, const uint8_t* dR,
+                          int Nr, float mbf, float fx, float* mvuRight, float* mvDepth, int* bestDist_out,
+                          int* outcome, int* bestIdx_out, int* bestHamming_out, int* ties_out, int* bestShift_out, float* frame_out)
 {
     Extractor* eL = (Extractor*)hL; Extractor* eR = (Extractor*)hR;
     const KeyPoint* mvKeys = (const KeyPoint*)kL_; const KeyPoint* mvKeysRight = (const KeyPoint*)kR_;
-    for (int i = 0; i < N; i++) { mvuRight[i] = -1.0f; mvDepth[i] = -1.0f; if (bestDist_out) bestDist_out[i] = -1; }
+    for (int i = 0; i < N; i++) {
+        mvuRight[i] = -1.0f; mvDepth[i] = -1.0f; if (bestDist_out) bestDist_out[i] = -1;
+        if (outcome) outcome[i] = ORC_ST_NO_CANDIDATE;
+        if (bestIdx_out) bestIdx_out[i] = -1;
+        if (bestHamming_out) bestHamming_out[i] = TH_HIGH;
+        if (ties_out) ties_out[i] = 0;
+        if (bestShift_out) bestShift_out[i] = -99;
+    }
+    if (frame_out) { frame_out[0] = 0; frame_out[1] = -1; frame_out[2] = -1; }
     const int thOrbDist = (TH_HIGH + TH_LOW) / 2;
     const int nRows = eL->mvImagePyramid[0].H;
     std::vector<std::vector<size_t> > vRowIndices(nRows);
@@ -554,16 +576,18 @@ int orc_stereo_matches(void* hL, void* hR, const void* kL_, const uint8_t* dL, i
     const float minD = 0;
     const float maxD = mbf / minZ;
     std::vector<std::pair<int, int> > vDistIdx;
+#define ORC_ST_EXIT(code) { if (outcome) outcome[iL] = (code); continue; }
     for (int iL = 0; iL < N; iL++) {
         const KeyPoint& kpL = mvKeys[iL];
         const int levelL = kpL.octave;
         const float vL = kpL.y, uL = kpL.x;
         const std::vector<size_t>& vCandidates = vRowIndices[(size_t)vL];
-        if (vCandidates.empty()) continue;
+        if (vCandidates.empty()) ORC_ST_EXIT(ORC_ST_NO_CANDIDATE);
         const float minU = uL - maxD, maxU = uL - minD;
-        if (maxU < 0) continue;
+        if (maxU < 0) ORC_ST_EXIT(ORC_ST_MAXU_NEGATIVE);
         int bestDist = TH_HIGH;
         size_t bestIdxR = 0;
+        int ties = 0;
         const uint8_t* dl = dL + (size_t)iL * 32;
         for (size_t iC = 0; iC < vCandidates.size(); iC++) {
             const size_t iR = vCandidates[iC];
@@ -572,10 +596,15 @@ int orc_stereo_matches(void* hL, void* hR, const void* kL_, const uint8_t* dL, i
             const float uR = kpR.x;
             if (uR >= minU && uR <= maxU) {
                 const int dist = DescriptorDistance(dl, dR + iR * 32);
-                if (dist < bestDist) { bestDist = dist; bestIdxR = iR; }
+                if (dist < bestDist) { bestDist = dist; bestIdxR = iR; ties = 1; }
+                else if (dist == bestDist && dist < TH_HIGH) ties++;
             }
         }
-        if (bestDist < thOrbDist) {
+        if (bestHamming_out) bestHamming_out[iL] = bestDist;
+        if (ties_out) ties_out[iL] = ties;
+        if (bestIdx_out && bestDist < TH_HIGH) bestIdx_out[iL] = (int)bestIdxR;
+        if (!(bestDist < thOrbDist)) ORC_ST_EXIT(ORC_ST_HAMMING);
+        {
             const float uR0 = mvKeysRight[bestIdxR].x;
             const float scaleFactor = mvInvScaleFactors[kpL.octave];
             const float scaleduL = roundf(kpL.x * scaleFactor);
@@ -592,7 +621,7 @@ int orc_stereo_matches(void* hL, void* hR, const void* kL_, const uint8_t* dL, i
             float vDists[2 * 5 + 1];
             const float iniu = scaleduR0 + L - w;
             const float endu = scaleduR0 + L + w + 1;
-            if (iniu < 0 || endu >= PR.W) continue;
+            if (iniu < 0 || endu >= PR.W) ORC_ST_EXIT(ORC_ST_WINDOW);
             for (int incR = -L; incR <= +L; incR++) {
                 const uint8_t* IR = PR.interior() + (ptrdiff_t)((int)(scaledvL - w)) * PR.stride + (int)(scaleduR0 + incR - w);
                 const float cR = (float)IR[w * PR.stride + w];
@@ -606,34 +635,45 @@ int orc_stereo_matches(void* hL, void* hR, const void* kL_, const uint8_t* dL, i
                 if (dist < bestDistS) { bestDistS = (int)dist; bestincR = incR; }
                 vDists[L + incR] = dist;
             }
-            if (bestincR == -L || bestincR == L) continue;
+            if (bestShift_out) bestShift_out[iL] = bestincR;
+            if (bestincR == -L || bestincR == L) ORC_ST_EXIT(ORC_ST_EDGE_SHIFT);
             const float dist1 = vDists[L + bestincR - 1];
             const float dist2 = vDists[L + bestincR];
             const float dist3 = vDists[L + bestincR + 1];
             const float deltaR = (dist1 - dist3) / (2.0f * (dist1 + dist3 - 2.0f * dist2));
-            if (deltaR < -1 || deltaR > 1) continue;
+            if (deltaR < -1 || deltaR > 1) ORC_ST_EXIT(ORC_ST_DELTA);
             float bestuR = mvScaleFactors[kpL.octave] * ((float)scaleduR0 + (float)bestincR + deltaR);
             float disparity = (uL - bestuR);
             if (disparity >= minD && disparity < maxD) {
-                if (disparity <= 0) { disparity = 0.01; bestuR = uL - 0.01; }
+                if (outcome) outcome[iL] = ORC_ST_MATCHED;
+                if (disparity <= 0) { disparity = 0.01; bestuR = uL - 0.01; if (outcome) outcome[iL] = ORC_ST_CLAMPED; }
                 mvDepth[iL] = mbf / disparity;
                 mvuRight[iL] = bestuR;
                 vDistIdx.push_back(std::pair<int, int>(bestDistS, iL));
                 if (bestDist_out) bestDist_out[iL] = bestDistS;
-            }
+            } else ORC_ST_EXIT(ORC_ST_DISPARITY);
         }
     }
+#undef ORC_ST_EXIT
     int nm = (int)vDistIdx.size();
     if (vDistIdx.empty()) return 0;   // reference: UB at Frame.cc:1035 (quirk C10)
     std::sort(vDistIdx.begin(), vDistIdx.end());
     const float median = (float)vDistIdx[vDistIdx.size() / 2].first;
     const float thDist = 1.5f * 1.4f * median;
+    if (frame_out) { frame_out[0] = (float)nm; frame_out[1] = median; frame_out[2] = thDist; }
     for (int i = (int)vDistIdx.size() - 1; i >= 0; i--) {
         if (vDistIdx[i].first < thDist) break;
         mvuRight[vDistIdx[i].second] = -1;
         mvDepth[vDistIdx[i].second] = -1;
+        if (outcome) outcome[vDistIdx[i].second] = ORC_ST_REMOVED;
     }
     return nm;
+}
+
+int orc_stereo_matches(void* hL, void* hR, const void* kL_, const uint8_t* dL, int N, const void* kR_, const uint8_t* dR,
+                       int Nr, float mbf, float fx, float* mvuRight, float* mvDepth, int* bestDist_out)
+{
+    return orc_stereo_matches_ex(hL, hR, kL_, dL, N, kR_, dR, Nr, mbf, fx, mvuRight, mvDepth, bestDist_out, 0, 0, 0, 0, 0, 0);
 }
 
 #include "frame_oracle.inc"

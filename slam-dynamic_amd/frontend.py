@@ -315,6 +315,11 @@ class Batch:
         check(lib().sd_batch_rgbd_from_f32(self.h, C.c_void_p(d_depth_ptr), stride_elems, pitch_elems, n, mbf,
                                            C.c_void_p(stream or 0)))
 
+    def rgbd_from_f32_scaled(self, d_depth_ptr, stride_elems, pitch_elems, n, depth_factor, mbf, stream=None):
+        """A CV_32F depth map times mDepthMapFactor (Tracking.cc:271-272 on a float image), fused into the lookup."""
+        check(lib().sd_batch_rgbd_from_f32_scaled(self.h, C.c_void_p(d_depth_ptr), stride_elems, pitch_elems, n, depth_factor,
+                                                  mbf, C.c_void_p(stream or 0)))
+
     def download_rgbd(self, image):
         ur = np.zeros(self.cap, np.float32); dep = np.zeros(self.cap, np.float32)
         check(lib().sd_batch_download_rgbd(self.h, image, _p(ur), _p(dep), self.cap))
