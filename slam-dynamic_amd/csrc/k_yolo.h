@@ -12,6 +12,7 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include "k_sort.h"
+#include "sd_yolo_plan.h"      // the tile sizes the host's choice of kernel depends on: SD_CV_*, SD_C3_*, SD_G3_BM / BN
 
 typedef _Float16 sd_h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 sd_h4 __attribute__((ext_vector_type(4)));
@@ -28,9 +29,6 @@ struct SdConvArgs {
     int Ho, Wo, cout, coutPad, outStride, outOff, resStride;
     int ksize, stride, pad, leaky;
 };
-
-#define SD_CV_BM 64          // couts per workgroup
-#define SD_CV_BN 256         // pixels per workgroup
 
 // 4 waves, each 64 couts x 64 pixels = 2 x 2 MFMA tiles of 32 x 32.  K is walked in steps of BK channels of one
 // filter tap; the global loads of step k+1 are issued into registers before the MFMAs of step k and written to
@@ -157,11 +155,7 @@ __global__ void __launch_bounds__(256) k_conv_mfma(SdConvArgs A)
 // nine taps read their B fragments from it at row offsets kh*W + kw; out-of-image taps read a zero row.  Only the
 // 128 x 32 weight tile changes per tap (double-buffered, prefetched through registers, one barrier per tap).
 // Wave tile: 128 filters x 64 pixels = 4 x 2 MFMA 32x32x16 tiles.
-#define SD_C3_BM 128
-#define SD_C3_BN 256
-#define SD_C3_BK 32
 #define SD_C3_LD 40          // LDS row length in halfs (80 B: conflict-free ds_read_b128 over consecutive rows)
-#define SD_C3_MAXW 80
 #define SD_C3_XROWS (SD_C3_BN + 2 * SD_C3_MAXW + 2)
 #define SD_C3_XCH ((SD_C3_XROWS * 4 + 255) / 256)      // 16-B activation chunks per thread per channel chunk
 __global__ void __launch_bounds__(256, 2) k_conv3x3_flat(SdConvArgs A)
@@ -299,8 +293,6 @@ __global__ void __launch_bounds__(256, 2) k_conv3x3_flat(SdConvArgs A)
 //   * an LDS-DMA wave-instruction writes 1 KiB linearly (16 rows x 64 B), so rows cannot be padded: the 16-byte slot a
 //     lane fills holds channel group q ^ ((row >> 2) & 3) (swizzle applied on the SOURCE address) and fragment reads apply
 //     the same XOR, which keeps every ds_read_b128 lane group on 16 distinct bank quads.
-#define SD_G3_BM 128
-#define SD_G3_BN 512
 #define SD_G3_NW 5
 #define SD_G3_WBYTES (SD_G3_BM * 64)
 // per maximum map width MAXW (80 for the 80/40/20-wide maps, 160 for the 160-wide ones):

@@ -5,9 +5,10 @@
 // [coutPad][taps][cin] f32 with batch-norm folded in f32.
 //   k_blob_from_image_f32   blobFromImage -> NHWC f32 x 4 channels (R, G, B, 0: one 16-byte piece per pixel; the first layer pairs two
 //                           filter taps into one 8-wide K chunk, see `pair` below)
-//   k_conv_f32<BK>          implicit-GEMM convolution, 1x1 / 3x3, stride 1 / 2, + bias + leaky ReLU + shortcut
+//   k_conv_f32<BK, WM, MT, NW>   implicit-GEMM convolution, 1x1 / 3x3, stride 1 / 2, + bias + leaky ReLU + shortcut
+//   k_upsample_into_f32     the up-sampled half of a 2-input [route] whose other half its producer wrote in place
 // One f32 MFMA is 64 cycles for 4096 FLOPs and needs ONE float per operand per lane, so the kernel is MFMA-bound with a
-// plain structure: 8 waves, K walked in steps of BK channels of one filter tap, tiles staged through registers into LDS.  A lane reads
+// plain structure: NW waves, K walked in steps of BK channels of one filter tap, tiles staged through registers into LDS.  A lane reads
 // its fragments as 16-byte pieces: half h of the wave takes floats [4h, 4h + 4) of an 8-wide K chunk, MFMA j of the chunk
 // uses element j on both operands -- which k a (half, j) pair stands for is immaterial as long as A and B agree.
 #pragma once
@@ -26,10 +27,15 @@ struct SdConvArgsF {
     int tilesX, tilesY, groupY;      // pixel tiles, filter tiles (groupY divides tilesY): the launch is 1-D, SD_F32_GRID(tilesX, tilesY) workgroups
 };
 
-// Tile shapes: WM waves along the filters x (8 / WM) waves along the pixels, a wave owns MT x 2 MFMA tiles (32 MT filters x 64
-// pixels).  <32, 2, 2>: 128 filters x 256 pixels (every layer with >= 128 filters); <16, 1, 2>: 64 x 512 and <16 | 8, 1, 1>:
-// 32 x 512 for the three 64- / 32-filter layers at 320 x 240 and the first layer, which would waste half or three quarters of a
-// 128-filter tile.  LDS holds TWO stages: while the MFMAs of stage s run, the tiles of stage s + 1 (fetched into registers one
+// Tile shapes: WM waves along the filters x (NW / WM) waves along the pixels, a wave owns MT x 2 MFMA tiles (32 MT filters x 64
+// pixels), K steps of BK channels.  Four instantiations exist, all launched by the one layer walk of sd_yolo_api.hip as yolo_plan_launch
+// (sd_yolo_plan.h) chooses them, in the f32-class modes for every convolution their Winograd / bf16-limb kernels do not take:
+//   <16, 2, 2, 4>   128 filters x 128 pixels, three workgroups per CU: every layer with more than 64 filters
+//   <16, 1, 2, 4>    64 filters x 256 pixels: the layers with 33 - 64 filters
+//   <16, 1, 1, 4>    32 filters x 256 pixels: the layers with <= 32 filters -- either would waste half or three quarters of a 128-filter tile
+//   <8, 1, 1, 8>     32 filters x 512 pixels on 8 waves: the first layer (3 input channels in `pair` mode)
+// The measurements against the tiles tried and dropped (8-wave 128 x 256, 32-channel steps, 8-wave small tiles): DESIGN.md 4.1.
+// LDS holds TWO stages: while the MFMAs of stage s run, the tiles of stage s + 1 (fetched into registers one
 // step earlier) are written to the other buffer and the global loads of stage s + 2 are issued -- one barrier per step, and
 // neither the address arithmetic of the gather nor the LDS writes sit between two barriers with the MFMA pipe idle.
 template <int BK, int WM, int MT, int NW>
@@ -296,7 +302,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
         }
     }
 }
-#define SD_F32_GRID(tx, ty) (unsigned)((((tx) + 7) / 8) * 8 * (ty))
 #define SD_F32_LDS(BK, WM, MT, NW) (2 * (32 * (MT) * (WM) + 64 * ((NW) / (WM))) * ((BK) + 4) * 4)
 
 // blobFromImage as k_blob_from_image, NHWC f32 with 4 channels (R, G, B after swapRB, then a zero)

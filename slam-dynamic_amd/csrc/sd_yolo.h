@@ -1,5 +1,5 @@
-// Host side of the detector behind the C ABI (included by sd_api.hip): network description, Darknet weight
-// loading with batch-norm folding, forward pass orchestration, and the reference's post-processing.
+// Host side of the detector behind the C ABI (included by sd_yolo_api.hip): the detector object, the resize tables and the
+// reference's post-processing helpers.  The network description and the choice of kernels: sd_yolo_plan.h.
 //   yolov3Segment::yolov3Segment / readNetFromDarknet     src/yolo.cc:15-31
 //   yolov3Segment::Segmentation_                          src/yolo.cc:60-77
 //   yolov3Segment::postprocess_ + rectCenterScale         src/yolo.cc:142-206
@@ -12,23 +12,25 @@
 #include "k_yolo32w.h"
 #include "k_yolo32b.h"
 #include "sd_common.h"
+#include "sd_yolo_plan.h"
 
-struct sd_yolo {
+struct sd_yolo : SdYoloTotals {          // sizes and FLOP totals: yolo_plan_net (sd_yolo_plan.h)
     std::vector<sd_yolo_layer> L;
-    struct Rt { int H = 0, W = 0, C = 0; int cinPad = 0, coutPad = 0; size_t wOff = 0, bOff = 0; _Float16* out = nullptr; int outC = 0; bool alias = false;
-                SdDevBuf<_Float16> own;                      // output storage allocated for this layer; `out` may point into another layer's (alias)
-                bool wino = false; size_t wOffW = 0;
-                bool b3 = false, b3flat = false; int b3wm = 2; size_t wOffB = 0; };          // SD_YOLO_F32X3: this layer runs on bf16 limbs (k_yolo32b.h), its split weights at d_wgtB + wOffB (16-byte units)        // SD_YOLO_F32W: this layer runs as Winograd F(2x2, 3x3), its transformed weights at d_wgtW + wOffW
+    struct Rt : SdYoloLayerPlan {        // a layer's shape record plus where its output lives; outC becomes the route's channel count when a 2-input [route] owns the storage
+        Rt(const SdYoloLayerPlan& p) : SdYoloLayerPlan(p) {}
+        void* out = nullptr;             // activations, _Float16 in the f16 mode and float in the f32-class modes: read through as<T>()
+        bool alias = false;
+        SdDevBuf<unsigned char> own;     // output storage allocated for this layer; `out` may point into another layer's (alias)
+        template <typename T> T* as() const { return (T*)out; }
+    };
     std::vector<Rt> R;
-    int netW = 0, netH = 0, classes = 80, maxBatch = 0, nconv = 0;
-    int f32 = 0;                   // SD_YOLO_F32: activations / weights / arithmetic in f32 (k_yolo32.h); the `out` pointers then hold floats
+    int netW = 0, netH = 0, classes = 80, maxBatch = 0;
+    int f32 = 0;                   // SD_YOLO_F32: activations / weights / arithmetic in f32 (k_yolo32.h)
     SdDevBuf<float> d_blob8; SdDevBuf<float> d_wgt32;
     int wino = 0;                  // SD_YOLO_F32W (k_yolo32w.h): f32 mode with the eligible 3 x 3 stride-1 layers as Winograd F(2x2, 3x3)
-    SdDevBuf<float> d_wgtW; SdDevBuf<float> d_V; size_t wTotalW = 0;
-    int b3 = 0;                    // SD_YOLO_F32X3 (k_yolo32b.h): f32 mode with the >= 128-filter layers on three bf16 limbs per operand
-    SdDevBuf<uint4> d_wgtB; size_t wTotalB = 0;
-    double mfmaFlopsBf16 = 0;      // per image: bf16 MFMA FLOPs executed by the limb kernels (six limb products per product)
-    double mfmaFlops = 0;          // per image, as executed (Winograd layers: 16 multiplies per 2 x 2 block instead of 36)
+    SdDevBuf<float> d_wgtW; SdDevBuf<float> d_V;
+    int b3 = 0;                    // SD_YOLO_F32X3 (k_yolo32b.h): f32 mode with the >= 64-filter layers on three bf16 limbs per operand
+    SdDevBuf<uint4> d_wgtB;
     float anchors[18];
     SdDevBuf<_Float16> d_blob4;   // network input, NHWC f16 x 4 channels
     SdDevBuf<_Float16> d_wgt; SdDevBuf<float> d_bias; SdDevBuf<_Float16> d_zero;
@@ -36,9 +38,8 @@ struct sd_yolo {
     SdDevBuf<SdDet> d_dets; SdDevBuf<int> d_ndet; SdDevBuf<float> d_raw;
     SdDevBuf<uint8_t> d_hostImg; size_t hostImgCap = 0; SdDevBuf<uint8_t> d_hostMask; size_t hostMaskCap = 0;      // sd_yolo_forward_host / mask_host
     SdDevBuf<double> d_nmsBoxes; SdDevBuf<int> d_nmsCls; SdDevBuf<float> d_nmsConf; SdDevBuf<int> d_nmsN;      // sd_yolo_boxes_batch
-    int detCap = 0, totalRows = 0;
+    int detCap = 0;
     int tabW = 0, tabH = 0;
-    size_t wTotal = 0, bTotal = 0;
     bool weightsLoaded = false;
     int lastN = 0;
     hipStream_t stream = nullptr;
@@ -47,45 +48,12 @@ struct sd_yolo {
     bool overlap = false, haveL0 = false, haveDecoded = false, haveNms = false;
     hipStream_t sPre = nullptr, sPost = nullptr;
     hipEvent_t evBlob = nullptr, evL0 = nullptr, evHead[3] = {nullptr, nullptr, nullptr}, evDecoded = nullptr, evNms = nullptr;
-    double convFlops = 0;     // per image
     ~sd_yolo()
     {
         for (hipStream_t q : {stream, sPre, sPost}) if (q) (void)hipStreamDestroy(q);
         for (hipEvent_t e : {evBlob, evL0, evHead[0], evHead[1], evHead[2], evDecoded, evNms}) if (e) (void)hipEventDestroy(e);
     }
 };
-
-static const float kYoloV3Anchors[18] = {10, 13, 16, 30, 33, 23, 30, 61, 62, 45, 59, 119, 116, 90, 156, 198, 373, 326};
-
-// The layer list of src/yolo/yolov3.cfg (107 layers), restated programmatically.
-static void yolo_v3_layers(std::vector<sd_yolo_layer>& L)
-{
-    auto conv = [&](int filters, int size, int stride, int bn = 1, int leaky = 1) {
-        sd_yolo_layer l = {}; l.type = SD_YOLO_CONV; l.filters = filters; l.size = size; l.stride = stride; l.batch_normalize = bn; l.leaky = leaky;
-        L.push_back(l);
-    };
-    auto shortcut = [&](int from) { sd_yolo_layer l = {}; l.type = SD_YOLO_SHORTCUT; l.from[0] = from; l.nfrom = 1; L.push_back(l); };
-    auto route = [&](int a, int b = 0, int n = 1) { sd_yolo_layer l = {}; l.type = SD_YOLO_ROUTE; l.from[0] = a; l.from[1] = b; l.nfrom = n; L.push_back(l); };
-    auto upsample = [&]() { sd_yolo_layer l = {}; l.type = SD_YOLO_UPSAMPLE; l.stride = 2; L.push_back(l); };
-    auto yolo = [&](int m0, int m1, int m2) { sd_yolo_layer l = {}; l.type = SD_YOLO_YOLO; l.mask[0] = m0; l.mask[1] = m1; l.mask[2] = m2; L.push_back(l); };
-    auto res = [&](int c, int n) { for (int i = 0; i < n; i++) { conv(c / 2, 1, 1); conv(c, 3, 1); shortcut(-3); } };
-    conv(32, 3, 1);
-    conv(64, 3, 2); res(64, 1);
-    conv(128, 3, 2); res(128, 2);
-    conv(256, 3, 2); res(256, 8);
-    conv(512, 3, 2); res(512, 8);
-    conv(1024, 3, 2); res(1024, 4);
-    for (int i = 0; i < 3; i++) { conv(512, 1, 1); conv(1024, 3, 1); }
-    conv(255, 1, 1, 0, 0); yolo(6, 7, 8);
-    route(-4); conv(256, 1, 1); upsample(); route(-1, 61, 2);
-    for (int i = 0; i < 3; i++) { conv(256, 1, 1); conv(512, 3, 1); }
-    conv(255, 1, 1, 0, 0); yolo(3, 4, 5);
-    route(-4); conv(128, 1, 1); upsample(); route(-1, 36, 2);
-    for (int i = 0; i < 3; i++) { conv(128, 1, 1); conv(256, 3, 1); }
-    conv(255, 1, 1, 0, 0); yolo(0, 1, 2);
-}
-
-static inline int yolo_resolve(int idx, int from) { return from < 0 ? idx + from : from; }
 
 // cv::resize INTER_LINEAR coefficient tables (same fixed-point scheme as the pyramid, sd_plan.h)
 static void yolo_resize_tables(int sw, int sh, int dw, int dh, std::vector<int16_t>& ct, std::vector<int16_t>& rt)

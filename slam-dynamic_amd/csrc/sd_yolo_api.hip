@@ -1,5 +1,5 @@
 // The detector part of the C ABI (include/sd_frontend.h, sd_yolo_*): its own translation unit, so that a change to a front-end kernel
-// does not recompile the convolution stack and vice versa.  Kernels: k_yolo.h (f16 mode), k_yolo32.h (f32 mode).
+// does not recompile the convolution stack and vice versa.  Kernels: k_yolo.h (f16 mode), k_yolo32.h / k_yolo32w.h / k_yolo32b.h (f32-class modes).
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +11,16 @@
 #include <vector>
 #include "sd_common.h"
 #include "sd_yolo.h"
+
+template <typename T>      // the region layer of a head (its input: layer i - 1), T = float | _Float16
+static void yolo_decode(const sd_yolo* y, const sd_yolo_layer& l, const sd_yolo::Rt& r, int n, float conf_threshold, int rowBase, hipStream_t s)
+{
+    const float* an = y->anchors;
+    const int rows = n * r.H * r.W * 3;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_region_decode<T>), dim3((rows + 255) / 256), dim3(256), 0, s, r.as<const T>(), r.outC, r.H, r.W, n, an[2 * l.mask[0]],
+                       an[2 * l.mask[0] + 1], an[2 * l.mask[1]], an[2 * l.mask[1] + 1], an[2 * l.mask[2]], an[2 * l.mask[2] + 1],
+                       y->netW, y->netH, conf_threshold, rowBase, y->d_dets, y->d_ndet, y->detCap, n == 1 ? y->d_raw : nullptr);
+}
 
 extern "C" {
 
@@ -29,38 +39,47 @@ int sd_yolo_v3_layers(sd_yolo_layer* layers, int cap, int* n, float anchors[18])
     return SD_OK;
 }
 
-// dynamic LDS of k_conv_glds<8, *> / k_conv_glds<4, *>
-static const int kGldsLds8 = 3 * (512 * 64 + SD_G3_WBYTES), kGldsLds4 = 3 * (256 * 64 + SD_G3_WBYTES);
+// The functions of sd_yolo_plan.h's kernel list, by kernel id
+static const void* const kYoloKernelFn[SD_YK_COUNT] = {
+#define X(id, block, ...) (const void*)__VA_ARGS__,
+    SD_YOLO_KERNELS(X)
+#undef X
+};
 
-// The dynamic-LDS limits of the kernels the detector's mode launches, raised once at creation
+// Dynamic LDS of kernel k, from the kernel headers' macros; only k_conv3x3_b3 / k_conv3x3_b3c size theirs by the map width
+static int yolo_kernel_lds(int k, int width)
+{
+    switch (k) {
+    case SD_YK_GLDS_8_1: case SD_YK_GLDS_8_3: return 3 * (512 * 64 + SD_G3_WBYTES);
+    case SD_YK_GLDS_4_1: case SD_YK_GLDS_4_3: return 3 * (256 * 64 + SD_G3_WBYTES);
+    case SD_YK_G3_80: return SD_G3_LDS(80);
+    case SD_YK_G3_160: return SD_G3_LDS(160);
+    case SD_YK_F32_8_1_1_8: return SD_F32_LDS(8, 1, 1, 8);
+    case SD_YK_F32_16_1_1_4: return SD_F32_LDS(16, 1, 1, 4);
+    case SD_YK_F32_16_1_2_4: return SD_F32_LDS(16, 1, 2, 4);
+    case SD_YK_F32_16_2_2_4: return SD_F32_LDS(16, 2, 2, 4);
+    case SD_YK_WINO_16_2: return SD_WINO_LDS(16, 2);
+    case SD_YK_B3_1: return SD_B3_LDS(1);
+    case SD_YK_B3_2: return SD_B3_LDS(2);
+    case SD_YK_B3F_3: case SD_YK_B3F_4: case SD_YK_B3F_5: case SD_YK_B3F_8: return SD_B3F_LDS(width, 128);
+    case SD_YK_B3C_5: case SD_YK_B3C_6: return SD_B3C_LDS(width);
+    default: return 0;      // static LDS only
+    }
+}
+
+// Launches what a launch record says; `args`: the addresses of the kernel's arguments
+static int yolo_launch(const SdYoloLaunch& K, void** args, hipStream_t s)
+{
+    (void)hipLaunchKernel(kYoloKernelFn[K.kernel], dim3(K.gridX, K.gridY), dim3(K.block), args, (size_t)yolo_kernel_lds(K.kernel, K.width), s);
+    LAUNCH_CHECK(kYoloKernelInfo[K.kernel].name);
+    return SD_OK;
+}
+
+// The dynamic-LDS limits of the kernels the detector's mode launches, raised once at creation (for the widest map the plan gives a kernel)
 static int yolo_raise_lds_limits(const sd_yolo* y)
 {
-    if (y->f32) {
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<32, 2, 2, 8>, SD_F32_LDS(32, 2, 2, 8)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<32, 2, 2, 4>, SD_F32_LDS(32, 2, 2, 4)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 1, 2, 8>, SD_F32_LDS(16, 1, 2, 8)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 1, 1, 8>, SD_F32_LDS(16, 1, 1, 8)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<8, 1, 1, 8>, SD_F32_LDS(8, 1, 1, 8)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 1, 2, 4>, SD_F32_LDS(16, 1, 2, 4)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 1, 1, 4>, SD_F32_LDS(16, 1, 1, 4)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_f32<16, 2, 2, 4>, SD_F32_LDS(16, 2, 2, 4)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_wino_gemm_f32<16, 2>, SD_WINO_LDS(16, 2)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_b3<1>, SD_B3_LDS(1)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_b3<2>, SD_B3_LDS(2)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3<3, 2, 2>, SD_B3F_LDS(160, 128)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3<4, 2, 2>, SD_B3F_LDS(160, 128)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3<5, 2, 2>, SD_B3F_LDS(160, 128)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3<8, 2, 2>, SD_B3F_LDS(160, 128)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3c<5>, SD_B3C_LDS(80)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_b3c<6>, SD_B3C_LDS(80)));
-    } else {
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_glds<8, 1>, kGldsLds8));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_glds<4, 1>, kGldsLds4));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_glds<8, 3>, kGldsLds8));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv_glds<4, 3>, kGldsLds4));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_glds<80>, SD_G3_LDS(80)));
-        HIPCHK(sd_raise_lds_limit((const void*)k_conv3x3_glds<160>, SD_G3_LDS(160)));
-    }
+    for (int k = y->f32 ? SD_YK_F32_FIRST : 0; k < (y->f32 ? SD_YK_COUNT : SD_YK_F32_FIRST); k++)
+        HIPCHK(sd_raise_lds_limit(kYoloKernelFn[k], yolo_kernel_lds(k, k >= SD_YK_B3C_5 ? SD_B3C_MAXW : SD_B3F_MAXW)));
     HIPCHK(sd_raise_lds_limit((const void*)k_yolo_nms, SD_NMS_LDS));
     return SD_OK;
 }
@@ -83,76 +102,18 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return set_err(SD_ERR_NO_DEVICE, "no HIP device: the detector has no CPU fallback");
     std::unique_ptr<sd_yolo> y(new sd_yolo());
+    SdYoloNetPlan P;
+    const SdYoloPlanError pe = yolo_plan_net(layers, n_layers, net_w, net_h, classes, precision, P);
+    if (pe.code != SD_OK) return set_err(pe.code, pe.text);
+    (SdYoloTotals&)*y = P;
     y->L.assign(layers, layers + n_layers);
-    y->R.resize(n_layers);
+    y->R.assign(P.R.begin(), P.R.end());
     y->netW = net_w; y->netH = net_h; y->classes = classes; y->maxBatch = max_batch;
     y->f32 = precision == SD_YOLO_F32 || precision == SD_YOLO_F32W || precision == SD_YOLO_F32X3;
     y->wino = precision == SD_YOLO_F32W;
     y->b3 = precision == SD_YOLO_F32X3;
-    size_t wOffW = 0, vMax = 0, wOffB = 0;
     const size_t eb = y->f32 ? 4 : 2;                     // bytes per activation element
     memcpy(y->anchors, anchors, sizeof(y->anchors));
-    // ---- shapes
-    int H = net_h, W = net_w, C = 32;      // blob: 3 channels padded to 32
-    size_t wOff = 0, bOff = 0;
-    for (int i = 0; i < n_layers; i++) {
-        const sd_yolo_layer& l = y->L[i];
-        sd_yolo::Rt& r = y->R[i];
-        if (l.type == SD_YOLO_CONV) {
-            if ((l.size != 1 && l.size != 3) || (l.stride != 1 && l.stride != 2) || l.filters < 1) return set_err(SD_ERR_UNSUPPORTED, "convolution size/stride not supported");
-            if (i == 0 && (l.size != 3 || l.stride != 1 || l.filters > 32)) return set_err(SD_ERR_UNSUPPORTED, "first convolution must be 3x3, stride 1, <= 32 filters");
-            const int cinReal = i == 0 ? 3 : C;
-            r.cinPad = i == 0 ? 32 : C;
-            if (r.cinPad % 32) return set_err(SD_ERR_UNSUPPORTED, "input channels must be a multiple of 32");
-            const int pad = l.size / 2;
-            r.H = (H + 2 * pad - l.size) / l.stride + 1; r.W = (W + 2 * pad - l.size) / l.stride + 1; r.C = l.filters;
-            r.outC = (l.filters + 31) / 32 * 32;            // stored channel count (255 -> 256)
-            r.coutPad = (l.filters + SD_G3_BM - 1) / SD_G3_BM * SD_G3_BM;        // weight/bias rows are padded to the widest filter tile
-            r.wOff = wOff; r.bOff = bOff;
-            wOff += (size_t)r.coutPad * l.size * l.size * r.cinPad;
-            bOff += r.coutPad;
-            y->convFlops += 2.0 * r.H * r.W * (double)l.filters * l.size * l.size * cinReal;
-            // Winograd F(2x2, 3x3): 3 x 3, stride 1, >= 64 input channels (the fold runs once per cin channels) and whole 128-filter tiles
-            r.wino = y->wino && i > 0 && l.size == 3 && l.stride == 1 && r.cinPad >= 64 && (r.cinPad % 16) == 0 && l.filters >= 128 && (l.filters % 128) == 0;
-            if (r.wino) {
-                const size_t blocks = (size_t)((r.H + 1) / 2) * ((r.W + 1) / 2);
-                r.wOffW = wOffW; wOffW += (size_t)r.coutPad * 16 * r.cinPad;
-                vMax = std::max(vMax, blocks * 16 * r.cinPad);
-                y->mfmaFlops += 2.0 * blocks * 16.0 * (double)l.filters * cinReal;
-            } else if (y->b3 && i > 0 && l.filters >= 64 && (l.filters > 64 || (l.filters % 64) == 0) && (r.cinPad % 16) == 0) {
-                // three bf16 limbs per operand: the layers k_conv_f32 runs on 128-filter tiles
-                r.b3 = true;
-                r.b3flat = l.size == 3 && l.stride == 1 && r.W <= 160 && l.filters > 64;       // k_conv3x3_b3: the nine taps share one staged chunk
-                r.b3wm = (r.b3flat && r.W <= 80) || l.filters == 64 ? 1 : 2;                      // 1: k_conv3x3_b3c (64-filter tiles, weights staged per chunk too); wider maps do not fit its LDS
-                r.wOffB = wOffB; wOffB += (size_t)(r.coutPad / 128) * (l.size * l.size * (r.cinPad / 16)) * 2 * 6 * 64;      // 16-byte fragments
-                y->mfmaFlopsBf16 += 6 * 2.0 * r.H * r.W * (double)l.filters * l.size * l.size * cinReal;
-            } else y->mfmaFlops += 2.0 * r.H * r.W * (double)l.filters * l.size * l.size * cinReal;
-            y->nconv++;
-        } else if (l.type == SD_YOLO_SHORTCUT) {
-            const int f = yolo_resolve(i, l.from[0]);
-            if (f < 0 || f >= i || y->R[f].H != H || y->R[f].W != W || y->R[f].C != C) return set_err(SD_ERR_INVALID, "bad shortcut");
-            r.H = H; r.W = W; r.C = C; r.outC = C;
-        } else if (l.type == SD_YOLO_ROUTE) {
-            const int f0 = yolo_resolve(i, l.from[0]);
-            if (f0 < 0 || f0 >= i) return set_err(SD_ERR_INVALID, "bad route");
-            r.H = y->R[f0].H; r.W = y->R[f0].W; r.C = y->R[f0].C;
-            if (l.nfrom == 2) {
-                const int f1 = yolo_resolve(i, l.from[1]);
-                if (f1 < 0 || f1 >= i || y->R[f1].H != r.H || y->R[f1].W != r.W) return set_err(SD_ERR_INVALID, "bad route");
-                r.C += y->R[f1].C;
-            }
-            r.outC = r.C;
-        } else if (l.type == SD_YOLO_UPSAMPLE) {
-            r.H = 2 * H; r.W = 2 * W; r.C = C; r.outC = C;
-        } else if (l.type == SD_YOLO_YOLO) {
-            if (C != 3 * (5 + classes)) return set_err(SD_ERR_INVALID, "[yolo] input must have 3*(5+classes) channels");
-            r.H = H; r.W = W; r.C = C; r.outC = C;
-            y->totalRows += H * W * 3;
-        } else return set_err(SD_ERR_INVALID, "unknown layer type");
-        H = r.H; W = r.W; C = r.C;
-        if ((l.type == SD_YOLO_CONV) && (r.C % 4) && r.C != 3 * (5 + classes)) return set_err(SD_ERR_UNSUPPORTED, "filters must be a multiple of 4");
-    }
-    y->wTotal = wOff; y->bTotal = bOff; y->wTotalW = wOffW; y->wTotalB = wOffB;
     y->detCap = 8192;
     // ---- device memory
     bool ok = true;
@@ -164,13 +125,13 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
     if (ok) ok = hipMemset(y->d_zero, 0, 256) == hipSuccess;
 
     if (!y->f32) {
-        alloc(y->d_wgt, wOff * 2 + 64);                             // f16 weights: the f16 mode only
+        alloc(y->d_wgt, y->wTotal * 2 + 64);                        // f16 weights: the f16 mode only
     } else {
-        alloc(y->d_wgt32, wOff * 4 + 64);
-        if (y->wino && wOffW) { alloc(y->d_wgtW, wOffW * 4 + 64); alloc(y->d_V, nB * vMax * 4 + 64); }
-        if (y->b3 && wOffB) alloc(y->d_wgtB, wOffB * 16 + 65536);  // slack: the kernels request weight fragments up to two steps past a tile's last
+        alloc(y->d_wgt32, y->wTotal * 4 + 64);
+        if (y->wTotalW) { alloc(y->d_wgtW, y->wTotalW * 4 + 64); alloc(y->d_V, nB * y->vMax * 4 + 64); }
+        if (y->wTotalB) alloc(y->d_wgtB, y->wTotalB * 16 + 65536);  // slack: the kernels request weight fragments up to two steps past a tile's last
     }
-    alloc(y->d_bias, bOff * 4 + 64);
+    alloc(y->d_bias, y->bTotal * 4 + 64);
     alloc(y->d_dets, nB * y->detCap * sizeof(SdDet));
     alloc(y->d_ndet, nB * 4);
     alloc(y->d_raw, (size_t)y->totalRows * (5 + classes) * 4 + 64);
@@ -225,9 +186,9 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
             if (j != i && y->L[j].type == SD_YOLO_ROUTE)
                 for (int k = 0; k < y->L[j].nfrom; k++) if (yolo_resolve(j, y->L[j].from[k]) == fb) soleRoute = false;
         if (!soleRoute) continue;
-        float* at = (float*)y->R[i].out + y->R[src].C;
-        y->R[conv].out = (_Float16*)at; y->R[conv].outC = y->R[i].C;
-        rb.out = (_Float16*)at; rb.outC = y->R[i].C;
+        float* at = y->R[i].as<float>() + y->R[src].C;
+        y->R[conv].out = at; y->R[conv].outC = y->R[i].C;
+        rb.out = at; rb.outC = y->R[i].C;
         y->R[i].alias = true;                              // marks the route: its second input is already in place
     }
     if (ok) ok = hipStreamCreateWithFlags(&y->stream, hipStreamNonBlocking) == hipSuccess;
@@ -266,14 +227,11 @@ int sd_yolo_weight_count(const sd_yolo* y, size_t* n_floats)
 {
     if (!y || !n_floats) return SD_ERR_INVALID;
     size_t n = 0;
-    int C = 3;
     for (size_t i = 0; i < y->L.size(); i++) {
         const sd_yolo_layer& l = y->L[i];
-        if (l.type == SD_YOLO_CONV) {
-            const int cin = i == 0 ? 3 : (int)y->R[i].cinPad;
-            n += (size_t)l.filters * (l.batch_normalize ? 4 : 1) + (size_t)l.filters * cin * l.size * l.size;
-        }
-        (void)C;
+        if (l.type != SD_YOLO_CONV) continue;
+        const int cin = i == 0 ? 3 : y->R[i].cinPad;
+        n += (size_t)l.filters * (l.batch_normalize ? 4 : 1) + (size_t)l.filters * cin * l.size * l.size;
     }
     *n_floats = n;
     return SD_OK;
@@ -319,7 +277,7 @@ int sd_yolo_load_darknet_weights(sd_yolo* y, const float* p, size_t n_floats)
             std::vector<float> wW(y->wTotalW, 0.f);
             for (size_t i = 0; i < y->L.size(); i++) {
                 const sd_yolo::Rt& r = y->R[i];
-                if (y->L[i].type != SD_YOLO_CONV || !r.wino) continue;
+                if (r.cls != SD_YC_WINO) continue;
                 const int cin = r.cinPad, F = y->L[i].filters;
                 for (int f = 0; f < F; f++)
                     for (int c = 0; c < cin; c++) {
@@ -352,9 +310,11 @@ int sd_yolo_load_darknet_weights(sd_yolo* y, const float* p, size_t n_floats)
             std::vector<uint16_t> wB(y->wTotalB * 8, 0);
             for (size_t i = 0; i < y->L.size(); i++) {
                 const sd_yolo::Rt& r = y->R[i];
-                if (y->L[i].type != SD_YOLO_CONV || !r.b3) continue;
+                if (!yolo_class_b3(r.cls)) continue;
                 const int cin = r.cinPad, taps = y->L[i].size * y->L[i].size, F = y->L[i].filters;
                 const size_t ksteps = (size_t)taps * (cin / 16);
+                const bool flat = yolo_class_b3_flat(r.cls);
+                const int wm = yolo_class_b3_wm(r.cls);
                 for (int f = 0; f < F; f++)
                     for (int t = 0; t < taps; t++)
                         for (int c = 0; c < cin; c++) {
@@ -362,9 +322,9 @@ int sd_yolo_load_darknet_weights(sd_yolo* y, const float* p, size_t n_floats)
                             const uint16_t hi = bf16_rne(v); const float r1 = v - bf16_val(hi);
                             const uint16_t mid = bf16_rne(r1); const float r2 = r1 - bf16_val(mid);
                             const uint16_t lo = bf16_rne(r2);
-                            const size_t ks = r.b3flat ? (size_t)(c / 16) * 9 + t : (size_t)t * (cin / 16) + c / 16;      // k_conv3x3_b3 walks [chunk][tap]
-                            const int k = c % 16, lane = f % 32 + 32 * (k / 8), bm = 64 * r.b3wm, wmr = (f % bm) / 64, m = (f % 64) / 32;
-                            const size_t frag0 = (((size_t)(f / bm) * ksteps + ks) * r.b3wm + wmr) * 6;
+                            const size_t ks = flat ? (size_t)(c / 16) * 9 + t : (size_t)t * (cin / 16) + c / 16;      // k_conv3x3_b3 walks [chunk][tap]
+                            const int k = c % 16, lane = f % 32 + 32 * (k / 8), bm = 64 * wm, wmr = (f % bm) / 64, m = (f % 64) / 32;
+                            const size_t frag0 = (((size_t)(f / bm) * ksteps + ks) * wm + wmr) * 6;
                             const uint16_t limb[3] = {hi, mid, lo};
                             for (int l = 0; l < 3; l++) wB[((r.wOffB + (frag0 + 2 * l + m) * 64 + lane) * 8) + k % 8] = limb[l];
                         }
@@ -433,7 +393,7 @@ int sd_yolo_winograd_layers(const sd_yolo* y, int* n_layers)
 {
     if (!y || !n_layers) return SD_ERR_INVALID;
     int n = 0;
-    for (const sd_yolo::Rt& r : y->R) n += r.wino ? 1 : 0;
+    for (const sd_yolo::Rt& r : y->R) n += r.cls == SD_YC_WINO;
     *n_layers = n;
     return SD_OK;
 }
@@ -445,161 +405,8 @@ int sd_yolo_mfma_flops(const sd_yolo* y, double* flops_per_image)
     return SD_OK;
 }
 
-// The forward pass in f32 (k_yolo32.h): same graph walk, one generic convolution kernel, f32 activations.
-// filter tiles walked back to back on a pixel tile (k_conv_f32's workgroup order): the largest power of two that divides tilesY and
-// keeps the group's weights (bm filters x kdim floats per tile) within 2.5 MB of an XCD's 4 MB L2
-static int f32_group_y(int tilesY, int bm, int kdim)
-{
-    int g = 1;
-    while (2 * g <= tilesY && tilesY % (2 * g) == 0 && (size_t)(2 * g) * bm * kdim * 4 <= (size_t)2560 * 1024) g *= 2;
-    return g;
-}
-
-static int yolo_forward_f32(sd_yolo* y, const uint8_t* d_bgr, int width, int height, size_t stride, size_t image_pitch, int n,
-                            float conf_threshold, hipStream_t s)
-{
-    const bool ov = y->overlap;
-    hipStream_t sb = ov ? y->sPre : s, sd = ov ? y->sPost : s;          // blobFromImage / region decodes
-    if (ov && y->haveL0) HIPCHK(hipStreamWaitEvent(sb, y->evL0, 0));    // the previous pass's first convolution has read the blob
-    {
-        dim3 blk(64, 4), grd((y->netW + 63) / 64, (y->netH + 3) / 4, n);
-        hipLaunchKernelGGL(k_blob_from_image_f32, grd, blk, 0, sb, d_bgr, width, height, stride, image_pitch, y->d_ct, y->d_rt, y->d_blob8, y->netW, y->netH, 1);
-    }
-    LAUNCH_CHECK("k_blob_from_image_f32");
-    if (ov) {
-        HIPCHK(hipEventRecord(y->evBlob, sb));
-        HIPCHK(hipStreamWaitEvent(s, y->evBlob, 0));
-    }
-    int head = 0;
-    bool headGuard = ov && y->haveDecoded;              // before the first head tensor is overwritten: the previous pass's decodes have read them
-    // tile variant of the >= 128-filter layers: 3 (default) = 128 x 128 tiles on 4-wave workgroups with 16-channel K steps, 40 KB of LDS and 144
-    // VGPRs: THREE independent workgroups per CU (3 waves per SIMD keep the MFMA pipe fed through each other's barriers and staging;
-    // +3.3 % over variant 1 on every such layer at batch 128; four per CU -- 8-channel steps, 128 VGPRs without fragment prefetch, or 64 x 128 tiles --
-    // were 5-7 % slower); 1 = the same tile with 32-channel steps, two workgroups per CU; 0 = 8-wave 128 x 256 tiles; 2 = variant 1 for the
-    // 1x1 layers only.  SD_F32_VARIANT is a developer switch.
-    static const int variant = getenv("SD_F32_VARIANT") ? atoi(getenv("SD_F32_VARIANT")) : 3;
-    static const int small4 = getenv("SD_F32_SMALL4") ? atoi(getenv("SD_F32_SMALL4")) : 1;       // 4-wave tiles for the <= 64-filter layers too (0.5 % at batch 128); developer switch
-    const float* cur = y->d_blob8;
-    int H = y->netH, W = y->netW, Cs = 4;
-    int rowBase = 0;
-    for (size_t i = 0; i < y->L.size(); i++) {
-        const sd_yolo_layer& l = y->L[i];
-        const sd_yolo::Rt& r = y->R[i];
-        if (l.type == SD_YOLO_CONV && r.wino) {
-            // Winograd F(2x2, 3x3), k_yolo32w.h: input transform into the scratch V, then one GEMM over K = 16 cin with the output transform folded in
-            SdWinoArgs A;
-            A.V = y->d_V; A.U = y->d_wgtW + r.wOffW; A.bias = y->d_bias + r.bOff; A.res = nullptr; A.out = (float*)r.out; A.zero = (const float*)y->d_zero.get();
-            A.N = n; A.H = r.H; A.W = r.W; A.th = (r.H + 1) / 2; A.tw = (r.W + 1) / 2;
-            A.cin = r.cinPad; A.cout = l.filters; A.outStride = r.outC; A.resStride = 0; A.leaky = l.leaky;
-            if (i + 1 < y->L.size() && y->L[i + 1].type == SD_YOLO_SHORTCUT && y->R[i + 1].alias) {
-                const int f = yolo_resolve((int)i + 1, y->L[i + 1].from[0]);
-                A.res = (const float*)y->R[f].out; A.resStride = y->R[f].outC;
-            }
-            const size_t nblk = (size_t)n * A.th * A.tw, work = nblk * (r.cinPad / 4);
-            hipLaunchKernelGGL(k_wino_input, dim3((unsigned)std::min<size_t>((work + 255) / 256, 65536)), dim3(256), 0, s, cur, n, H, W, r.cinPad, Cs, A.th, A.tw, y->d_V);
-            LAUNCH_CHECK("k_wino_input");
-            // 128 filters x 64 blocks per workgroup.  Measured on one box against the direct f32 mode's 126.4 ms per 128-image batch: this tile
-            // 90.9 ms; 64 x 64 tiles (a wave owns 32 x 32, 126 VGPRs, three workgroups per CU) 93.8 ms with 16-channel steps, 92.4 ms with 32.
-            // All filter tiles back to back on a block tile: V is the big operand here (4 x the layer's input; a block tile's 16 cin x 64 floats stay in L2
-            // while the filter tiles pass, the weights come from the Infinity Cache) -- with k_conv_f32's rule (a group's weights <= 2.5 MB) the 512-channel
-            // layers re-read V eight times: 89.1 / 88.1 ms per 128-image batch against 86.1 on the same box.
-            A.tilesX = (int)((nblk + 63) / 64); A.tilesY = r.coutPad / 128; A.groupY = A.tilesY;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wino_gemm_f32<16, 2>), dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(256), SD_WINO_LDS(16, 2), s, A);
-            LAUNCH_CHECK("k_wino_gemm_f32");
-        } else if (l.type == SD_YOLO_CONV) {
-            if (headGuard && i + 1 < y->L.size() && y->L[i + 1].type == SD_YOLO_YOLO) { HIPCHK(hipStreamWaitEvent(s, y->evDecoded, 0)); headGuard = false; }
-            SdConvArgsF A;
-            A.in = cur; A.wgt = y->d_wgt32 + r.wOff; A.bias = y->d_bias + r.bOff; A.res = nullptr; A.out = (float*)r.out; A.zero = (const float*)y->d_zero.get();
-            A.N = n; A.H = H; A.W = W; A.cin = i == 0 ? 8 : r.cinPad; A.cinStride = Cs; A.pair = i == 0 ? 1 : 0;
-            A.Ho = r.H; A.Wo = r.W; A.cout = l.filters; A.outStride = r.outC; A.resStride = 0;
-            A.ksize = l.size; A.stride = l.stride; A.pad = l.size / 2; A.leaky = l.leaky;
-            if (i + 1 < y->L.size() && y->L[i + 1].type == SD_YOLO_SHORTCUT && y->R[i + 1].alias) {
-                const int f = yolo_resolve((int)i + 1, y->L[i + 1].from[0]);
-                A.res = (const float*)y->R[f].out; A.resStride = y->R[f].outC;
-            }
-            const int npix = n * r.H * r.W;
-            if (r.b3) {
-                A.tilesX = (npix + 127) / 128; A.tilesY = r.coutPad / 128; A.groupY = f32_group_y(A.tilesY, 128, A.cin * l.size * l.size * 3 / 2);
-                if (r.b3flat && r.b3wm == 1) {
-                    const uint4* wq = (const uint4*)(y->d_wgtB + r.wOffB);
-                    A.tilesX = (npix + 511) / 512; A.tilesY = r.coutPad / 64; A.groupY = f32_group_y(A.tilesY, 64, A.cin * 9 * 3 / 2);
-                    const int np = (4 * (512 + 2 * W + 2) + 511) / 512;
-                    const dim3 grd(8 * (unsigned)std::min(((A.tilesX + 7) / 8) * A.tilesY, 32));      // persistent: one workgroup per CU, 32 per XCD
-                    if (np <= 5) hipLaunchKernelGGL(k_conv3x3_b3c<5>, grd, dim3(512), SD_B3C_LDS(W), s, A, wq);
-                    else hipLaunchKernelGGL(k_conv3x3_b3c<6>, grd, dim3(512), SD_B3C_LDS(W), s, A, wq);
-                } else if (r.b3flat) {
-                    const uint4* wq = (const uint4*)(y->d_wgtB + r.wOffB);
-                    const int np = (4 * (128 + 2 * W + 2) + 255) / 256;
-                    const size_t lds = SD_B3F_LDS(W, 128);
-                    const dim3 grd(SD_F32_GRID(A.tilesX, A.tilesY));
-                    if (np <= 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3x3_b3<3, 2, 2>), grd, dim3(256), lds, s, A, wq);
-                    else if (np == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3x3_b3<4, 2, 2>), grd, dim3(256), lds, s, A, wq);
-                    else if (np == 5) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3x3_b3<5, 2, 2>), grd, dim3(256), lds, s, A, wq);
-                    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3x3_b3<8, 2, 2>), grd, dim3(256), lds, s, A, wq);
-                } else if (r.b3wm == 1) {              // the 64-filter layers
-                    A.tilesX = (npix + 255) / 256; A.tilesY = 1; A.groupY = 1;
-                    hipLaunchKernelGGL(k_conv_b3<1>, dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(256), SD_B3_LDS(1), s, A, (const uint4*)(y->d_wgtB + r.wOffB));
-                } else
-                hipLaunchKernelGGL(k_conv_b3<2>, dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(256), SD_B3_LDS(2), s, A, (const uint4*)(y->d_wgtB + r.wOffB));
-            } else if (i == 0)                         // 3 (-> 8) input channels, <= 32 filters (round 4: the same tile on 4 waves, two workgroups per CU: 118.4 vs 118.3 ms per 128-image pass, no change)
-                { A.tilesX = (npix + 511) / 512; A.tilesY = (l.filters + 31) / 32; A.groupY = f32_group_y(A.tilesY, 32, A.cin * l.size * l.size); hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_f32<8, 1, 1, 8>), dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(512), SD_F32_LDS(8, 1, 1, 8), s, A); }
-            else if (l.filters <= 32 && small4)
-                { A.tilesX = (npix + 255) / 256; A.tilesY = 1; A.groupY = f32_group_y(A.tilesY, 32, A.cin * l.size * l.size); hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_f32<16, 1, 1, 4>), dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(256), SD_F32_LDS(16, 1, 1, 4), s, A); }
-            else if (l.filters <= 32)
-                { A.tilesX = (npix + 511) / 512; A.tilesY = 1; A.groupY = f32_group_y(A.tilesY, 32, A.cin * l.size * l.size); hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_f32<16, 1, 1, 8>), dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(512), SD_F32_LDS(16, 1, 1, 8), s, A); }
-            else if (l.filters <= 64 && small4)
-                { A.tilesX = (npix + 255) / 256; A.tilesY = 1; A.groupY = f32_group_y(A.tilesY, 64, A.cin * l.size * l.size); hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_f32<16, 1, 2, 4>), dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(256), SD_F32_LDS(16, 1, 2, 4), s, A); }
-            else if (l.filters <= 64)
-                { A.tilesX = (npix + 511) / 512; A.tilesY = 1; A.groupY = f32_group_y(A.tilesY, 64, A.cin * l.size * l.size); hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_f32<16, 1, 2, 8>), dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(512), SD_F32_LDS(16, 1, 2, 8), s, A); }
-            else if (variant == 3)
-                { A.tilesX = (npix + 127) / 128; A.tilesY = r.coutPad / 128; A.groupY = f32_group_y(A.tilesY, 128, A.cin * l.size * l.size); hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_f32<16, 2, 2, 4>), dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(256), SD_F32_LDS(16, 2, 2, 4), s, A); }
-            else if (variant == 1 || (variant == 2 && l.size == 1))
-                { A.tilesX = (npix + 127) / 128; A.tilesY = r.coutPad / 128; A.groupY = f32_group_y(A.tilesY, 128, A.cin * l.size * l.size); hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_f32<32, 2, 2, 4>), dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(256), SD_F32_LDS(32, 2, 2, 4), s, A); }
-            else
-                { A.tilesX = (npix + 255) / 256; A.tilesY = r.coutPad / 128; A.groupY = f32_group_y(A.tilesY, 128, A.cin * l.size * l.size); hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_f32<32, 2, 2, 8>), dim3(SD_F32_GRID(A.tilesX, A.tilesY)), dim3(512), SD_F32_LDS(32, 2, 2, 8), s, A); }
-            LAUNCH_CHECK("k_conv_f32");
-        } else if (l.type == SD_YOLO_SHORTCUT) {
-            if (!r.alias) return set_err(SD_ERR_UNSUPPORTED, "unfused [shortcut] is not implemented");
-        } else if (l.type == SD_YOLO_ROUTE && l.nfrom == 2) {
-            const int fa = yolo_resolve((int)i, l.from[0]), fb = yolo_resolve((int)i, l.from[1]);
-            const int src = yolo_resolve(fa, -1);
-            const sd_yolo::Rt& ra = y->R[src]; const sd_yolo::Rt& rb = y->R[fb];
-            if (r.alias) {                             // the skip tensor was written in place by its producer: only the up-sampled half moves
-                const size_t quads = (size_t)n * r.H * r.W * (ra.C / 4);
-                hipLaunchKernelGGL(k_upsample_into_f32, dim3((unsigned)std::min<size_t>((quads + 255) / 256, 4096)), dim3(256), 0, s, (const float*)ra.out, ra.C, ra.outC, ra.H, ra.W,
-                                   (float*)r.out, r.C, n);
-                LAUNCH_CHECK("k_upsample_into_f32");
-            } else {
-                if (ra.outC != ra.C || rb.outC != rb.C || (ra.C % 4) || (rb.C % 4)) return set_err(SD_ERR_UNSUPPORTED, "route inputs must be dense, channels % 4 == 0");
-                // the copy kernel moves 16-byte pieces: an f32 channel counts as two halfs
-                hipLaunchKernelGGL(k_upsample_concat, dim3(2048), dim3(256), 0, s, ra.out, 2 * ra.C, ra.H, ra.W, rb.out, 2 * rb.C, r.out, n);
-                LAUNCH_CHECK("k_upsample_concat");
-            }
-        } else if (l.type == SD_YOLO_YOLO) {
-            const float* an = y->anchors;
-            const int rows = n * r.H * r.W * 3;
-            if (ov && head < 3) {
-                HIPCHK(hipEventRecord(y->evHead[head], s));
-                HIPCHK(hipStreamWaitEvent(sd, y->evHead[head], 0));
-                if (head == 0 && y->haveNms) HIPCHK(hipStreamWaitEvent(sd, y->evNms, 0));     // the previous pass's NMS has read the row lists
-            }
-            if (head == 0) HIPCHK(hipMemsetAsync(y->d_ndet, 0, (size_t)n * 4, sd));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_region_decode<float>), dim3((rows + 255) / 256), dim3(256), 0, sd, (const float*)r.out, r.outC, r.H, r.W, n, an[2 * l.mask[0]],
-                               an[2 * l.mask[0] + 1], an[2 * l.mask[1]], an[2 * l.mask[1] + 1], an[2 * l.mask[2]], an[2 * l.mask[2] + 1],
-                               y->netW, y->netH, conf_threshold, rowBase, y->d_dets, y->d_ndet, y->detCap, n == 1 ? y->d_raw : nullptr);
-            LAUNCH_CHECK("k_region_decode");
-            rowBase += r.H * r.W * 3;
-            head++;
-        }
-        if (ov && i == 0) { HIPCHK(hipEventRecord(y->evL0, s)); y->haveL0 = true; }
-        if (l.type != SD_YOLO_YOLO && l.type != SD_YOLO_UPSAMPLE) { cur = (const float*)r.out; H = r.H; W = r.W; Cs = r.outC; }
-        if (l.type == SD_YOLO_YOLO) { cur = (const float*)r.out; }
-    }
-    if (head == 0) HIPCHK(hipMemsetAsync(y->d_ndet, 0, (size_t)n * 4, sd));          // a network without a [yolo] layer yields no rows
-    if (ov) { HIPCHK(hipEventRecord(y->evDecoded, sd)); y->haveDecoded = true; }
-    return SD_OK;
-}
-
+// The forward pass: one walk over the layers for the four modes.  Which kernel runs a convolution, on which tiles and grid, is yolo_plan_launch's
+// decision (sd_yolo_plan.h); here its argument struct is filled and the table row launched.
 int sd_yolo_forward_device(sd_yolo* y, const uint8_t* d_bgr, int width, int height, size_t stride, size_t image_pitch, int n,
                            float conf_threshold, void* stream_)
 {
@@ -613,85 +420,119 @@ int sd_yolo_forward_device(sd_yolo* y, const uint8_t* d_bgr, int width, int heig
         HIPCHK(hipMemcpy(y->d_rt, rt.data(), rt.size() * 2, hipMemcpyHostToDevice));
         y->tabW = width; y->tabH = height;
     }
-    if (y->f32) {
-        int rc = yolo_forward_f32(y, d_bgr, width, height, stride, image_pitch, n, conf_threshold, s);
-        if (rc != SD_OK) return rc;
-        y->lastN = n;
-        if (!stream_) { HIPCHK(hipStreamSynchronize(s)); if (y->overlap) HIPCHK(hipStreamSynchronize(y->sPost)); }
-        return SD_OK;
-    }
+    const bool f32 = y->f32, ov = y->overlap;                           // overlap mode: f32-class modes only (sd_yolo_set_overlap)
+    hipStream_t sb = ov ? y->sPre : s, sd = ov ? y->sPost : s;          // blobFromImage / region decodes
+    if (ov && y->haveL0) HIPCHK(hipStreamWaitEvent(sb, y->evL0, 0));    // the previous pass's first convolution has read the blob
     {
         dim3 blk(64, 4), grd((y->netW + 63) / 64, (y->netH + 3) / 4, n);
-        hipLaunchKernelGGL(k_blob_from_image, grd, blk, 0, s, d_bgr, width, height, stride, image_pitch, y->d_ct, y->d_rt, y->d_blob4,
-                           y->netW, y->netH, 1);
+        if (f32) hipLaunchKernelGGL(k_blob_from_image_f32, grd, blk, 0, sb, d_bgr, width, height, stride, image_pitch, y->d_ct, y->d_rt, y->d_blob8, y->netW, y->netH, 1);
+        else hipLaunchKernelGGL(k_blob_from_image, grd, blk, 0, sb, d_bgr, width, height, stride, image_pitch, y->d_ct, y->d_rt, y->d_blob4, y->netW, y->netH, 1);
     }
-    LAUNCH_CHECK("k_blob_from_image");
-    HIPCHK(hipMemsetAsync(y->d_ndet, 0, (size_t)n * 4, s));
-    const _Float16* cur = y->d_blob4;
-    int H = y->netH, W = y->netW, Cs = 32;
+    LAUNCH_CHECK(f32 ? "k_blob_from_image_f32" : "k_blob_from_image");
+    if (ov) {
+        HIPCHK(hipEventRecord(y->evBlob, sb));
+        HIPCHK(hipStreamWaitEvent(s, y->evBlob, 0));
+    }
+    // the row counts are cleared ahead of the pass in the f16 mode, ahead of the first decode in the f32-class modes (overlap mode: once the
+    // previous pass's NMS has read the row lists)
+    bool cleared = !f32;
+    if (cleared) HIPCHK(hipMemsetAsync(y->d_ndet, 0, (size_t)n * 4, s));
+    int head = 0;
+    bool headGuard = ov && y->haveDecoded;              // before the first head tensor is overwritten: the previous pass's decodes have read them
+    const void* cur = f32 ? (const void*)y->d_blob8.get() : (const void*)y->d_blob4.get();
+    int H = y->netH, W = y->netW, Cs = f32 ? 4 : 32;
     int rowBase = 0;
     for (size_t i = 0; i < y->L.size(); i++) {
         const sd_yolo_layer& l = y->L[i];
         const sd_yolo::Rt& r = y->R[i];
-        if (l.type == SD_YOLO_CONV && i == 0) {
-            const size_t npix0 = (size_t)n * r.H * r.W;
-            hipLaunchKernelGGL(k_conv_first, dim3((unsigned)((npix0 + 255) / 256)), dim3(256), 0, s, y->d_blob4, y->d_wgt + r.wOff,
-                               y->d_bias + r.bOff, r.out, n, r.H, r.W, l.filters, r.outC, l.leaky);
-            LAUNCH_CHECK("k_conv_first");
-        } else if (l.type == SD_YOLO_CONV) {
-            SdConvArgs A;
-            A.zero = y->d_zero; A.in = cur; A.wgt = y->d_wgt + r.wOff; A.bias = y->d_bias + r.bOff; A.res = nullptr; A.out = r.out;
-            A.N = n; A.H = H; A.W = W; A.cin = r.cinPad; A.cinStride = Cs;
-            A.Ho = r.H; A.Wo = r.W; A.cout = l.filters; A.coutPad = r.coutPad; A.outStride = r.outC; A.outOff = 0; A.resStride = 0;
-            A.ksize = l.size; A.stride = l.stride; A.pad = l.size / 2; A.leaky = l.leaky;
+        if (l.type == SD_YOLO_CONV) {
+            if (headGuard && i + 1 < y->L.size() && y->L[i + 1].type == SD_YOLO_YOLO) { HIPCHK(hipStreamWaitEvent(s, y->evDecoded, 0)); headGuard = false; }
+            const SdYoloLaunch K = yolo_plan_launch(l, r, i == 0, n);
+            const void* bias = y->d_bias + r.bOff;
+            const void* res = nullptr; int resStride = 0;          // the residual of a shortcut fused into this convolution's epilogue
             if (i + 1 < y->L.size() && y->L[i + 1].type == SD_YOLO_SHORTCUT && y->R[i + 1].alias) {
-                const int f = yolo_resolve((int)i + 1, y->L[i + 1].from[0]);
-                A.res = y->R[f].out; A.resStride = y->R[f].outC;
+                const sd_yolo::Rt& rf = y->R[yolo_resolve((int)i + 1, y->L[i + 1].from[0])];
+                res = rf.out; resStride = rf.outC;
             }
-            const int npix = n * r.H * r.W;
-            dim3 grd((npix + SD_CV_BN - 1) / SD_CV_BN, (l.filters + SD_CV_BM - 1) / SD_CV_BM);
-            const bool flat3 = l.size == 3 && l.stride == 1 && W <= 160 && l.filters % SD_G3_BM == 0 && r.cinPad % 32 == 0 && npix >= SD_G3_BN;
-            if (!flat3 && r.cinPad % 32 == 0 && npix >= 512 && (l.size == 1 || l.filters >= SD_G3_BM / 2)) {
-                const int ct = r.coutPad / SD_G3_BM;
-                const bool big = ((npix + 511) / 512) * ct >= 256;
-                const dim3 g8((npix + 511) / 512, ct), g4((npix + 255) / 256, ct);
-                if (l.size == 1 && big) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<8, 1>), g8, dim3(512), kGldsLds8, s, A);
-                else if (l.size == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<4, 1>), g4, dim3(256), kGldsLds4, s, A);
-                else if (big) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<8, 3>), g8, dim3(512), kGldsLds8, s, A);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_glds<4, 3>), g4, dim3(256), kGldsLds4, s, A);
-            } else if (flat3) {
-                const dim3 g3((npix + SD_G3_BN - 1) / SD_G3_BN, l.filters / SD_G3_BM);
-                if (W <= 80) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3x3_glds<80>), g3, dim3(512), SD_G3_LDS(80), s, A);
-                else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv3x3_glds<160>), g3, dim3(512), SD_G3_LDS(160), s, A);
-            } else if (l.size == 3 && l.stride == 1 && W <= SD_C3_MAXW && l.filters % SD_C3_BM == 0 && r.cinPad % SD_C3_BK == 0)
-                hipLaunchKernelGGL(k_conv3x3_flat, dim3((npix + SD_C3_BN - 1) / SD_C3_BN, l.filters / SD_C3_BM), dim3(256), 0, s, A);
-            else if (r.cinPad % 64 == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_mfma<64>), grd, dim3(256), 0, s, A);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_conv_mfma<32>), grd, dim3(256), 0, s, A);
-            LAUNCH_CHECK("k_conv_mfma");
+            int rc;
+            if (K.kernel == SD_YK_CONV_FIRST) {
+                const _Float16* blob = y->d_blob4; const _Float16* wgt = y->d_wgt + r.wOff; _Float16* out = r.as<_Float16>();
+                int Ho = r.H, Wo = r.W, cout = l.filters, outStride = r.outC, leaky = l.leaky;
+                void* args[] = {&blob, &wgt, &bias, &out, &n, &Ho, &Wo, &cout, &outStride, &leaky};
+                rc = yolo_launch(K, args, s);
+            } else if (r.cls == SD_YC_F16) {
+                SdConvArgs A;
+                A.zero = y->d_zero; A.in = (const _Float16*)cur; A.wgt = y->d_wgt + r.wOff; A.bias = (const float*)bias; A.res = (const _Float16*)res; A.out = r.as<_Float16>();
+                A.N = n; A.H = H; A.W = W; A.cin = r.cinPad; A.cinStride = Cs;
+                A.Ho = r.H; A.Wo = r.W; A.cout = l.filters; A.coutPad = r.coutPad; A.outStride = r.outC; A.outOff = 0; A.resStride = resStride;
+                A.ksize = l.size; A.stride = l.stride; A.pad = l.size / 2; A.leaky = l.leaky;
+                void* args[] = {&A};
+                rc = yolo_launch(K, args, s);
+            } else if (r.cls == SD_YC_WINO) {
+                // Winograd F(2x2, 3x3), k_yolo32w.h: input transform into the scratch V, then one GEMM over K = 16 cin with the output transform folded in
+                SdWinoArgs A;
+                A.V = y->d_V; A.U = y->d_wgtW + r.wOffW; A.bias = (const float*)bias; A.res = (const float*)res; A.out = r.as<float>(); A.zero = (const float*)y->d_zero.get();
+                A.N = n; A.H = r.H; A.W = r.W; A.th = (r.H + 1) / 2; A.tw = (r.W + 1) / 2;
+                A.cin = r.cinPad; A.cout = l.filters; A.outStride = r.outC; A.resStride = resStride; A.leaky = l.leaky;
+                A.tilesX = K.tilesX; A.tilesY = K.tilesY; A.groupY = K.groupY;
+                hipLaunchKernelGGL(k_wino_input, dim3(K.inputGrid), dim3(256), 0, s, (const float*)cur, n, H, W, r.cinPad, Cs, A.th, A.tw, y->d_V);
+                LAUNCH_CHECK("k_wino_input");
+                void* args[] = {&A};
+                rc = yolo_launch(K, args, s);
+            } else {
+                SdConvArgsF A;
+                A.in = (const float*)cur; A.wgt = y->d_wgt32 + r.wOff; A.bias = (const float*)bias; A.res = (const float*)res; A.out = r.as<float>(); A.zero = (const float*)y->d_zero.get();
+                A.N = n; A.H = H; A.W = W; A.cin = i == 0 ? 8 : r.cinPad; A.cinStride = Cs; A.pair = i == 0 ? 1 : 0;
+                A.Ho = r.H; A.Wo = r.W; A.cout = l.filters; A.outStride = r.outC; A.resStride = resStride;
+                A.ksize = l.size; A.stride = l.stride; A.pad = l.size / 2; A.leaky = l.leaky;
+                A.tilesX = K.tilesX; A.tilesY = K.tilesY; A.groupY = K.groupY;
+                const uint4* wq = y->d_wgtB + r.wOffB;                 // the limb kernels' second argument
+                void* args[] = {&A, &wq};
+                rc = yolo_launch(K, args, s);
+            }
+            if (rc != SD_OK) return rc;
         } else if (l.type == SD_YOLO_SHORTCUT) {
             if (!r.alias) return set_err(SD_ERR_UNSUPPORTED, "unfused [shortcut] is not implemented");
         } else if (l.type == SD_YOLO_ROUTE && l.nfrom == 2) {
             const int fa = yolo_resolve((int)i, l.from[0]), fb = yolo_resolve((int)i, l.from[1]);
             const int src = yolo_resolve(fa, -1);          // the layer the [upsample] reads
             const sd_yolo::Rt& ra = y->R[src]; const sd_yolo::Rt& rb = y->R[fb];
-            if (ra.outC != ra.C || rb.outC != rb.C || (ra.C % 8) || (rb.C % 8)) return set_err(SD_ERR_UNSUPPORTED, "route inputs must be dense, channels % 8 == 0");
-            hipLaunchKernelGGL(k_upsample_concat, dim3(2048), dim3(256), 0, s, ra.out, ra.C, ra.H, ra.W, rb.out, rb.C, r.out, n);
-            LAUNCH_CHECK("k_upsample_concat");
+            if (f32 && r.alias) {                          // the skip tensor was written in place by its producer: only the up-sampled half moves
+                const size_t quads = (size_t)n * r.H * r.W * (ra.C / 4);
+                hipLaunchKernelGGL(k_upsample_into_f32, dim3((unsigned)std::min<size_t>((quads + 255) / 256, 4096)), dim3(256), 0, s, ra.as<const float>(), ra.C, ra.outC, ra.H, ra.W,
+                                   r.as<float>(), r.C, n);
+                LAUNCH_CHECK("k_upsample_into_f32");
+            } else {
+                // the copy kernel moves 16-byte pieces of halfs: an f32 channel counts as two
+                const int hc = f32 ? 2 : 1, piece = 8 / hc;
+                if (ra.outC != ra.C || rb.outC != rb.C || (ra.C % piece) || (rb.C % piece))
+                    return set_err(SD_ERR_UNSUPPORTED, f32 ? "route inputs must be dense, channels % 4 == 0" : "route inputs must be dense, channels % 8 == 0");
+                hipLaunchKernelGGL(k_upsample_concat, dim3(2048), dim3(256), 0, s, ra.as<const _Float16>(), hc * ra.C, ra.H, ra.W, rb.as<const _Float16>(), hc * rb.C,
+                                   r.as<_Float16>(), n);
+                LAUNCH_CHECK("k_upsample_concat");
+            }
         } else if (l.type == SD_YOLO_YOLO) {
-            const float* an = y->anchors;
-            const int rows = n * r.H * r.W * 3;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_region_decode<_Float16>), dim3((rows + 255) / 256), dim3(256), 0, s, (const _Float16*)r.out, r.outC, r.H, r.W, n, an[2 * l.mask[0]],
-                               an[2 * l.mask[0] + 1], an[2 * l.mask[1]], an[2 * l.mask[1] + 1], an[2 * l.mask[2]], an[2 * l.mask[2] + 1],
-                               y->netW, y->netH, conf_threshold, rowBase, y->d_dets, y->d_ndet, y->detCap, n == 1 ? y->d_raw : nullptr);
+            if (ov && head < 3) {
+                HIPCHK(hipEventRecord(y->evHead[head], s));
+                HIPCHK(hipStreamWaitEvent(sd, y->evHead[head], 0));
+                if (head == 0 && y->haveNms) HIPCHK(hipStreamWaitEvent(sd, y->evNms, 0));     // the previous pass's NMS has read the row lists
+            }
+            if (!cleared) { HIPCHK(hipMemsetAsync(y->d_ndet, 0, (size_t)n * 4, sd)); cleared = true; }
+            if (f32) yolo_decode<float>(y, l, r, n, conf_threshold, rowBase, sd);
+            else yolo_decode<_Float16>(y, l, r, n, conf_threshold, rowBase, sd);
             LAUNCH_CHECK("k_region_decode");
             rowBase += r.H * r.W * 3;
+            head++;
         }
+        if (ov && i == 0) { HIPCHK(hipEventRecord(y->evL0, s)); y->haveL0 = true; }
         // the input of the next layer
         if (l.type != SD_YOLO_YOLO && l.type != SD_YOLO_UPSAMPLE) { cur = r.out; H = r.H; W = r.W; Cs = r.outC; }
         if (l.type == SD_YOLO_YOLO) { cur = r.out; }
     }
+    if (!cleared) HIPCHK(hipMemsetAsync(y->d_ndet, 0, (size_t)n * 4, sd));          // a network without a [yolo] layer yields no rows
+    if (ov) { HIPCHK(hipEventRecord(y->evDecoded, sd)); y->haveDecoded = true; }
     y->lastN = n;
-    if (!stream_) HIPCHK(hipStreamSynchronize(s));
+    if (!stream_) { HIPCHK(hipStreamSynchronize(s)); if (ov) HIPCHK(hipStreamSynchronize(y->sPost)); }
     return SD_OK;
 }
 
@@ -702,7 +543,7 @@ int sd_yolo_download_layer(sd_yolo* y, int layer, int image, uint16_t* out)
     if (!r.out) return set_err(SD_ERR_INVALID, "layer has no materialised output");
     HIPCHK(hipDeviceSynchronize());
     const size_t pix = (size_t)r.H * r.W, eb = y->f32 ? 4 : 2;       // f32 mode: `out` receives floats
-    const unsigned char* src = (const unsigned char*)r.out + (size_t)image * pix * r.outC * eb;
+    const unsigned char* src = r.as<const unsigned char>() + (size_t)image * pix * r.outC * eb;
     if (r.outC == r.C) {
         HIPCHK(hipMemcpy(out, src, pix * r.C * eb, hipMemcpyDeviceToHost));
     } else {
