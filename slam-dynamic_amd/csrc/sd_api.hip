@@ -162,6 +162,59 @@ struct sd_batch {
 #define KPUN(b) ((b)->hasDist ? (b)->d_kpUn : (b)->d_kp)
 #define KPDUN(b) ((b)->hasDist ? (b)->d_kpDUn : (b)->d_kpD)
 
+// ---- What a frame is: the per-slot arrays of a workspace, slot k of each at base + k * bytes, in ONE fixed order.  Every mover of frames
+// (sd_batch_copy_frame[s], the tracker's pool / initialisation-extractor copies, the prefetched records) takes its segments from here, so a
+// new per-slot array is added in this list and nowhere else.  The subsets are prefixes of each other:
+//   EXTRACT  what ORB extraction writes
+//   FRONT    the history-free half (+ undistortion, stereo / RGB-D association); padded to 16 bytes per segment, in this order, it is the
+//            layout of a prefetched record (sd_tracker_prefetched_record_bytes)
+//   ALL      Frame's copy constructor (Frame.cc:39-63)
+enum SdFrameSubset { SD_FRAME_EXTRACT, SD_FRAME_FRONT, SD_FRAME_ALL };
+struct SdSlotArray { const void* base; size_t bytes; SdFrameSubset subset; bool distOnly; };
+
+static int frame_arrays(const sd_batch* b, SdFrameSubset subset, SdSlotArray out[SD_COPY_SEGS])
+{
+    const size_t cap = b->plan.kpCap, kp = cap * sizeof(sd_keypoint);
+    const SdSlotArray all[] = {
+        {b->d_count, 4, SD_FRAME_EXTRACT, false}, {b->d_lvlCount, (size_t)b->plan.nlevels * 4, SD_FRAME_EXTRACT, false},
+        {b->d_kp, kp, SD_FRAME_EXTRACT, false}, {b->d_desc, cap * 32, SD_FRAME_EXTRACT, false},
+        {b->d_uright, cap * 4, SD_FRAME_FRONT, false}, {b->d_depth, cap * 4, SD_FRAME_FRONT, false}, {b->d_sad, cap * 4, SD_FRAME_FRONT, false},
+        {b->d_kpUn, kp, SD_FRAME_FRONT, true},
+        {b->d_cellOf, cap * 2, SD_FRAME_ALL, false}, {b->d_xw, cap * 12, SD_FRAME_ALL, false}, {b->d_flags, cap, SD_FRAME_ALL, false},
+        {b->d_sortedIdx, cap * 2, SD_FRAME_ALL, false}, {b->d_cellStart, (SD_GRID_CELLS + 8) * 2, SD_FRAME_ALL, false},
+        {b->d_kpD, kp, SD_FRAME_ALL, false}, {b->d_descD, cap * 32, SD_FRAME_ALL, false}, {b->d_urD, cap * 4, SD_FRAME_ALL, false},
+        {b->d_depD, cap * 4, SD_FRAME_ALL, false}, {b->d_kpDUn, kp, SD_FRAME_ALL, true},
+        {b->d_fb, sizeof(SdFrameBoxes), SD_FRAME_ALL, false}, {b->d_boxItems, (size_t)b->itemsCap * 4, SD_FRAME_ALL, false},
+    };
+    static_assert(sizeof(all) / sizeof(all[0]) <= SD_COPY_SEGS, "SdCopyTable must hold every per-slot array of a frame");
+    int n = 0;
+    for (const SdSlotArray& a : all)
+        if (a.subset <= subset && (!a.distOnly || b->hasDist)) out[n++] = a;
+    return n;
+}
+
+// `subset` of src's slots -> dst's slots: two workspaces of the same plan, or one and the same
+static SdCopyTable frame_copy_table(const sd_batch* src, const sd_batch* dst, SdFrameSubset subset)
+{
+    SdSlotArray A[SD_COPY_SEGS], B[SD_COPY_SEGS];
+    SdCopyTable T;
+    T.n = frame_arrays(src, subset, A);
+    frame_arrays(dst, subset, B);
+    for (int i = 0; i < T.n; i++) {
+        T.src[i] = (const char*)A[i].base; T.dst[i] = (char*)const_cast<void*>(B[i].base);
+        T.srcStride[i] = T.dstStride[i] = T.bytes[i] = (unsigned)A[i].bytes;
+    }
+    return T;
+}
+
+// copy z of n: slot pairs[z].x -> pairs[z].y, or without a list slot srcFirst + z * srcStep -> dstFirst + z * dstStep
+static int launch_copy_frames(const SdCopyTable& T, int blocks, int n, const int2* pairs, int srcFirst, int srcStep, int dstFirst, int dstStep, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_copy_frames, dim3(blocks, T.n, n), dim3(256), 0, s, T, pairs, srcFirst, srcStep, dstFirst, dstStep);
+    LAUNCH_CHECK("k_copy_frames");
+    return SD_OK;
+}
+
 extern "C" {
 
 int sd_version(void) { return 100; }
@@ -934,18 +987,6 @@ int sd_hamming_matrix_device(const uint8_t* d_a, int na, const uint8_t* d_b, int
 
 
 // ---------------------------------------------------------------- grid / unproject / projection matcher
-struct SdCopySegs { const char* src[24]; char* dst[24]; unsigned bytes[24]; int n; };
-__global__ void __launch_bounds__(256) k_copy_segments(SdCopySegs S)
-{
-    const int seg = blockIdx.y;
-    const unsigned n = S.bytes[seg];
-    const char* s = S.src[seg]; char* d = S.dst[seg];
-    const bool aligned = ((((size_t)s) | ((size_t)d)) & 3) == 0;
-    const unsigned words = aligned ? n >> 2 : 0;
-    for (unsigned i = blockIdx.x * 256 + threadIdx.x; i < words; i += gridDim.x * 256) ((uint32_t*)d)[i] = ((const uint32_t*)s)[i];
-    for (unsigned i = (words << 2) + blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) d[i] = s[i];
-}
-
 static int cam_ok(const sd_camera* c)
 {
     return c && c->fx > 0 && c->fy > 0 && c->mnMaxX > c->mnMinX && c->mnMaxY > c->mnMinY;
@@ -1626,35 +1667,41 @@ int sd_image_bounds(int cols, int rows, const float* K4, const float* dist5, flo
     return SD_OK;
 }
 
-// Frame copy (mLastFrame = Frame(mCurrentFrame), Tracking.cc; Frame.cc:39-63): keypoints, descriptors,
-// stereo coordinates, grid cells and the map-point table of slot `src` into slot `dst`.
+// Frame copy (mLastFrame = Frame(mCurrentFrame), Tracking.cc; Frame.cc:39-63): every per-slot array (frame_arrays) of n (src, dst) slot
+// pairs in one launch; the pairs come from `d_pairs` or, for one pair, as (src0, dst0)
+static int copy_frames_impl(sd_batch* b, int n, const int2* d_pairs, int src0, int dst0, const int32_t* dst, hipStream_t s)
+{
+    int rc = launch_copy_frames(frame_copy_table(b, b, SD_FRAME_ALL), 8, n, d_pairs, src0, 0, dst0, 0, s);
+    if (rc != SD_OK) return rc;
+    for (int i = 0; i < n; i++) {
+        b->slotValid[dst[i]] = 1;
+        if (!b->bowValid.empty()) b->bowValid[dst[i]] = 0;      // mBowVec / mFeatVec are recomputed on demand (ComputeBoW's `if(mBowVec.empty())`)
+    }
+    return SD_OK;
+}
+
 int sd_batch_copy_frame(sd_batch* b, int src, int dst, void* stream_)
 {
     if (!b || !slot_ok(b, src) || dst < 0 || dst >= b->maxImages || src == dst) return set_err(SD_ERR_INVALID, "bad copy_frame slots");
     hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
     b->lastStream = s;
-    const size_t cap = b->plan.kpCap;
-#define CP(ptr, elemBytes) do { if (nseg < 24) { segs.src[nseg] = (const char*)(ptr).get() + src * cap * (elemBytes); segs.dst[nseg] = (char*)(ptr).get() + dst * cap * (elemBytes); segs.bytes[nseg] = (unsigned)(cap * (elemBytes)); nseg++; } } while (0)
-    SdCopySegs segs;
-    int nseg = 0;
-    CP(b->d_kp, sizeof(sd_keypoint)); CP(b->d_desc, 32); CP(b->d_uright, 4); CP(b->d_depth, 4); CP(b->d_sad, 4);
-    CP(b->d_cellOf, 2); CP(b->d_xw, 12); CP(b->d_flags, 1); CP(b->d_sortedIdx, 2);
-    CP(b->d_kpD, sizeof(sd_keypoint)); CP(b->d_descD, 32); CP(b->d_urD, 4); CP(b->d_depD, 4);
-    if (b->hasDist) { CP(b->d_kpUn, sizeof(sd_keypoint)); CP(b->d_kpDUn, sizeof(sd_keypoint)); }
-#undef CP
-#define CPX(ptr, elems, elemBytes) do { if (nseg < 24) { segs.src[nseg] = (const char*)((ptr) + (size_t)src * (elems)); segs.dst[nseg] = (char*)((ptr) + (size_t)dst * (elems)); segs.bytes[nseg] = (unsigned)((elems) * (elemBytes)); nseg++; } } while (0)
-    CPX(b->d_cellStart, SD_GRID_CELLS + 8, 2);
-    CPX(b->d_count, 1, 4);
-    CPX(b->d_lvlCount, b->plan.nlevels, 4);
-    CPX(b->d_fb, 1, sizeof(SdFrameBoxes));
-    CPX(b->d_boxItems, b->itemsCap, 4);
-#undef CPX
-    segs.n = nseg;
-    hipLaunchKernelGGL(k_copy_segments, dim3(32, nseg), dim3(256), 0, s, segs);      // one launch instead of 19 small copies
-    LAUNCH_CHECK("k_copy_segments");
-    b->slotValid[dst] = 1;
-    if (!b->bowValid.empty()) b->bowValid[dst] = 0;      // mBowVec / mFeatVec are recomputed on demand (ComputeBoW's `if(mBowVec.empty())`)
-    return SD_OK;
+    return copy_frames_impl(b, 1, nullptr, src, dst, &dst, s);
+}
+
+int sd_batch_copy_frames(sd_batch* b, int n, const int32_t* src, const int32_t* dst, void* stream_)
+{
+    if (!b || n < 0 || n > b->maxImages || (n > 0 && (!src || !dst))) return set_err(SD_ERR_INVALID, "bad copy_frames arguments");
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
+    b->lastStream = s;
+    if (n == 0) return SD_OK;
+    std::vector<int2>& pr = b->hostCopyPairs;
+    pr.resize(n);
+    for (int i = 0; i < n; i++) {
+        if (!slot_ok(b, src[i]) || dst[i] < 0 || dst[i] >= b->maxImages) return set_err(SD_ERR_INVALID, "bad copy_frames slots");
+        pr[i] = make_int2(src[i], dst[i]);
+    }
+    HIPCHK(hipMemcpyAsync(b->d_copyPairs, pr.data(), (size_t)n * sizeof(int2), hipMemcpyHostToDevice, s));
+    return copy_frames_impl(b, n, b->d_copyPairs, 0, 0, dst, s);
 }
 
 int sd_batch_matches_device(sd_batch* b, int32_t** d_match, int32_t** d_pairs, int32_t** d_npairs, int32_t** d_nmatches, int* cap)

@@ -34,6 +34,9 @@ struct sd_tracker {
     std::unique_ptr<sd_extractor> exIni; std::unique_ptr<sd_batch> bIni;
     // time-batched mode (sd_tracker_prefetch): the history-free part of up to 2 x lookahead frames per lane lives in `bp`
     std::unique_ptr<sd_batch> bp[2];                                                   // one workspace per outstanding block
+    // Invariant the pool slots rely on: sd_tracker_track ends with a synchronisation (tracker_summary), so when a block's workspace is
+    // refilled -- only a later prefetch / import can do that -- every pool copy-out that read it has completed.  Prefetch and import therefore
+    // need no ordering against the copy-out; `ready` orders the other direction (fill before copy-out / export).
     struct Block { int n = 0, next = 0; hipEvent_t ready = nullptr; };                 // frames of the block, `next` consumed so far
     Block blocks[2]; int blockHead = 0, blockCount = 0;
     // caller-owned SLAM state (sd_tracker_set_state); empty = the automatic rule of the sharded batch mode
@@ -125,19 +128,14 @@ int sd_tracker_reset(sd_tracker* t)
     return SD_OK;
 }
 
-// The history-free half of a frame for `n` frames per lane in one batch (images in frame-major order: frame k, lane s, eye e): GrabImage*'s
-// conversion, ORB extraction, UndistortKeyPoints and the stereo / RGB-D association.  Slot of (k, s, e) in `b` = (k * S + s) * ipl + e.
-static int tracker_front_half(sd_tracker* t, sd_batch* b, int n, const uint8_t* d_images, size_t stride, size_t image_pitch, const void* d_depth,
-                              size_t depth_stride_elems, size_t depth_pitch_elems, hipStream_t s)
+// What follows extraction in the history-free half of F frames (left slots f * ipl of `b`): UndistortKeyPoints (the identity and free when
+// Camera.k1 == 0), then the stereo / RGB-D association or the monocular fill
+static int tracker_associate(sd_tracker* t, sd_batch* b, int F, const void* d_depth, size_t depth_stride_elems, size_t depth_pitch_elems, hipStream_t s)
 {
-    const int S = t->S, ipl = t->ipl, F = n * S;
     const sd_camera* cam = &t->p.cam;
-    int rc = sd_batch_extract_pixels_device(b, d_images, stride, image_pitch, t->p.channels, t->p.rgb_order, F * ipl, s);
-    if (rc != SD_OK) return rc;
-    // ---- UndistortKeyPoints (the identity and free when Camera.k1 == 0), then the stereo association
     std::vector<int32_t> slots(F);
-    for (int f = 0; f < F; f++) slots[f] = f * ipl;
-    rc = sd_batch_undistort(b, F, slots.data(), s);
+    for (int f = 0; f < F; f++) slots[f] = f * t->ipl;
+    int rc = sd_batch_undistort(b, F, slots.data(), s);
     if (rc != SD_OK) return rc;
     if (t->p.sensor == SD_SENSOR_STEREO) return sd_batch_stereo_match(b, F, cam->mbf, cam->fx, s);
     if (t->p.sensor == SD_SENSOR_RGBD) {
@@ -150,6 +148,17 @@ static int tracker_front_half(sd_tracker* t, sd_batch* b, int n, const uint8_t* 
     hipLaunchKernelGGL(k_fill_mono, dim3((b->plan.kpCap + 255) / 256, F), dim3(256), 0, s, b->d_count, b->d_uright, b->d_depth, b->plan.kpCap);
     LAUNCH_CHECK("k_fill_mono");
     return SD_OK;
+}
+
+// The history-free half of a frame for `n` frames per lane in one batch (images in frame-major order: frame k, lane s, eye e): GrabImage*'s
+// conversion, ORB extraction, then tracker_associate.  Slot of (k, s, e) in `b` = (k * S + s) * ipl + e.
+static int tracker_front_half(sd_tracker* t, sd_batch* b, int n, const uint8_t* d_images, size_t stride, size_t image_pitch, const void* d_depth,
+                              size_t depth_stride_elems, size_t depth_pitch_elems, hipStream_t s)
+{
+    const int F = n * t->S;
+    int rc = sd_batch_extract_pixels_device(b, d_images, stride, image_pitch, t->p.channels, t->p.rgb_order, F * t->ipl, s);
+    if (rc != SD_OK) return rc;
+    return tracker_associate(t, b, F, d_depth, depth_stride_elems, depth_pitch_elems, s);
 }
 
 int sd_tracker_prefetch(sd_tracker* t, const uint8_t* d_images, size_t stride, size_t image_pitch, const void* d_depth,
@@ -172,30 +181,32 @@ int sd_tracker_prefetch(sd_tracker* t, const uint8_t* d_images, size_t stride, s
     return SD_OK;
 }
 
-// The arrays of a pool workspace that sd_tracker_track consumes from a prefetched frame (its left slot): the record of one (frame, lane).
-static SdRecordTable record_table(const sd_tracker* t, sd_batch* bp)
-{
-    SdRecordTable T;
-    int n = 0;
-    unsigned off = 0;
-    const size_t cap = t->b->plan.kpCap;
-#define SEGR(field, bytes) do { T.base[n] = (char*)(bp ? bp->field : nullptr); T.slotBytes[n] = (unsigned)(bytes); T.offset[n] = off; \
-                                off += ((unsigned)(bytes) + 15u) & ~15u; n++; } while (0)
-    SEGR(d_count, 4); SEGR(d_lvlCount, (size_t)t->b->plan.nlevels * 4);
-    SEGR(d_kp, cap * sizeof(sd_keypoint)); SEGR(d_desc, cap * 32); SEGR(d_uright, cap * 4); SEGR(d_depth, cap * 4); SEGR(d_sad, cap * 4);
-    if (t->b->hasDist) SEGR(d_kpUn, cap * sizeof(sd_keypoint));
-#undef SEGR
-    T.n = n; T.recordBytes = off;
-    return T;
-}
+// The record of one prefetched (frame, lane): the FRONT arrays of its left pool slot back to back, each padded to 16 bytes
+static size_t record_pad(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
 
 size_t sd_tracker_prefetched_record_bytes(const sd_tracker* t)
 {
     if (!t || !t->bp[0]) return 0;
-    return record_table(t, nullptr).recordBytes;
+    SdSlotArray A[SD_COPY_SEGS];
+    size_t bytes = 0;
+    for (int i = 0, n = frame_arrays(t->bp[0].get(), SD_FRAME_FRONT, A); i < n; i++) bytes += record_pad(A[i].bytes);
+    return bytes;
 }
 
-static bool record_stride_ok(const sd_tracker* t, size_t stride) { return t->bp[0] && stride >= record_table(t, nullptr).recordBytes && (stride & 15) == 0; }
+static bool record_stride_ok(const sd_tracker* t, size_t stride) { return t->bp[0] && stride >= sd_tracker_prefetched_record_bytes(t) && (stride & 15) == 0; }
+
+// pool slots of `bp` -> records `stride` bytes apart (toRecord), or the records -> the pool slots
+static SdCopyTable record_table(const sd_batch* bp, char* records, size_t stride, bool toRecord)
+{
+    SdCopyTable T = frame_copy_table(bp, bp, SD_FRAME_FRONT);
+    size_t off = 0;
+    for (int i = 0; i < T.n; i++) {
+        if (toRecord) { T.dst[i] = records + off; T.dstStride[i] = (unsigned)stride; }
+        else { T.src[i] = records + off; T.srcStride[i] = (unsigned)stride; }
+        off += record_pad(T.bytes[i]);
+    }
+    return T;
+}
 
 int sd_tracker_export_prefetched(sd_tracker* t, int first_frame, int n_frames, void* d_records, size_t record_stride, void* stream_)
 {
@@ -208,11 +219,7 @@ int sd_tracker_export_prefetched(sd_tracker* t, int first_frame, int n_frames, v
     sd_batch* bp = t->bp[slot].get();
     hipStream_t s = stream_ ? (hipStream_t)stream_ : bp->stream;
     HIPCHK(hipStreamWaitEvent(s, B.ready, 0));
-    SdRecordTable T = record_table(t, bp);
-    T.recordBytes = (unsigned)record_stride;
-    hipLaunchKernelGGL(k_frame_records, dim3(4, T.n, n_frames * t->S), dim3(256), 0, s, T, (char*)d_records, first_frame * t->S, t->ipl, 1);
-    LAUNCH_CHECK("k_frame_records");
-    return SD_OK;
+    return launch_copy_frames(record_table(bp, (char*)d_records, record_stride, true), 4, n_frames * t->S, nullptr, first_frame * t->nCur, t->ipl, 0, 1, s);
 }
 
 int sd_tracker_import_prefetched(sd_tracker* t, const void* d_records, size_t record_stride, int n_frames, void* stream_)
@@ -226,10 +233,8 @@ int sd_tracker_import_prefetched(sd_tracker* t, const void* d_records, size_t re
     sd_tracker::Block& B = t->blocks[slot];
     sd_batch* bp = t->bp[slot].get();
     hipStream_t s = stream_ ? (hipStream_t)stream_ : bp->stream;
-    SdRecordTable T = record_table(t, bp);
-    T.recordBytes = (unsigned)record_stride;
-    hipLaunchKernelGGL(k_frame_records, dim3(4, T.n, n_frames * t->S), dim3(256), 0, s, T, (char*)const_cast<void*>(d_records), 0, t->ipl, 0);
-    LAUNCH_CHECK("k_frame_records");
+    int rc = launch_copy_frames(record_table(bp, (char*)const_cast<void*>(d_records), record_stride, false), 4, n_frames * t->S, nullptr, 0, 1, 0, t->ipl, s);
+    if (rc != SD_OK) return rc;
     B.n = n_frames; B.next = 0;
     HIPCHK(hipEventRecord(B.ready, s));
     t->blockCount++;
@@ -278,43 +283,6 @@ int sd_tracker_batch(sd_tracker* t, sd_batch** b)
 {
     if (!t || !b) return SD_ERR_INVALID;
     *b = t->b.get();
-    return SD_OK;
-}
-
-static SdCopyTable copy_table(sd_batch* b)
-{
-    SdCopyTable T;
-    int n = 0;
-    const size_t cap = b->plan.kpCap;
-#define SEG(ptr, bytes) do { T.base[n] = (char*)(ptr).get(); T.slotBytes[n] = (unsigned)(bytes); n++; } while (0)
-    SEG(b->d_kp, cap * sizeof(sd_keypoint)); SEG(b->d_desc, cap * 32); SEG(b->d_uright, cap * 4); SEG(b->d_depth, cap * 4); SEG(b->d_sad, cap * 4);
-    SEG(b->d_cellOf, cap * 2); SEG(b->d_xw, cap * 12); SEG(b->d_flags, cap); SEG(b->d_sortedIdx, cap * 2);
-    SEG(b->d_kpD, cap * sizeof(sd_keypoint)); SEG(b->d_descD, cap * 32); SEG(b->d_urD, cap * 4); SEG(b->d_depD, cap * 4);
-    SEG(b->d_cellStart, (SD_GRID_CELLS + 8) * 2); SEG(b->d_count, 4); SEG(b->d_lvlCount, (size_t)b->plan.nlevels * 4);
-    SEG(b->d_fb, sizeof(SdFrameBoxes)); SEG(b->d_boxItems, (size_t)b->itemsCap * 4);
-    if (b->hasDist) { SEG(b->d_kpUn, cap * sizeof(sd_keypoint)); SEG(b->d_kpDUn, cap * sizeof(sd_keypoint)); }
-#undef SEG
-    T.n = n;
-    return T;
-}
-
-int sd_batch_copy_frames(sd_batch* b, int n, const int32_t* src, const int32_t* dst, void* stream_)
-{
-    if (!b || n < 0 || n > b->maxImages || (n > 0 && (!src || !dst))) return set_err(SD_ERR_INVALID, "bad copy_frames arguments");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
-    if (n == 0) return SD_OK;
-    std::vector<int2>& pr = b->hostCopyPairs;
-    pr.resize(n);
-    for (int i = 0; i < n; i++) {
-        if (!slot_ok(b, src[i]) || dst[i] < 0 || dst[i] >= b->maxImages) return set_err(SD_ERR_INVALID, "bad copy_frames slots");
-        pr[i] = make_int2(src[i], dst[i]);
-    }
-    HIPCHK(hipMemcpyAsync(b->d_copyPairs, pr.data(), (size_t)n * sizeof(int2), hipMemcpyHostToDevice, s));
-    const SdCopyTable T = copy_table(b);
-    hipLaunchKernelGGL(k_copy_frames, dim3(8, T.n, n), dim3(256), 0, s, T, (const int2*)b->d_copyPairs);
-    LAUNCH_CHECK("k_copy_frames");
-    for (int i = 0; i < n; i++) { b->slotValid[dst[i]] = 1; if (!b->bowValid.empty()) b->bowValid[dst[i]] = 0; }
     return SD_OK;
 }
 
@@ -440,17 +408,7 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
         sd_tracker::Block& B = t->blocks[t->blockHead];
         sd_batch* bp = t->bp[t->blockHead].get();
         HIPCHK(hipStreamWaitEvent(s, B.ready, 0));
-        SdCopyTableX T;
-        int n = 0;
-        const size_t cap = b->plan.kpCap;
-#define SEGX(field, bytes) do { T.src[n] = (const char*)bp->field.get(); T.dst[n] = (char*)b->field.get(); T.slotBytes[n] = (unsigned)(bytes); n++; } while (0)
-        SEGX(d_kp, cap * sizeof(sd_keypoint)); SEGX(d_desc, cap * 32); SEGX(d_uright, cap * 4); SEGX(d_depth, cap * 4); SEGX(d_sad, cap * 4);
-        SEGX(d_count, 4); SEGX(d_lvlCount, (size_t)b->plan.nlevels * 4);
-        if (b->hasDist) SEGX(d_kpUn, cap * sizeof(sd_keypoint));
-#undef SEGX
-        T.n = n;
-        hipLaunchKernelGGL(k_copy_frames_x, dim3(8, T.n, S), dim3(256), 0, s, T, B.next * t->nCur, ipl);
-        LAUNCH_CHECK("k_copy_frames_x");
+        TRK(launch_copy_frames(frame_copy_table(bp, b, SD_FRAME_FRONT), 8, S, nullptr, B.next * t->nCur, ipl, 0, ipl, s));
         b->nExtracted = t->nCur; b->nStereo = t->p.sensor == SD_SENSOR_STEREO ? S : 0; b->lastStream = s;
         for (int l = 0; l < S; l++) b->slotValid[l * ipl] = 1;
         if (++B.next == B.n) { t->blockHead ^= 1; t->blockCount--; }
@@ -461,43 +419,22 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
         if (nIni > 0) {                                            // monocular lanes that are not initialised: mpIniORBextractor (Tracking.cc:335-338)
             sd_batch* bi = t->bIni.get();
             TRK(sd_batch_extract_pixels_device(bi, d_images, stride, image_pitch, t->p.channels, t->p.rgb_order, S, s));
-            const size_t cap = b->plan.kpCap, nl = (size_t)b->plan.nlevels;
-            for (int l0 = 0; l0 < S;) {                            // runs of consecutive lanes: one copy per array
+            const SdCopyTable T = frame_copy_table(bi, b, SD_FRAME_EXTRACT);
+            for (int l0 = 0; l0 < S;) {                            // runs of consecutive lanes: one launch each
                 if (!t->useIniExtractor(l0)) { l0++; continue; }
                 int l1 = l0;
                 while (l1 < S && t->useIniExtractor(l1)) l1++;
-                const size_t n = (size_t)(l1 - l0);
-                HIPCHK(hipMemcpyAsync(b->d_kp + l0 * cap, bi->d_kp + l0 * cap, n * cap * sizeof(sd_keypoint), hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(b->d_desc + l0 * cap * 32, bi->d_desc + l0 * cap * 32, n * cap * 32, hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(b->d_count + l0, bi->d_count + l0, n * 4, hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(b->d_lvlCount + l0 * nl, bi->d_lvlCount + l0 * nl, n * nl * 4, hipMemcpyDeviceToDevice, s));
+                TRK(launch_copy_frames(T, 8, l1 - l0, nullptr, l0, 1, l0, 1, s));
                 l0 = l1;
             }
             b->nExtracted = S; b->nStereo = 0; b->lastStream = s;
             for (int l = 0; l < S; l++) b->slotValid[l] = 1;
         }
     }
-    // ---- UndistortKeyPoints (the identity and free when Camera.k1 == 0), then the stereo association
+    // ---- UndistortKeyPoints, then the stereo / RGB-D association (done ahead by sd_tracker_prefetch for a pool frame)
+    if (!fromPool) TRK(tracker_associate(t, b, S, d_depth, depth_stride_elems, depth_pitch_elems, s));
     std::vector<int32_t> curSlots(S);
     for (int l = 0; l < S; l++) curSlots[l] = l * ipl;
-    if (fromPool) {
-        // done ahead by sd_tracker_prefetch
-    } else if (t->p.sensor == SD_SENSOR_STEREO) {
-        TRK(sd_batch_undistort(b, S, curSlots.data(), s));
-        TRK(sd_batch_stereo_match(b, S, cam->mbf, cam->fx, s));
-    } else if (t->p.sensor == SD_SENSOR_RGBD) {
-        TRK(sd_batch_undistort(b, S, curSlots.data(), s));
-        const float factor = fabsf(t->p.depth_map_factor) < 1e-5f ? 1.0f : 1.0f / t->p.depth_map_factor;       // Tracking.cc:141-146
-        // `if((fabs(mDepthMapFactor-1.0f)>1e-5) || imDepth.type()!=CV_32F) imDepth.convertTo(imDepth,CV_32F,mDepthMapFactor)` (Tracking.cc:271-272)
-        if (t->p.depth_type == SD_DEPTH_F32)
-            TRK(sd_batch_rgbd_from_f32_scaled(b, (const float*)d_depth, depth_stride_elems, depth_pitch_elems, S, fabsf(factor - 1.0f) > 1e-5f ? factor : 1.0f, cam->mbf, s));
-        else
-            TRK(sd_batch_rgbd_from_u16(b, (const uint16_t*)d_depth, depth_stride_elems, depth_pitch_elems, S, factor, cam->mbf, s));
-    } else {
-        TRK(sd_batch_undistort(b, S, curSlots.data(), s));
-        hipLaunchKernelGGL(k_fill_mono, dim3((b->plan.kpCap + 255) / 256, S), dim3(256), 0, s, b->d_count, b->d_uright, b->d_depth, b->plan.kpCap);
-        LAUNCH_CHECK("k_fill_mono");
-    }
     // ---- firstSeparate + split on the device (boxTrack ran on the host above)
     if (!t->hResetSlots.empty()) {
         const int n = (int)t->hResetSlots.size();

@@ -124,6 +124,7 @@ def lib():
         L.sd_batch_set_distortion.argtypes = [vp, vp, vp]
         L.sd_batch_undistort.argtypes = [vp, i, vp, vp]
         L.sd_batch_download_keys_un.argtypes = [vp, i, vp, i, C.POINTER(i)]
+        L.sd_batch_download_dynamic_keys_un.argtypes = [vp, i, vp, i, C.POINTER(i)]
         L.sd_image_bounds.argtypes = [i, i, vp, vp, vp]
         L.sd_batch_backproject_dense.argtypes = [vp, i, vp, vp, sz, sz, vp, sz, sz, f, vp, sz, sz, vp, vp, vp, i, vp, vp]
         L.sd_pose_optimize_device.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
@@ -257,6 +258,13 @@ class Batch:
         kp = np.zeros(self.cap, KP_DTYPE)
         n = C.c_int()
         check(lib().sd_batch_download_keys_un(self.h, image, _p(kp), self.cap, C.byref(n)))
+        return kp[:n.value].copy()
+
+    def download_dynamic_keys_un(self, slot):
+        """mvdynKeysUn of a slot, indexed like download_dynamic (== its key points unless a distortion is set)."""
+        kp = np.zeros(self.cap, KP_DTYPE)
+        n = C.c_int()
+        check(lib().sd_batch_download_dynamic_keys_un(self.h, slot, _p(kp), self.cap, C.byref(n)))
         return kp[:n.value].copy()
 
     def set_distortion(self, K4, dist5):

@@ -486,3 +486,58 @@ def test_export_import_prefetched_between_trackers(gpu, fe, orc, synth, kind):
         assert flags >= 1, "TrackHomo must have run on the later frames"
     finally:
         owner.close(); worker.close(); plain.close()
+
+
+@pytest.mark.parametrize("kind", ["stereo", "rgbd-tum1"])
+def test_prefetched_record_layout(gpu, fe, orc, synth, kind):
+    """The record of a prefetched frame is the history-free half of its slot in a fixed order, each segment padded to 16 bytes: N, the per-level
+    counts, mvKeys (28-byte records), descriptors, mvuRight, mvDepth, the SAD distances, and mvKeysUn when the camera is distorted (TUM1).
+    sd_tracker_prefetched_record_bytes is the sum of those, and an exported record holds at those offsets what the worker's pool slot holds.  The
+    pool workspace has no accessor of its own: a box-less sd_tracker_track(d_images = NULL) moves the pool slot, byte for byte, to the lane's
+    current slot of the tracker's workspace (no boxes: nothing permutes the arrays afterwards), and that slot is downloaded."""
+    import torch
+    stereo = kind == "stereo"
+    cfg = synth.KITTI_STEREO if stereo else synth.TUM1
+    sensor = fe.SENSOR_STEREO if stereo else fe.SENSOR_RGBD
+    ch = 1 if stereo else 3
+    W, H, S = cfg["width"], cfg["height"], 2
+    ex = fe.ORBextractor(cfg["n_features"], cfg["scale_factor"], cfg["n_levels"], cfg["ini_th_fast"], cfg["min_th_fast"])
+    trk = fe.Tracker(ex, cfg, sensor, S, channels=ch, rgb_order=True, track_last=False, lookahead=1)
+    try:
+        cap, nl = trk.batch.cap, cfg["n_levels"]
+        a16 = lambda n: (n + 15) & ~15
+        sizes = [("count", 4), ("per_level", nl * 4), ("kp", cap * 28), ("desc", cap * 32), ("uright", cap * 4), ("depth", cap * 4), ("sad", cap * 4)]
+        if not stereo:
+            sizes.append(("keys_un", cap * 28))
+        offset, R = {}, 0
+        for name, n in sizes:
+            offset[name] = R; R += a16(n)
+        assert trk.record_bytes() == R
+        frames = [(synth.stereo_frame_dyn(q, 0, cfg)[:2] if stereo else synth.rgbd_frame_dyn(q, 0, cfg)[:2]) for q in (95, 96)]
+        if stereo:
+            img, dep = torch.from_numpy(np.stack([np.stack(f) for f in frames])).cuda(), None
+        else:
+            img = torch.from_numpy(np.stack([f[0] for f in frames])).cuda()
+            dep = torch.from_numpy(np.stack([f[1] for f in frames]).view(np.int16)).cuda()
+        trk.prefetch(img.data_ptr(), W * ch, W * H * ch, 1, d_depth=dep.data_ptr() if dep is not None else 0, depth_stride=W, depth_pitch=W * H)
+        rec = torch.full((S, R), 0xA5, dtype=torch.uint8, device="cuda")
+        trk.export_prefetched(0, 1, rec.data_ptr())
+        res = trk.track(0, W * ch, W * H * ch, [0.0] * S)
+        rec = rec.cpu().numpy()
+        for l in range(S):
+            slot = res[l].cur_slot
+            kp, desc, per_level = trk.batch.download(slot)
+            ur, dpt = trk.batch.download_rgbd(slot)
+            n = len(kp)
+            seg = lambda name, nbytes: rec[l, offset[name]:offset[name] + nbytes].tobytes()
+            assert n > 500 and seg("count", 4) == np.int32(n).tobytes()
+            assert seg("per_level", nl * 4) == per_level.tobytes()
+            assert seg("kp", n * 28) == kp.tobytes() and seg("desc", n * 32) == desc.tobytes()
+            assert seg("uright", n * 4) == ur[:n].tobytes() and seg("depth", n * 4) == dpt[:n].tobytes()
+            if stereo:
+                assert seg("sad", n * 4) == trk.batch.download_stereo(l)[2][:n].tobytes()
+            else:
+                un = trk.batch.download_keys_un(slot)
+                assert seg("keys_un", n * 28) == un.tobytes() and un.tobytes() != kp.tobytes()
+    finally:
+        trk.close()
