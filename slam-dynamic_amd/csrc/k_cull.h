@@ -63,7 +63,7 @@ __global__ void __launch_bounds__(256) k_box_separate(SdCullPtrs A, const int* _
     unsigned* code = (unsigned*)(dmask + A.cap);    // [cap] partition code: static rank, or 0x80000000 | dynamic rank
     __shared__ int s_wsum[4];
     __shared__ bmask s_has;
-    __shared__ int s_nb2, s_empty, s_remap[SD_MAXB], s_kept[SD_MAXB], s_cnt[SD_MAXB], s_start[SD_MAXB + 1];
+    __shared__ int s_nb2, s_empty, s_ovf, s_remap[SD_MAXB], s_kept[SD_MAXB], s_cnt[SD_MAXB], s_start[SD_MAXB + 1];
     __shared__ double s_box[SD_MAXB][4];
     const int slot = slots[blockIdx.x], tid = threadIdx.x;
     SdFrameBoxes& F = A.fb[slot];
@@ -189,6 +189,7 @@ __global__ void __launch_bounds__(256) k_box_separate(SdCullPtrs A, const int* _
         int pos = 0;
         for (int b = 0; b < nb2; b++) { s_start[b] = pos; pos += cntNew[b]; }
         s_start[nb2] = pos;
+        s_ovf = pos > A.itemsCap;
         if (pos > A.itemsCap) atomicOr(A.errFlag, 16);
     }
     __syncthreads();
@@ -200,6 +201,13 @@ __global__ void __launch_bounds__(256) k_box_separate(SdCullPtrs A, const int* _
     }
     __syncthreads();
     // ---- frame record: objects = boxes after the erase; N = N_s
+    // The lists do not fit the item table (flag 16, refused at the next synchronisation): kernels enqueued before that
+    // synchronisation (the tracker's k_separate / k_update_frame) index boxItems, dynStatus and matches by boxStart, so the record
+    // they see is a frame without boxes.
+    if (s_ovf) {
+        if (tid == 0) { F.nb = 0; F.boxStart[0] = 0; F.nAll = N; F.nOri = Ns; F.nDyn = Nd; A.count[slot] = Ns; }
+        return;
+    }
     int o = 0, id = 0;
     if (tid < nb2) { o = s_kept[tid]; id = F.box_idx[o]; }
     __syncthreads();                                              // all reads of F.box_idx before the in-place rewrite

@@ -166,3 +166,169 @@ def test_randomised_cull_configurations(gpu):
     spec = importlib.util.spec_from_file_location("fuzz_cull", os.path.join(os.path.dirname(__file__), "..", "tools", "fuzz_cull.py"))
     m = importlib.util.module_from_spec(spec); spec.loader.exec_module(m)
     assert m.run(6, 17) == 0
+
+
+# ---- crafted key points, boxes and models (tests/cull_cases.py): the images only make the slots valid, key points and descriptors are
+# written over the extraction results.  tests/test_oracle_cull.py pins which branch every case reaches (and that the threshold scans can see
+# an FMA contraction); here the device output on the same arrays must be the oracle's bytes.
+
+import cull_cases as cc  # noqa: E402
+
+
+def _assert_cases(orc, ws, cases, what, only_if_static=False):
+    got = cc.run_cases(ws, cases, only_if_static)
+    bad, n_kp, n_dyn = [], 0, 0
+    for p, (c, g_) in enumerate(zip(cases, got)):
+        o = cc.oracle(orc, c, only_if_static)
+        d = cc.compare(g_, o, orc)
+        n_kp += len(c["cur"]["kp"]) + len(c["ref"]["kp"]); n_dyn += len(o["dyn"])
+        if d:
+            bad.append("%s [pair %d of %d]: %s" % (c["name"], p, len(cases), "; ".join(d)))
+    print("%s: %d cases, %d key points, %d classified matches compared, %d cases differ" % (what, len(cases), n_kp, n_dyn, len(bad)))
+    assert not bad, "\n".join(bad)
+    return got
+
+
+def test_crafted_cases_match_oracle(gpu, fe, orc):
+    """cull_cases.suite() in launches of 128 pairs, then the distortion group (its own camera) on the same workspace: every field that
+    firstSeparate, Separate and UpdateFrame leave behind is the oracle's.  Building the library with -ffp-contract=fast makes this test fail
+    on the threshold_scans cases (test_oracle_cull.py::test_threshold_scans_see_contraction shows the same source deciding 112 / 95 of their
+    matches differently when contracted)."""
+    cases = cc.suite()
+    ws = cc.Workspace(fe, 128)
+    try:
+        assert ws.cap == cc.GEOM.cap, "kp_capacity %d, the generators assume %d" % (ws.cap, cc.GEOM.cap)
+        for k0 in range(0, len(cases), ws.n_pairs):
+            _assert_cases(orc, ws, cases[k0:k0 + ws.n_pairs], "suite %d.." % k0)
+        _assert_cases(orc, ws, cc.distortion(), "distortion")
+        _assert_cases(orc, ws, cases[:3], "after the distortion is switched off again")
+    finally:
+        ws.close()
+
+
+def test_crafted_chunk_boundary(gpu, fe, orc):
+    """Train lists of 2047, 2048, 2049 and 4097 descriptors: the LDS chunk limit of k_separate, with ties across it."""
+    ws = cc.Workspace(fe, 4, cc.GEOM_BIG)
+    try:
+        assert ws.cap >= 4200, "kp_capacity %d" % ws.cap
+        _assert_cases(orc, ws, cc.chunk_boundary(ws.cap), "chunk_boundary")
+    finally:
+        ws.close()
+
+
+def _pool():
+    S = {c["name"]: c for c in cc.suite()}
+    return [S[n] for n in ("threshold_scans-flag1-0", "empty_box_patterns-no_keypoints_cur", "hamming_ties-two_queries_3_259", "empty_box_patterns-none",
+                           "membership_edges-depth", "empty_box_patterns-no_keypoints_ref", "threshold_scans-flag2-1", "empty_box_patterns-010010",
+                           "partition_sizes-n513-alternating", "status_table-n_last_64", "readmission-shared")]
+
+
+def test_crafted_cases_do_not_depend_on_slot_or_neighbours(gpu, fe, orc):
+    """1, 7, 8, 9, 17 pairs per launch, the pool in rotated order: the same case in different slots, frames without key points and a frame
+    without boxes between full ones.  Every case's result is the same bytes in every launch, equals the oracle, and a launch run twice gives
+    the same bytes (the LDS atomics are order-free)."""
+    pool = _pool()
+    ws = cc.Workspace(fe, 17)
+    seen = {}
+    try:
+        for n in (1, 7, 8, 9, 17):
+            cases = [pool[(k + n) % len(pool)] for k in range(n)]
+            got = _assert_cases(orc, ws, cases, "%d pairs" % n)
+            again = cc.run_cases(ws, cases)
+            for p, (c, g_, a_) in enumerate(zip(cases, got, again)):
+                bts = cc.result_bytes(g_)
+                assert bts == cc.result_bytes(a_), "%s [pair %d of %d]: two runs of one launch differ" % (c["name"], p, n)
+                assert seen.setdefault(c["name"], bts) == bts, "%s [pair %d of %d]: differs from its result in another launch" % (c["name"], p, n)
+        assert len(seen) == len(pool)
+    finally:
+        ws.close()
+
+
+def test_update_frame_only_if_static(gpu, fe, orc):
+    """UpdateFrame(only_if_static) leaves a frame alone whose Separate returned 0 and re-admits where it returned 1; UpdateFrame(always)
+    re-admits the consistent match of the ret-0 box too."""
+    cases = cc.readmission()
+    ws = cc.Workspace(fe, len(cases))
+    try:
+        gated = _assert_cases(orc, ws, cases, "only_if_static", only_if_static=True)
+        always = _assert_cases(orc, ws, cases, "always", only_if_static=False)
+        shared, ret0 = 0, 1
+        assert gated[ret0]["ret"] == 0 and gated[ret0]["count_after"] == gated[ret0]["cur"]["n_static"]
+        assert always[ret0]["count_after"] == always[ret0]["cur"]["n_static"] + 1
+        assert gated[shared]["ret"] == 1 and gated[shared]["count_after"] == always[shared]["count_after"] == gated[shared]["cur"]["n_static"] + 11
+    finally:
+        ws.close()
+
+
+def _overflow_frames(cap):
+    """Three boxes that each hold every key point; 3 N box items against an item table of 2 * cap: N just above and just below."""
+    n_over = 2 * cap // 3 + 1
+    n_under = 2 * cap // 3
+    assert 3 * n_over > 2 * cap >= 3 * n_under and n_over <= cap
+    rng = np.random.default_rng(5)
+    out = []
+    for n in (n_over, n_under):
+        k = cc.kps(rng.uniform(4, cc.W - 4, n), rng.uniform(4, cc.H - 4, n))
+        out.append(cc.frame(k, cc.sc.rand_desc(rng, n), [(0.0, 0.0, float(cc.W), float(cc.H))] * 3, [1, 2, 3]))
+    return out
+
+
+def test_item_table_overflow_is_refused(gpu, fe, orc):
+    """A frame whose box lists need more than 2 * kp_capacity items: the next synchronisation refuses it and names the box tables; the frame
+    just below the limit, alone on a fresh workspace, is the oracle's."""
+    ws = cc.Workspace(fe, 1)
+    try:
+        over, under = _overflow_frames(ws.cap)
+        cc.upload(ws, [over, under])
+        ws.b.first_separate([0, 1], [over["boxes"], under["boxes"]], [over["ids"], under["ids"]])
+        with pytest.raises(fe.SdError) as e:
+            ws.b.sync()
+        assert e.value.code == fe.SD_ERR_UNSUPPORTED and "box tables" in str(e.value)
+    finally:
+        ws.close()
+    ws = cc.Workspace(fe, 1)
+    try:
+        cc.upload(ws, [under])
+        ws.b.first_separate([0], [under["boxes"]], [under["ids"]])
+        r = cc.oracle_frame(orc, under)
+        assert r["boxStart"][-1] == 3 * len(under["kp"]) <= 2 * ws.cap
+        bad = cc.compare_frame([], "below the limit", cc.download_frame(ws.b, 0), r, np.full(3, -1))
+        assert not bad, "; ".join(bad)
+    finally:
+        ws.close()
+
+
+def test_item_table_overflow_leaves_an_empty_frame_record(gpu, fe, orc):
+    """The tracker enqueues Separate and UpdateFrame behind firstSeparate without a synchronisation between them, so an overflowed frame must
+    reach them as a frame without boxes (nb = 0, boxStart[0] = 0): then no index leaves the item table.  Pair 0 has the overflowed frame as
+    its current frame, pair 1 as its reference frame, pair 2 is an untouched neighbour; the whole chain is enqueued, the synchronisation
+    refuses, and the neighbour's results are the oracle's."""
+    ws = cc.Workspace(fe, 3)
+    try:
+        over, under = _overflow_frames(ws.cap)
+        (neighbour, _) = cc.readmission()
+        frames = [under, over, over, under, neighbour["ref"], neighbour["cur"]]
+        cc.upload(ws, frames)
+        b = ws.b
+        b.first_separate(list(range(6)), [f["boxes"] for f in frames], [f["ids"] for f in frames])
+        b.separate([1, 3, 5], [0, 2, 4], np.stack([cc.I3] * 3), [1, 1, 1], [[], [], []], [[], [], []])
+        b.update_frame(only_if_static=False)
+        with pytest.raises(fe.SdError) as e:
+            b.sync()
+        assert e.value.code == fe.SD_ERR_UNSUPPORTED and "box tables" in str(e.value)
+        for slot in (1, 2):
+            g = b.download_boxes(slot)
+            assert g["nb"] == 0 and g["boxStart"].tolist() == [0] and g["n_all"] == len(over["kp"]) and g["n_static"] == 0
+        for pair in (0, 1):
+            ret, ds, dyn, mt = b.download_separate(pair)
+            assert ret == 0 and not ds.any() and len(dyn) == 0
+        o = cc.oracle(orc, neighbour)
+        ret, ds, dyn, mt = b.download_separate(2)
+        assert ret == o["ret"] and np.array_equal(ds[:3], o["dynStart"]) and np.array_equal(dyn, o["dyn"]) and np.array_equal(mt, o["matches"])
+        bad = cc.compare_frame([], "neighbour", cc.download_frame(b, 5), dict(o["cur"], Ns=o["cur"]["Ns"]), o["status"])
+        # UpdateFrame has run: the static count has grown by the re-admitted key points, everything else is as after Separate
+        bad = [m for m in bad if not m.startswith("neighbour static")]
+        kp, desc, _ = b.download(5)
+        assert not bad and kp.tobytes() == o["kp_after"].tobytes() and np.array_equal(desc, o["desc_after"]), "; ".join(bad)
+    finally:
+        ws.close()

@@ -1,8 +1,14 @@
 """Randomised parity sweep of the dynamic-object cull against the CPU oracle (developer tool): firstSeparate with random box
 sets (empty, overlapping, partly outside the image), Separate with H or F (exact or perturbed, so that the static / dynamic
-decision goes both ways) and random carried-over box states, UpdateFrame."""
+decision goes both ways) and random carried-over box states, UpdateFrame.
+
+    python tools/fuzz_cull.py [cases = 20] [seed = 3]             rendered frames, extracted key points
+    python tools/fuzz_cull.py crafted [draws = 64] [seed = 5]     crafted key points (tests/cull_cases.py): random populated / empty box
+                                                                  patterns, Hamming ties, matches within a few f32 steps of the threshold"""
 import os, sys
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import __graft_entry__ as g
 
@@ -111,5 +117,64 @@ def run(n_cases, seed0):
     return 0
 
 
+def draw_crafted(cc, seed, k):
+    """One random crafted case: up to 8 boxes on tiles of their own, each populated (1 .. 40 pairs, some 10 px off, some unpartnered key points
+    on either side) or empty; in half the draws two queries of a box are put at the same distance from one train and two trains at the same
+    distance from one query; in half the draws consistent matches are moved sqrt(threshold) +- a few f32 steps along x."""
+    P = cc.Pair("fuzz-%d-%d" % (seed, k), 77, seed, k)
+    rng = P.rng
+    flag = int(rng.integers(1, 3))
+    th = cc.TH_H if flag == 1 else cc.TH_F
+    nb = int(rng.integers(0, 9))
+    ids = rng.permutation(12)[:nb]
+    for t, id_ in zip(rng.permutation(24)[:nb], ids):
+        if rng.random() < 0.3:
+            for side in (0, 1):
+                P.add_box(side, (94.0 * (t % 8) + 40, 60.0 * (t // 8) + 30, float(rng.uniform(-2, 2)), 1.0), int(id_))
+            continue
+        n = int(rng.integers(1, 41))
+        dyn = np.nonzero(rng.random(n) < rng.choice([0.0, 0.3, 0.8, 1.0]))[0]
+        P.box(int(t), int(id_), n, dyn=dyn, ref_id=int(id_) + 50 if rng.random() < 0.1 else None,
+              n_ref_extra=int(rng.integers(0, 4)), n_cur_extra=int(rng.integers(0, 6)) * int(rng.random() < 0.5))
+        kr, dr, kc, dc = P.k[0][-1], P.d[0][-1], P.k[1][-1], P.d[1][-1]
+        if n >= 6 and rng.random() < 0.5:
+            a, b2, c, d = rng.permutation(n)[:4]
+            dc[a] = cc.sc.flipped(rng, dr[a:a + 1], 16)[0]; dc[b2] = cc.sc.flipped(rng, dr[a:a + 1], 16)[0]
+            dr[c] = cc.sc.flipped(rng, dc[d:d + 1], 16)[0]; dr[d] = cc.sc.flipped(rng, dc[d:d + 1], 16)[0]
+        if rng.random() < 0.5:
+            for m in np.nonzero(rng.random(n) < 0.5)[0]:
+                if m not in dyn:
+                    kc["x"][m] = cc.steps(np.float32(kr["x"][m] + np.float32(np.sqrt(th))), int(rng.integers(-6, 7)))
+    P.statics(int(rng.integers(0, 12)))
+    nl = int(rng.integers(0, 6))
+    return P.case(M=cc.I3 if flag == 1 else cc.F_IDENT, flag=flag, last_idx=rng.permutation(12)[:nl], last_status=rng.integers(-1, 3, nl))
+
+
+def run_crafted(n_draws, seed, pairs=32):
+    """-> number of crafted cases whose device result differs from the oracle."""
+    import cull_cases as cc
+    pkg = g.load_package(); orc = g.load_oracle()
+    ws = cc.Workspace(pkg.frontend, pairs)
+    stats = dict(cases=0, boxes=0, empty_boxes_dropped=0, matches=0, consistent=0, ret1=0, readmitted=0)
+    failures = 0
+    try:
+        for k0 in range(0, n_draws, pairs):
+            cases = [draw_crafted(cc, seed, k) for k in range(k0, min(k0 + pairs, n_draws))]
+            for c, r in zip(cases, cc.run_cases(ws, cases)):
+                o = cc.oracle(orc, c)
+                stats["cases"] += 1; stats["boxes"] += len(o["cur"]["box_idx"]); stats["empty_boxes_dropped"] += len(c["cur"]["ids"]) - len(o["cur"]["box_idx"])
+                stats["matches"] += len(o["dyn"]); stats["consistent"] += int((o["dyn"] != -1).sum()); stats["ret1"] += o["ret"]; stats["readmitted"] += len(o["appended"])
+                bad = cc.compare(r, o, orc)
+                if bad:
+                    failures += 1
+                    print("MISMATCH %s: %s" % (c["name"], "; ".join(bad)))
+    finally:
+        ws.close()
+    print("fuzz_cull crafted: %d cases, %d differ (seed %d);" % (stats["cases"], failures, seed), stats)
+    return failures
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "crafted":
+        sys.exit(min(1, run_crafted(int(sys.argv[2]) if len(sys.argv) > 2 else 64, int(sys.argv[3]) if len(sys.argv) > 3 else 5)))
     sys.exit(run(int(sys.argv[1]) if len(sys.argv) > 1 else 20, int(sys.argv[2]) if len(sys.argv) > 2 else 3))
