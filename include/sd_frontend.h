@@ -264,6 +264,42 @@ int sd_batch_download_bow(sd_batch* b, int image, uint32_t* bow_word, double* bo
 int sd_batch_search_by_bow(sd_batch* b, int n_pairs, const int32_t* kf_index, const int32_t* frame_index,
                            const uint8_t* d_kf_valid, float nnratio, int checkOrientation, void* stream);
 
+/* ---- LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:208-453) ----
+ * ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (src/ORBmatcher.cc:814-980, with
+ * CheckDistEpipolarLine :140-157) for n_pairs independent pairs of batch slots: KF1 = slot kf1_index[p], KF2 = slot kf2_index[p]
+ * (sd_batch_compute_bow must have run on both: SD_ERR_STATE otherwise).  Tcw1_host / Tcw2_host: n_pairs row-major 4x4 poses; F12
+ * (LocalMapping::ComputeF12, :537-554) and the epipole are formed from them and `cam` on the host.  d_has_mp1 / d_has_mp2
+ * (nullable, [n_pairs][cap] u8): pKF->GetMapPoint(i) != NULL.  check_orientation = the matcher's mbCheckOrientation
+ * (CreateNewMapPoints builds ORBmatcher(0.6, false)).  As in the reference two features of KF1 may take the same feature of KF2
+ * (vbMatched2 is never set).  Results through sd_batch_download_matches: match[idx1] = idx2 or -1, pairs = vMatchedPairs
+ * ((idx1, idx2), ascending idx1), nmatches = the return value. */
+int sd_batch_search_for_triangulation(sd_batch* b, int n_pairs, const int32_t* kf1_index, const int32_t* kf2_index,
+                                      const float* Tcw1_host, const float* Tcw2_host, const sd_camera* cam,
+                                      const uint8_t* d_has_mp1, const uint8_t* d_has_mp2, int only_stereo, int check_orientation,
+                                      void* stream);
+/* A point CreateNewMapPoints creates: `neighbour` = position in the keyframe's neighbour list, idx1 / idx2 = the observations
+ * (pMP->AddObservation(mpCurrentKeyFrame, idx1), AddObservation(pKF2, idx2)), xw = the MapPoint's world position. */
+typedef struct sd_new_map_point {
+    int32_t neighbour, idx1, idx2;
+    float xw[3];
+} sd_new_map_point;       /* 24 bytes */
+/* The loop body of CreateNewMapPoints for n_kf keyframes in one launch sequence.  Keyframe k = slot kf_index[k] with pose
+ * kf_Tcw_host[k] and d_kf_has_mp (nullable, [n_kf][cap] u8: GetMapPoint(i) != NULL when the function starts); it owns neighbours
+ * [neigh_offset[k], neigh_offset[k+1]) in GetBestCovisibilityKeyFrames order: slot neigh_index[j], pose neigh_Tcw_host[j],
+ * d_neigh_has_mp (nullable, [neighbours][cap] u8).  neigh_median_depth NULL = the stereo / RGB-D rule `baseline < mb -> skip`;
+ * otherwise the monocular rule `baseline / neigh_median_depth[j] < 0.01 -> skip` (pKF2->ComputeSceneMedianDepth(2), the caller's).
+ * A feature triangulated with one neighbour is skipped by the later ones (AddMapPoint, :440).  Keyframes of one call do not see each
+ * other's new points.  The early return on CheckNewKeyFrames() is the caller's: it passes the neighbours it wants.
+ * The poses are used as given (any 4x4): a match whose triangulation has x3D[3] == 0 is skipped, as in the reference.  A stereo point
+ * (uRight >= 0) whose depth is <= 0 is skipped where the reference would unproject it.
+ * Output (library-owned device memory, valid until the next call): d_new [n_kf][cap] records in creation order (neighbour ascending,
+ * then idx1 ascending), d_nnew [n_kf] = nnew. */
+int sd_batch_create_new_map_points(sd_batch* b, int n_kf, const int32_t* kf_index, const float* kf_Tcw_host,
+                                   const uint8_t* d_kf_has_mp, const int32_t* neigh_offset, const int32_t* neigh_index,
+                                   const float* neigh_Tcw_host, const float* neigh_median_depth, const uint8_t* d_neigh_has_mp,
+                                   const sd_camera* cam, sd_new_map_point** d_new, int32_t** d_nnew, void* stream);
+int sd_batch_download_new_map_points(sd_batch* b, int kf, sd_new_map_point* out, int cap, int* nnew);
+
 /* The model fit of Tracking::TrackHomo (src/Tracking.cc:1026-1075) for every pair of the preceding
  * sd_batch_search_by_projection, from its points_last / points_current: replaces cv::findHomography(points_last,
  * points_current, RANSAC, 3, inliers_H), cv::findFundamentalMat(..., RANSAC, 3, 0.99, inliers_F), the inlier counts

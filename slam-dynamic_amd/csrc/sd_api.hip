@@ -20,6 +20,7 @@
 #include "k_tracker.h"
 #include "k_cloud.h"
 #include "k_pose.h"
+#include "k_triangulate.h"
 #include "sd_common.h"
 #include "sd_vocab.h"
 
@@ -44,11 +45,11 @@ struct sd_extractor {
     SdParams prm;
 };
 
-enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_COUNT };
+enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_TRI_M, K_TRI_T, K_TRI_R, K_COUNT };
 static const char* kKernelNames[K_COUNT] = {"k_pyr_level0", "k_pyr_level", "k_fast_cells", "k_quadtree", "k_orient",
                                             "k_blur", "k_describe", "k_stereo_match", "k_stereo_filter", "k_rgbd",
                                             "k_grid_cells", "k_unproject", "k_proj_candidates", "k_proj_resolve",
-                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select"};
+                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select", "k_tri_match", "k_tri_triangulate", "k_tri_resolve"};
 
 #define SD_PT_TW 256
 #define SD_PT_TH 16
@@ -119,6 +120,12 @@ struct sd_batch {
     SdDevBuf<sd_pose_edge> d_poseEdges; SdDevBuf<int> d_poseFirst; SdDevBuf<int> d_poseLast; SdDevBuf<float> d_poseT;
     SdDevBuf<uint8_t> d_poseOut; SdDevBuf<int> d_poseGood; SdDevBuf<sd_camera> d_poseCam; SdDevBuf<int> d_poseMap; SdDevBuf<int> d_poseRan;
     SdDevBuf<float> d_poseTin;
+    // SearchForTriangulation / CreateNewMapPoints (k_triangulate.h), grown on demand: the pair records, and for CreateNewMapPoints the
+    // (keyframe x neighbour) match tables, the per-match triangulation results and the compacted new points per keyframe
+    SdDevBuf<SdTriPair> d_triPairs; int triPairCap = 0; std::vector<SdTriPair> hostTriPairs;     // staging that must outlive the async upload
+    SdDevBuf<int> d_triMatch; SdDevBuf<int> d_triPairList; SdDevBuf<int> d_triNp; SdDevBuf<uint8_t> d_triOk; SdDevBuf<float> d_triXw;
+    int triTableCap = 0;
+    SdDevBuf<int> d_triOff; SdDevBuf<sd_new_map_point> d_triNew; SdDevBuf<int> d_triNnew; int triKfCap = 0, triKfs = 0;
     std::vector<sd_camera> pairCam, hPoseCam; std::vector<int32_t> hPoseMap;
     int nPairs = 0;
     int dlPairs = 0;          // pairs sd_batch_download_matches may read (the tracker also keeps pairs at [n_lanes, 2 * n_lanes))
@@ -1468,6 +1475,214 @@ int sd_batch_search_by_bow(sd_batch* b, int n_pairs, const int32_t* kf_index, co
         LAUNCH_CHECK("k_search_by_bow");
     }
     b->nPairs = n_pairs; b->dlPairs = n_pairs;
+    return SD_OK;
+}
+
+// ---------------------------------------------------------------- SearchForTriangulation / CreateNewMapPoints (k_triangulate.h)
+// Everything the reference derives from the two poses alone, as cv::Mat forms it (every small product accumulates in
+// double, k ascending, and narrows once).
+namespace {
+inline float tri_acc3(const float* a, int sa, const float* b, int sb, bool neg = false, const float* add = nullptr)
+{
+    double s = 0.0;
+    for (int k = 0; k < 3; k++) s += (double)(neg ? -a[k * sa] : a[k * sa]) * (double)b[k * sb];
+    if (add) s += (double)*add;
+    return (float)s;
+}
+inline void tri_mul33(const float* A, const float* B, float* C)      // C = A * B, row-major 3x3
+{
+    float out[9];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) out[i * 3 + j] = tri_acc3(A + i * 3, 1, B + j, 3);
+    memcpy(C, out, sizeof(out));
+}
+// KeyFrame::SetPose: Ow = -Rwc * tcw (KeyFrame.cc:70-84)
+inline void tri_center(const float* T /*4x4*/, float* Ow)
+{
+    const float t[3] = {T[3], T[7], T[11]};
+    for (int i = 0; i < 3; i++) Ow[i] = tri_acc3(T + i, 4, t, 1, true);       // row i of Rwc = column i of Rcw
+}
+// false = the neighbour is skipped by the baseline rule (LocalMapping.cc:245-262)
+inline void tri_pair_setup(const float* Tcw1, const float* Tcw2, const sd_camera& cam, const float* medianDepth, bool baselineRule, SdTriPair& P)
+{
+    for (int r = 0; r < 3; r++) for (int c = 0; c < 4; c++) { P.T1[r * 4 + c] = Tcw1[r * 4 + c]; P.T2[r * 4 + c] = Tcw2[r * 4 + c]; }
+    tri_center(Tcw1, P.Ow1); tri_center(Tcw2, P.Ow2);
+    P.skip = 0;
+    if (baselineRule) {
+        const float bx = P.Ow2[0] - P.Ow1[0], by = P.Ow2[1] - P.Ow1[1], bz = P.Ow2[2] - P.Ow1[2];
+        double ss = (double)bx * (double)bx; ss += (double)by * (double)by; ss += (double)bz * (double)bz;
+        const float baseline = (float)std::sqrt(ss);
+        if (!medianDepth) { if (baseline < cam.mb) P.skip = 1; }
+        else { const float ratio = baseline / *medianDepth; if ((double)ratio < 0.01) P.skip = 1; }
+    }
+    float R1[9], R2[9], R2t[9], t1[3], t2[3];
+    for (int r = 0; r < 3; r++) { for (int c = 0; c < 3; c++) { R1[r * 3 + c] = Tcw1[r * 4 + c]; R2[r * 3 + c] = Tcw2[r * 4 + c]; R2t[c * 3 + r] = Tcw2[r * 4 + c]; } t1[r] = Tcw1[r * 4 + 3]; t2[r] = Tcw2[r * 4 + 3]; }
+    // ComputeF12 (LocalMapping.cc:537-554)
+    float R12[9], t12[3];
+    tri_mul33(R1, R2t, R12);
+    for (int i = 0; i < 3; i++) t12[i] = tri_acc3(R12 + i * 3, 1, t2, 1, true, &t1[i]);
+    const float t12x[9] = {0.f, -t12[2], t12[1], t12[2], 0.f, -t12[0], -t12[1], t12[0], 0.f};
+    const float ifx = (float)(1.0 / (double)cam.fx), ify = (float)(1.0 / (double)cam.fy);
+    const float icx = (float)(-(double)cam.cx / (double)cam.fx), icy = (float)(-(double)cam.cy / (double)cam.fy);
+    const float Kinv[9] = {ifx, 0.f, icx, 0.f, ify, icy, 0.f, 0.f, 1.f};
+    const float KinvT[9] = {ifx, 0.f, 0.f, 0.f, ify, 0.f, icx, icy, 1.f};
+    float M[9];
+    tri_mul33(KinvT, t12x, M); tri_mul33(M, R12, M); tri_mul33(M, Kinv, P.F12);
+    // the epipole of KF1's centre in KF2 (ORBmatcher.cc:820-827)
+    float C2[3];
+    for (int i = 0; i < 3; i++) C2[i] = tri_acc3(R2 + i * 3, 1, P.Ow1, 1, false, &t2[i]);
+    const float invz = 1.0f / C2[2];
+    P.ex = cam.fx * C2[0] * invz + cam.cx;
+    P.ey = cam.fy * C2[1] * invz + cam.cy;
+}
+SdTriLevels tri_levels(const sd_batch* b)
+{
+    SdTriLevels L;
+    for (int l = 0; l < SD_MAX_LEVELS; l++) { const bool in = l < b->ex->prm.nlevels; L.scale[l] = in ? b->ex->prm.scale[l] : 1.f; L.sigma2[l] = in ? b->ex->prm.sigma2[l] : 1.f; }
+    return L;
+}
+int tri_ensure_pairs(sd_batch* b, int n)
+{
+    if (n <= b->triPairCap) return SD_OK;
+    SdDevBuf<SdTriPair> p;
+    HIPCHK(p.alloc((size_t)n * sizeof(SdTriPair)));
+    b->d_triPairs = std::move(p); b->triPairCap = n;
+    return SD_OK;
+}
+int tri_launch_match(sd_batch* b, int n, const uint8_t* h1, const uint8_t* h2, int onlyStereo, int checkOrientation, int* match, int* pairs,
+                     int* np, int* nm, hipStream_t s)
+{
+    const int cap = b->plan.kpCap;
+    const size_t lds = (size_t)cap * 4 + SD_TRI_THREADS * 4 + cap + 16;
+    if (lds > 64 * 1024) HIPCHK(sd_raise_lds_limit((const void*)k_tri_match, (int)lds));
+    ProfScope ps(b, s, K_TRI_M);
+    hipLaunchKernelGGL(k_tri_match, dim3(n), dim3(SD_TRI_THREADS), lds, s, KPUN(b), b->d_desc, b->d_uright, b->d_count, b->d_fvFeat, b->d_fvRunStart,
+                       b->d_fvRunNode, b->d_bowMeta, h1, h2, b->d_triPairs, tri_levels(b), cap, onlyStereo, checkOrientation, match, pairs, np, nm);
+    LAUNCH_CHECK("k_tri_match");
+    return SD_OK;
+}
+bool tri_bow_ok(const sd_batch* b, int slot) { return b->d_bowWordF && b->bowValid[slot]; }
+}
+
+// ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (src/ORBmatcher.cc:814-980)
+int sd_batch_search_for_triangulation(sd_batch* b, int n_pairs, const int32_t* kf1_index, const int32_t* kf2_index, const float* Tcw1_host,
+                                      const float* Tcw2_host, const sd_camera* cam, const uint8_t* d_has_mp1, const uint8_t* d_has_mp2,
+                                      int only_stereo, int check_orientation, void* stream_)
+{
+    if (!b || n_pairs <= 0 || n_pairs > b->maxImages || !cam_ok(cam) || !kf1_index || !kf2_index || !Tcw1_host || !Tcw2_host)
+        return set_err(SD_ERR_INVALID, "bad search_for_triangulation arguments");
+    for (int p = 0; p < n_pairs; p++) {
+        if (kf1_index[p] < 0 || kf1_index[p] >= b->maxImages || kf2_index[p] < 0 || kf2_index[p] >= b->maxImages)
+            return set_err(SD_ERR_INVALID, "search_for_triangulation: slot out of range");
+        if (!slot_ok(b, kf1_index[p]) || !slot_ok(b, kf2_index[p])) return set_err(SD_ERR_STATE, "search_for_triangulation: slot holds no results");
+        if (!tri_bow_ok(b, kf1_index[p]) || !tri_bow_ok(b, kf2_index[p]))
+            return set_err(SD_ERR_STATE, "search_for_triangulation: sd_batch_compute_bow has not run on these slots");
+    }
+    if (b->plan.kpCap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
+    b->lastStream = s;
+    b->nPairs = 0; b->dlPairs = 0;
+    std::vector<SdTriPair>& P = b->hostTriPairs;
+    P.resize(n_pairs);
+    for (int p = 0; p < n_pairs; p++) {
+        P[p].img1 = kf1_index[p]; P[p].img2 = kf2_index[p]; P[p].row1 = p; P[p].row2 = p;
+        tri_pair_setup(Tcw1_host + 16 * (size_t)p, Tcw2_host + 16 * (size_t)p, *cam, nullptr, false, P[p]);
+    }
+    int rc = tri_ensure_pairs(b, n_pairs);
+    if (rc != SD_OK) return rc;
+    HIPCHK(hipMemcpyAsync(b->d_triPairs, P.data(), (size_t)n_pairs * sizeof(SdTriPair), hipMemcpyHostToDevice, s));
+    rc = tri_launch_match(b, n_pairs, d_has_mp1, d_has_mp2, only_stereo != 0, check_orientation != 0, b->d_match, b->d_pairs, b->d_npairs, b->d_nmatch, s);
+    if (rc != SD_OK) return rc;
+    b->nPairs = n_pairs; b->dlPairs = n_pairs;
+    return SD_OK;
+}
+
+// LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:208-453) for n_kf keyframes and their neighbour lists
+int sd_batch_create_new_map_points(sd_batch* b, int n_kf, const int32_t* kf_index, const float* kf_Tcw_host, const uint8_t* d_kf_has_mp,
+                                   const int32_t* neigh_offset, const int32_t* neigh_index, const float* neigh_Tcw_host,
+                                   const float* neigh_median_depth, const uint8_t* d_neigh_has_mp, const sd_camera* cam,
+                                   sd_new_map_point** d_new, int32_t** d_nnew, void* stream_)
+{
+    if (!b || n_kf <= 0 || !cam_ok(cam) || !kf_index || !kf_Tcw_host || !neigh_offset)
+        return set_err(SD_ERR_INVALID, "bad create_new_map_points arguments");
+    if (neigh_offset[0] != 0) return set_err(SD_ERR_INVALID, "create_new_map_points: neighbour offsets must start at 0 and ascend");
+    for (int k = 0; k < n_kf; k++) if (neigh_offset[k + 1] < neigh_offset[k]) return set_err(SD_ERR_INVALID, "create_new_map_points: neighbour offsets must start at 0 and ascend");
+    const int nP = neigh_offset[n_kf];
+    if (nP > 0 && (!neigh_index || !neigh_Tcw_host)) return set_err(SD_ERR_INVALID, "bad create_new_map_points arguments");
+    for (int k = 0; k < n_kf; k++) {
+        if (kf_index[k] < 0 || kf_index[k] >= b->maxImages) return set_err(SD_ERR_INVALID, "create_new_map_points: slot out of range");
+        if (!slot_ok(b, kf_index[k])) return set_err(SD_ERR_STATE, "create_new_map_points: slot holds no results");
+        if (!tri_bow_ok(b, kf_index[k])) return set_err(SD_ERR_STATE, "create_new_map_points: sd_batch_compute_bow has not run on these slots");
+    }
+    for (int p = 0; p < nP; p++) {
+        if (neigh_index[p] < 0 || neigh_index[p] >= b->maxImages) return set_err(SD_ERR_INVALID, "create_new_map_points: slot out of range");
+        if (!slot_ok(b, neigh_index[p])) return set_err(SD_ERR_STATE, "create_new_map_points: slot holds no results");
+        if (!tri_bow_ok(b, neigh_index[p])) return set_err(SD_ERR_STATE, "create_new_map_points: sd_batch_compute_bow has not run on these slots");
+    }
+    if (b->plan.kpCap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
+    b->lastStream = s;
+    b->triKfs = 0;
+    if (d_new) *d_new = nullptr;
+    if (d_nnew) *d_nnew = nullptr;
+    const size_t cap = b->plan.kpCap;
+    if (n_kf > b->triKfCap) {
+        SdDevBuf<int> off, nn; SdDevBuf<sd_new_map_point> nw;
+        HIPCHK(off.alloc(((size_t)n_kf + 1) * 4)); HIPCHK(nn.alloc((size_t)n_kf * 4)); HIPCHK(nw.alloc((size_t)n_kf * cap * sizeof(sd_new_map_point)));
+        b->d_triOff = std::move(off); b->d_triNnew = std::move(nn); b->d_triNew = std::move(nw); b->triKfCap = n_kf;
+    }
+    if (nP > b->triTableCap) {
+        SdDevBuf<int> m, pl, np; SdDevBuf<uint8_t> ok; SdDevBuf<float> xw;
+        HIPCHK(m.alloc((size_t)nP * cap * 4)); HIPCHK(pl.alloc((size_t)nP * cap * 8)); HIPCHK(np.alloc((size_t)nP * 4));
+        HIPCHK(ok.alloc((size_t)nP * cap)); HIPCHK(xw.alloc((size_t)nP * cap * 12));
+        b->d_triMatch = std::move(m); b->d_triPairList = std::move(pl); b->d_triNp = std::move(np);
+        b->d_triOk = std::move(ok); b->d_triXw = std::move(xw); b->triTableCap = nP;
+    }
+    HIPCHK(hipMemcpyAsync(b->d_triOff, neigh_offset, ((size_t)n_kf + 1) * 4, hipMemcpyHostToDevice, s));
+    if (nP > 0) {
+        std::vector<SdTriPair>& P = b->hostTriPairs;
+        P.resize(nP);
+        for (int k = 0; k < n_kf; k++)
+            for (int p = neigh_offset[k]; p < neigh_offset[k + 1]; p++) {
+                P[p].img1 = kf_index[k]; P[p].img2 = neigh_index[p]; P[p].row1 = k; P[p].row2 = p;
+                tri_pair_setup(kf_Tcw_host + 16 * (size_t)k, neigh_Tcw_host + 16 * (size_t)p, *cam, neigh_median_depth ? neigh_median_depth + p : nullptr, true, P[p]);
+            }
+        int rc = tri_ensure_pairs(b, nP);
+        if (rc != SD_OK) return rc;
+        HIPCHK(hipMemcpyAsync(b->d_triPairs, P.data(), (size_t)nP * sizeof(SdTriPair), hipMemcpyHostToDevice, s));
+        rc = tri_launch_match(b, nP, d_kf_has_mp, d_neigh_has_mp, 0, 0, b->d_triMatch, b->d_triPairList, b->d_triNp, nullptr, s);   // ORBmatcher(0.6, false), bOnlyStereo = false
+        if (rc != SD_OK) return rc;
+        SdCamera c; memcpy(&c, cam, sizeof(c));
+        const float ratioFactor = 1.5f * (float)b->ex->prm.scaleFactor;
+        HIPCHK(hipMemsetAsync(b->d_triOk, 0, (size_t)nP * cap, s));
+        ProfScope ps(b, s, K_TRI_T);
+        hipLaunchKernelGGL(k_tri_triangulate, dim3((unsigned)((cap + 255) / 256), nP), dim3(256), 0, s, KPUN(b), b->d_kp, b->d_uright, b->d_depth,
+                           b->d_triPairs, b->d_triPairList, b->d_triNp, tri_levels(b), c, ratioFactor, (int)cap, b->d_triOk, b->d_triXw);
+        LAUNCH_CHECK("k_tri_triangulate");
+    }
+    {
+        const size_t lds = cap + 16;
+        ProfScope ps(b, s, K_TRI_R);
+        hipLaunchKernelGGL(k_tri_resolve, dim3(n_kf), dim3(256), lds, s, b->d_count, b->d_triPairs, b->d_triOff, b->d_triMatch, b->d_triOk, b->d_triXw, (int)cap,
+                           b->d_triNew.get(), b->d_triNnew);
+        LAUNCH_CHECK("k_tri_resolve");
+    }
+    b->triKfs = n_kf;
+    if (d_new) *d_new = b->d_triNew;
+    if (d_nnew) *d_nnew = b->d_triNnew;
+    return SD_OK;
+}
+
+int sd_batch_download_new_map_points(sd_batch* b, int kf, sd_new_map_point* out, int cap, int* nnew)
+{
+    if (!b || !nnew) return set_err(SD_ERR_INVALID, "bad download_new_map_points arguments");
+    if (kf < 0 || kf >= b->triKfs) return set_err(SD_ERR_INVALID, "download_new_map_points: no such keyframe in the last sd_batch_create_new_map_points");
+    int rc = sd_batch_sync(b);
+    if (rc != SD_OK) return rc;
+    int n = 0;
+    HIPCHK(hipMemcpy(&n, b->d_triNnew + kf, 4, hipMemcpyDeviceToHost));
+    *nnew = n;
+    if (n > cap) return set_err(SD_ERR_CAPACITY, "new map point buffer too small");
+    if (out && n > 0) HIPCHK(hipMemcpy(out, b->d_triNew + (size_t)kf * b->plan.kpCap, (size_t)n * sizeof(sd_new_map_point), hipMemcpyDeviceToHost));
     return SD_OK;
 }
 

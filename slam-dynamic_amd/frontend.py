@@ -133,6 +133,9 @@ def lib():
         L.sd_batch_download_pose.argtypes = [vp, i, vp, vp, i, C.POINTER(i), C.POINTER(i)]
         L.sd_tracker_set_pose_optimization.argtypes = [vp, i]
         L.sd_tracker_pose_results.argtypes = [vp, vp]
+        L.sd_batch_search_for_triangulation.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, vp]
+        L.sd_batch_create_new_map_points.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
+        L.sd_batch_download_new_map_points.argtypes = [vp, i, vp, i, C.POINTER(i)]
         _lib = L
     return _lib
 
@@ -402,6 +405,50 @@ class Batch:
         check(lib().sd_batch_search_by_bow(self.h, len(ki), _p(ki), _p(fi), C.c_void_p(d_kf_valid or 0), C.c_float(nnratio),
                                            int(checkOrientation), C.c_void_p(stream or 0)))
 
+    # -- LocalMapping::CreateNewMapPoints: ORBmatcher::SearchForTriangulation, triangulation, the neighbour loop
+    def stereo_device(self):
+        """Device pointers of mvuRight / mvDepth: (d_uright, d_depth, cap), both [max_images][cap] f32."""
+        ur, dep = C.c_void_p(), C.c_void_p()
+        cap = C.c_int()
+        check(lib().sd_batch_stereo_device(self.h, C.byref(ur), C.byref(dep), C.byref(cap)))
+        return ur.value, dep.value, cap.value
+
+    def search_for_triangulation(self, kf1_index, kf2_index, Tcw1, Tcw2, cam, d_has_mp1=None, d_has_mp2=None, only_stereo=False,
+                                 checkOrientation=False, stream=None):
+        """ORBmatcher::SearchForTriangulation for independent pairs of slots (compute_bow must have run on them); F12 and the epipole
+        come from the poses (n, 4, 4) and the camera.  Results: download_matches(pair) -> match[idx1] = idx2, vMatchedPairs, nmatches."""
+        c = camera_array(cam)
+        a = np.ascontiguousarray(kf1_index, np.int32).reshape(-1); d = np.ascontiguousarray(kf2_index, np.int32).reshape(-1)
+        T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(-1, 16); T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(-1, 16)
+        if len(d) != len(a) or len(T1) != len(a) or len(T2) != len(a):
+            raise ValueError("search_for_triangulation: one slot and one pose per pair and side")
+        check(lib().sd_batch_search_for_triangulation(self.h, len(a), _p(a), _p(d), _p(T1), _p(T2), _p(c), C.c_void_p(d_has_mp1 or 0),
+                                                      C.c_void_p(d_has_mp2 or 0), int(only_stereo), int(checkOrientation), C.c_void_p(stream or 0)))
+
+    def create_new_map_points(self, kf_index, kf_Tcw, neigh_offset, neigh_index, neigh_Tcw, cam, neigh_median_depth=None, d_kf_has_mp=None,
+                              d_neigh_has_mp=None, stream=None):
+        """The loop body of LocalMapping::CreateNewMapPoints for len(kf_index) keyframes: keyframe k owns neighbours
+        [neigh_offset[k], neigh_offset[k+1]) in GetBestCovisibilityKeyFrames order.  neigh_median_depth None = the stereo / RGB-D baseline
+        rule, else the monocular one.  -> (d_new, d_nnew): device pointers of sd_new_map_point [n_kf][cap] and the counts [n_kf]."""
+        c = camera_array(cam)
+        ki = np.ascontiguousarray(kf_index, np.int32).reshape(-1); off = np.ascontiguousarray(neigh_offset, np.int32).reshape(-1)
+        ni = np.ascontiguousarray(neigh_index, np.int32).reshape(-1)
+        Tk = np.ascontiguousarray(kf_Tcw, np.float32).reshape(-1, 16); Tn = np.ascontiguousarray(neigh_Tcw, np.float32).reshape(-1, 16)
+        md = np.ascontiguousarray(neigh_median_depth, np.float32).reshape(-1) if neigh_median_depth is not None else None
+        if len(off) != len(ki) + 1 or len(Tk) != len(ki) or len(Tn) != len(ni) or (len(off) and off[-1] != len(ni)) or (md is not None and len(md) != len(ni)):
+            raise ValueError("create_new_map_points: offsets, slots and poses do not fit together")
+        d_new, d_nnew = C.c_void_p(), C.c_void_p()
+        check(lib().sd_batch_create_new_map_points(self.h, len(ki), _p(ki), _p(Tk), C.c_void_p(d_kf_has_mp or 0), _p(off), _p(ni), _p(Tn),
+                                                   _p(md) if md is not None else None, C.c_void_p(d_neigh_has_mp or 0), _p(c),
+                                                   C.byref(d_new), C.byref(d_nnew), C.c_void_p(stream or 0)))
+        return d_new.value, d_nnew.value
+
+    def download_new_map_points(self, kf):
+        """The points keyframe `kf` of the last create_new_map_points created, in creation order (NEW_MAP_POINT_DTYPE)."""
+        out = np.zeros(self.cap, NEW_MAP_POINT_DTYPE); n = C.c_int()
+        check(lib().sd_batch_download_new_map_points(self.h, kf, _p(out), self.cap, C.byref(n)))
+        return out[:n.value].copy()
+
     # -- Tracking::TrackHomo model fit (H / F from the projection matcher's point pairs)
     def estimate_motion(self, stream=None):
         check(lib().sd_batch_estimate_motion(self.h, C.c_void_p(stream or 0)))
@@ -529,6 +576,7 @@ class Batch:
         return out
 
 
+NEW_MAP_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("xw", "<f4", (3,))])     # sd_new_map_point
 MAXB = 64             # SD_MAX_BOXES (include/sd_frontend.h)
 CLOUD_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1")])     # sd_cloud_point
 SENSOR_MONOCULAR, SENSOR_STEREO, SENSOR_RGBD = 0, 1, 2
