@@ -300,6 +300,42 @@ int sd_batch_create_new_map_points(sd_batch* b, int n_kf, const int32_t* kf_inde
                                    const sd_camera* cam, sd_new_map_point** d_new, int32_t** d_nnew, void* stream);
 int sd_batch_download_new_map_points(sd_batch* b, int kf, sd_new_map_point* out, int cap, int* nnew);
 
+/* ---- LocalMapping::SearchInNeighbors (src/LocalMapping.cc:455-535) ----
+ * The per-candidate search of ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:982-1106) for n_jobs calls at once; the tail
+ * (:1108-1128: Replace / AddObservation / AddMapPoint) stays with the caller that owns the map, who walks the sd_fuse_hit records.
+ * Job j = Fuse(slot kf_index[j], entries [cand_offset[j], cand_offset[j+1]) of d_cand_point, th) with pose Tcw_host[j] (row-major 4x4);
+ * sd_batch_assign_grid must have run on the slot since it was last extracted (SD_ERR_STATE otherwise).  An entry is an index into
+ * d_points / d_point_desc (n_points records; sd_map_point as for sd_batch_search_local_map, `flags` ignored) or -1 where the reference
+ * `continue`s at :1003-1007 (NULL, isBad(), IsInKeyFrame(pKF)).  Many jobs may name the same point; the entries of ONE job must be
+ * distinct points (not checked).  d_kf_state (nullable = every feature empty, [n_jobs][cap] u8): 0 = GetMapPoint(idx) == NULL, 1 = the
+ * feature holds a point that is not bad, 2 = it holds a bad point.  n_jobs is not bounded by max_images (at most 65535 per call).
+ * Every job sees the map as given: a Replace the caller's tail performs for job j is not seen by job j+1 of the same call.
+ * Outputs (library-owned device memory, valid until the next call): d_best[e] = (bestIdx, bestDist) per entry, (-1, 256) when the point
+ * was rejected or no feature passed; d_hits at cand_offset[j] = the entries of job j with bestDist <= TH_LOW in entry order: cand =
+ * position in the job's list, idx = bestIdx, dist = bestDist, action = what the tail meets at idx: SD_FUSE_MEET_KF (state 1),
+ * SD_FUSE_MEET_BAD (state 2: counted, nothing done), SD_FUSE_ADD (state 0, the job's first hit on idx) or SD_FUSE_MEET_CANDIDATE (state
+ * 0, a later hit; other = `cand` of the entry that got SD_FUSE_ADD, -1 for every other action); d_nfused[j] = the return value.
+ * Errors: SD_ERR_INVALID for negative or descending offsets, cand_offset[0] != 0, th <= 0, a slot out of range, NULL tables with
+ * n_jobs > 0.  The entries live in device memory, so one outside [-1, n_points) is found by the kernel: it is searched as -1, nothing
+ * is read out of range, and the next sd_batch_download_fuse returns SD_ERR_INVALID. */
+typedef struct sd_fuse_hit { int32_t cand, idx, dist, action, other; } sd_fuse_hit;   /* 20 bytes */
+enum { SD_FUSE_ADD = 1, SD_FUSE_MEET_KF = 2, SD_FUSE_MEET_BAD = 3, SD_FUSE_MEET_CANDIDATE = 4 };
+int sd_batch_fuse(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Tcw_host, const int32_t* cand_offset,
+                  const int32_t* d_cand_point, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
+                  const uint8_t* d_kf_state, const sd_camera* cam, float th, int32_t** d_best, sd_fuse_hit** d_hits,
+                  int32_t** d_nfused, void* stream);
+/* best [n][2] (nullable), hits (nullable) with room for cap_entries records, n_entries = the job's entry count, nfused = its return
+ * value.  SD_ERR_CAPACITY when the job has more than cap_entries entries. */
+int sd_batch_download_fuse(sd_batch* b, int job, int32_t* best, sd_fuse_hit* hits, int cap_entries, int* n_entries, int* nfused);
+/* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307) for n_points points in one launch (the "Update points" loop of
+ * SearchInNeighbors, Replace, CreateNewMapPoints).  Point p owns observations [d_obs_offset[p], d_obs_offset[p+1]) of d_obs_desc (32 B
+ * each, 16-byte aligned) in the order the reference fills vDescriptors: the caller's std::map order, bad keyframes left out.
+ * d_best_obs[p] = BestIdx relative to the point's first observation (the first row whose median distance, sorted[(int)(0.5*(N-1))] of
+ * the full matrix row with its zero diagonal, is strictly smallest) or -1 when it has none; d_desc_out (nullable, [n_points][32])
+ * receives the chosen descriptor and is untouched for -1.  Every pointer is device memory; asynchronous on `stream`. */
+int sd_distinctive_descriptors_device(int n_points, const int32_t* d_obs_offset, const uint8_t* d_obs_desc, int32_t* d_best_obs,
+                                      uint8_t* d_desc_out, void* stream);
+
 /* The model fit of Tracking::TrackHomo (src/Tracking.cc:1026-1075) for every pair of the preceding
  * sd_batch_search_by_projection, from its points_last / points_current: replaces cv::findHomography(points_last,
  * points_current, RANSAC, 3, inliers_H), cv::findFundamentalMat(..., RANSAC, 3, 0.99, inliers_F), the inlier counts

@@ -21,6 +21,7 @@
 #include "k_cloud.h"
 #include "k_pose.h"
 #include "k_triangulate.h"
+#include "k_fuse.h"
 #include "sd_common.h"
 #include "sd_vocab.h"
 
@@ -45,11 +46,11 @@ struct sd_extractor {
     SdParams prm;
 };
 
-enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_TRI_M, K_TRI_T, K_TRI_R, K_COUNT };
+enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_TRI_M, K_TRI_T, K_TRI_R, K_FUSE_S, K_FUSE_R, K_COUNT };
 static const char* kKernelNames[K_COUNT] = {"k_pyr_level0", "k_pyr_level", "k_fast_cells", "k_quadtree", "k_orient",
                                             "k_blur", "k_describe", "k_stereo_match", "k_stereo_filter", "k_rgbd",
                                             "k_grid_cells", "k_unproject", "k_proj_candidates", "k_proj_resolve",
-                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select", "k_tri_match", "k_tri_triangulate", "k_tri_resolve"};
+                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select", "k_tri_match", "k_tri_triangulate", "k_tri_resolve", "k_fuse_search", "k_fuse_resolve"};
 
 #define SD_PT_TW 256
 #define SD_PT_TH 16
@@ -65,6 +66,7 @@ struct sd_batch {
     int maxImages = 0;
     int nExtracted = 0;       // images processed by the last extract
     std::vector<uint8_t> slotValid;   // slot holds frame results (extracted or carried over)
+    std::vector<uint8_t> gridValid;   // sd_batch_assign_grid has run on what the slot holds now (sd_batch_fuse asks)
     SdDevBuf<int2> d_pairIdx;
     int nStereo = 0;
     hipStream_t stream = nullptr;
@@ -126,6 +128,10 @@ struct sd_batch {
     SdDevBuf<int> d_triMatch; SdDevBuf<int> d_triPairList; SdDevBuf<int> d_triNp; SdDevBuf<uint8_t> d_triOk; SdDevBuf<float> d_triXw;
     int triTableCap = 0;
     SdDevBuf<int> d_triOff; SdDevBuf<sd_new_map_point> d_triNew; SdDevBuf<int> d_triNnew; int triKfCap = 0, triKfs = 0;
+    // ORBmatcher::Fuse (k_fuse.h), grown with the largest call seen: job tables (slot, offsets, poses), per-entry results, and the
+    // first-taker table of k_fuse_resolve where [cap] ints do not fit the LDS
+    SdDevBuf<int> d_fuseJobs; SdDevBuf<float> d_fuseT; SdDevBuf<int> d_fuseN; SdDevBuf<int> d_fuseFirst; int fuseJobCap = 0, fuseFirstCap = 0, fuseJobs = 0;
+    SdDevBuf<int2> d_fuseBest; SdDevBuf<SdFuseHit> d_fuseHits; int fuseEntryCap = 0; SdDevBuf<int> d_fuseErr; std::vector<int32_t> fuseOff;
     std::vector<sd_camera> pairCam, hPoseCam; std::vector<int32_t> hPoseMap;
     int nPairs = 0;
     int dlPairs = 0;          // pairs sd_batch_download_matches may read (the tracker also keeps pairs at [n_lanes, 2 * n_lanes))
@@ -408,6 +414,7 @@ static int batch_create_impl(std::unique_ptr<sd_batch>& out, sd_extractor* ex, i
     HIPCHK(b->d_copyPairs.alloc(nI * sizeof(int2)));
     HIPCHK(b->d_pairIdx.alloc(nI * sizeof(int2)));
     b->slotValid.assign(nI, 0);
+    b->gridValid.assign(nI, 0);
     HIPCHK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
     HIPCHK(hipMemcpy(b->d_plan, &D, sizeof(D), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(b->d_cells, P.cells.data(), sizeof(SdCell) * P.cells.size(), hipMemcpyHostToDevice));
@@ -699,7 +706,7 @@ static int extract_impl(sd_batch* b, const uint8_t* d_gray, size_t stride, size_
     }
     LAUNCH_CHECK("k_describe");
     b->nExtracted = n_images;
-    for (int i = 0; i < n_images; i++) b->slotValid[i] = 1;
+    for (int i = 0; i < n_images; i++) { b->slotValid[i] = 1; b->gridValid[i] = 0; }
     return SD_OK;
 }
 
@@ -1029,6 +1036,7 @@ static int assign_grid_impl(sd_batch* b, int n_images, int image_step, const sd_
                            b->d_cellStart, b->plan.kpCap, image_step);
     }
     LAUNCH_CHECK("k_grid_sort");
+    for (int i = 0; i < n_images; i++) b->gridValid[i * image_step] = 1;
     return SD_OK;
 }
 
@@ -1686,6 +1694,135 @@ int sd_batch_download_new_map_points(sd_batch* b, int kf, sd_new_map_point* out,
     return SD_OK;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// LocalMapping::SearchInNeighbors: ORBmatcher::Fuse(pKF, vpMapPoints, th) and MapPoint::ComputeDistinctiveDescriptors (k_fuse.h)
+// ---------------------------------------------------------------------------------------------------------
+// Job tables and per-entry scratch of sd_batch_fuse: they grow with the largest call seen (old ones freed first), as ensure_local_map does
+static int ensure_fuse(sd_batch* b, int n_jobs, int total, bool firstInMemory, hipStream_t s)
+{
+    const size_t cap = b->plan.kpCap;
+    if (!b->d_fuseErr) { HIPCHK(b->d_fuseErr.alloc(4)); HIPCHK(hipMemset(b->d_fuseErr, 0, 4)); }
+    if (n_jobs > b->fuseJobCap || total > b->fuseEntryCap || (firstInMemory && n_jobs > b->fuseFirstCap)) HIPCHK(hipStreamSynchronize(s));
+    if (n_jobs > b->fuseJobCap) {
+        const int want = std::max(n_jobs, 2 * b->fuseJobCap);
+        b->fuseJobCap = 0; b->d_fuseJobs.reset(); b->d_fuseT.reset(); b->d_fuseN.reset();
+        HIPCHK(b->d_fuseJobs.alloc(((size_t)2 * want + 1) * 4)); HIPCHK(b->d_fuseT.alloc((size_t)want * 64)); HIPCHK(b->d_fuseN.alloc((size_t)want * 4));
+        b->fuseJobCap = want;
+    }
+    if (total > b->fuseEntryCap) {
+        const int want = std::max(total, 2 * b->fuseEntryCap);
+        b->fuseEntryCap = 0; b->d_fuseBest.reset(); b->d_fuseHits.reset();
+        HIPCHK(b->d_fuseBest.alloc((size_t)want * sizeof(int2))); HIPCHK(b->d_fuseHits.alloc((size_t)want * sizeof(SdFuseHit)));
+        b->fuseEntryCap = want;
+    }
+    if (firstInMemory && n_jobs > b->fuseFirstCap) {
+        b->fuseFirstCap = 0;
+        HIPCHK(b->d_fuseFirst.alloc((size_t)n_jobs * cap * 4));
+        b->fuseFirstCap = n_jobs;
+    }
+    return SD_OK;
+}
+
+int sd_batch_fuse(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Tcw_host, const int32_t* cand_offset,
+                  const int32_t* d_cand_point, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
+                  const uint8_t* d_kf_state, const sd_camera* cam, float th, int32_t** d_best, sd_fuse_hit** d_hits,
+                  int32_t** d_nfused, void* stream_)
+{
+    static_assert(sizeof(SdFuseHit) == sizeof(sd_fuse_hit) && sizeof(sd_fuse_hit) == 20, "sd_fuse_hit is 20 bytes");
+    if (d_best) *d_best = nullptr;
+    if (d_hits) *d_hits = nullptr;
+    if (d_nfused) *d_nfused = nullptr;
+    if (!b || n_jobs < 0 || n_jobs > 65535 || n_points < 0 || !cam_ok(cam) || !(th > 0) || (n_jobs > 0 && (!kf_index || !Tcw_host || !cand_offset)))
+        return set_err(SD_ERR_INVALID, "bad fuse arguments");
+    b->fuseJobs = 0;
+    if (n_jobs == 0) return SD_OK;
+    if (cand_offset[0] != 0) return set_err(SD_ERR_INVALID, "fuse: candidate offsets must start at 0 and ascend");
+    int maxM = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const int M = cand_offset[j + 1] - cand_offset[j];
+        if (M < 0 || cand_offset[j] < 0) return set_err(SD_ERR_INVALID, "fuse: candidate offsets must start at 0 and ascend");
+        maxM = std::max(maxM, M);
+        if (kf_index[j] < 0 || kf_index[j] >= b->maxImages) return set_err(SD_ERR_INVALID, "fuse: slot out of range");
+    }
+    for (int j = 0; j < n_jobs; j++) {
+        if (!slot_ok(b, kf_index[j])) return set_err(SD_ERR_STATE, "fuse: slot holds no results");
+        if (!b->gridValid[kf_index[j]]) return set_err(SD_ERR_STATE, "fuse: sd_batch_assign_grid has not run on this slot");
+    }
+    const int total = cand_offset[n_jobs];
+    if (total > 0 && (!d_cand_point || !d_points || !d_point_desc || n_points == 0)) return set_err(SD_ERR_INVALID, "fuse: entries but no map points given");
+    const int cap = b->plan.kpCap;
+    if (cap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
+    b->lastStream = s;
+    // the first-taker table of k_fuse_resolve: [cap] ints in LDS while that fits beside the scan, else one row per job in memory
+    const size_t lds = (size_t)cap * 4 + 16;
+    const bool firstInMemory = lds > SD_LDS_MAX_BYTES - 2048;
+    int rc = ensure_fuse(b, n_jobs, total, firstInMemory, s);
+    if (rc != SD_OK) return rc;
+    int* dFrameOf = b->d_fuseJobs;
+    int* dOff = b->d_fuseJobs + n_jobs;
+    b->fuseOff.assign(cand_offset, cand_offset + n_jobs + 1);
+    HIPCHK(hipMemcpyAsync(dFrameOf, kf_index, (size_t)n_jobs * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dOff, cand_offset, ((size_t)n_jobs + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b->d_fuseT, Tcw_host, (size_t)n_jobs * 64, hipMemcpyHostToDevice, s));
+    if (maxM > 0) {
+        SdFuseLevels L;
+        const SdParams& prm = b->ex->prm;
+        for (int l = 0; l < SD_MAX_LEVELS; l++) { const bool in = l < prm.nlevels; L.scale[l] = in ? prm.scale[l] : 1.f; L.invSigma2[l] = in ? prm.invSigma2[l] : 1.f; }
+        L.nlevels = prm.nlevels;
+        ProfScope ps(b, s, K_FUSE_S);
+        hipLaunchKernelGGL(k_fuse_search, dim3((maxM + 3) / 4, n_jobs), dim3(256), 0, s, KPUN(b), b->d_desc, b->d_uright, b->d_sortedIdx, b->d_cellStart,
+                           (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->d_fuseT, b->d_fuseBest.get(),
+                           b->d_fuseErr.get(), L, to_cam(cam), th, cap);
+        LAUNCH_CHECK("k_fuse_search");
+    }
+    {
+        if (!firstInMemory && lds > 64 * 1024) HIPCHK(sd_raise_lds_limit((const void*)k_fuse_resolve, (int)lds));
+        ProfScope ps(b, s, K_FUSE_R);
+        hipLaunchKernelGGL(k_fuse_resolve, dim3(n_jobs), dim3(256), firstInMemory ? 0 : lds, s, b->d_count, dFrameOf, dOff, b->d_fuseBest.get(), d_kf_state, cap,
+                           firstInMemory ? b->d_fuseFirst.get() : nullptr, b->d_fuseHits.get(), b->d_fuseN.get());
+        LAUNCH_CHECK("k_fuse_resolve");
+    }
+    b->fuseJobs = n_jobs;
+    if (d_best) *d_best = (int32_t*)b->d_fuseBest.get();
+    if (d_hits) *d_hits = (sd_fuse_hit*)b->d_fuseHits.get();
+    if (d_nfused) *d_nfused = b->d_fuseN;
+    return SD_OK;
+}
+
+int sd_batch_download_fuse(sd_batch* b, int job, int32_t* best, sd_fuse_hit* hits, int cap_entries, int* n_entries, int* nfused)
+{
+    if (!b || !n_entries || !nfused || cap_entries < 0) return set_err(SD_ERR_INVALID, "bad download_fuse arguments");
+    if (job < 0 || job >= b->fuseJobs) return set_err(SD_ERR_INVALID, "download_fuse: no such job in the last sd_batch_fuse");
+    int rc = sd_batch_sync(b);
+    if (rc != SD_OK) return rc;
+    int err = 0;
+    HIPCHK(hipMemcpy(&err, b->d_fuseErr, 4, hipMemcpyDeviceToHost));
+    if (err) {
+        HIPCHK(hipMemset(b->d_fuseErr, 0, 4));
+        return set_err(SD_ERR_INVALID, "fuse: an entry names a point outside [-1, n_points)");
+    }
+    const int e0 = b->fuseOff[job], n = b->fuseOff[job + 1] - e0;
+    *n_entries = n;
+    int nf = 0;
+    HIPCHK(hipMemcpy(&nf, b->d_fuseN + job, 4, hipMemcpyDeviceToHost));
+    *nfused = nf;
+    if (n > cap_entries) return set_err(SD_ERR_CAPACITY, "fuse result buffers too small");
+    if (best && n > 0) HIPCHK(hipMemcpy(best, b->d_fuseBest + e0, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+    if (hits && nf > 0) HIPCHK(hipMemcpy(hits, b->d_fuseHits + e0, (size_t)nf * sizeof(SdFuseHit), hipMemcpyDeviceToHost));
+    return SD_OK;
+}
+
+int sd_distinctive_descriptors_device(int n_points, const int32_t* d_obs_offset, const uint8_t* d_obs_desc, int32_t* d_best_obs,
+                                      uint8_t* d_desc_out, void* stream_)
+{
+    if (n_points < 0 || (n_points > 0 && (!d_obs_offset || !d_obs_desc || !d_best_obs))) return set_err(SD_ERR_INVALID, "bad distinctive_descriptors arguments");
+    if (n_points == 0) return SD_OK;
+    hipLaunchKernelGGL(k_distinctive, dim3((n_points + 3) / 4), dim3(256), 0, (hipStream_t)stream_, n_points, d_obs_offset, d_obs_desc, d_best_obs, d_desc_out);
+    LAUNCH_CHECK("k_distinctive");
+    return SD_OK;
+}
+
 // The model-fit buffers of sd_batch_estimate_motion (a tracker allocates them at creation)
 static int ensure_motion(sd_batch* b)
 {
@@ -1884,12 +2021,13 @@ int sd_image_bounds(int cols, int rows, const float* K4, const float* dist5, flo
 
 // Frame copy (mLastFrame = Frame(mCurrentFrame), Tracking.cc; Frame.cc:39-63): every per-slot array (frame_arrays) of n (src, dst) slot
 // pairs in one launch; the pairs come from `d_pairs` or, for one pair, as (src0, dst0)
-static int copy_frames_impl(sd_batch* b, int n, const int2* d_pairs, int src0, int dst0, const int32_t* dst, hipStream_t s)
+static int copy_frames_impl(sd_batch* b, int n, const int2* d_pairs, int src0, int dst0, const int32_t* src, const int32_t* dst, hipStream_t s)
 {
     int rc = launch_copy_frames(frame_copy_table(b, b, SD_FRAME_ALL), 8, n, d_pairs, src0, 0, dst0, 0, s);
     if (rc != SD_OK) return rc;
     for (int i = 0; i < n; i++) {
         b->slotValid[dst[i]] = 1;
+        b->gridValid[dst[i]] = b->gridValid[src[i]];             // the grid arrays travel with the frame
         if (!b->bowValid.empty()) b->bowValid[dst[i]] = 0;      // mBowVec / mFeatVec are recomputed on demand (ComputeBoW's `if(mBowVec.empty())`)
     }
     return SD_OK;
@@ -1900,7 +2038,7 @@ int sd_batch_copy_frame(sd_batch* b, int src, int dst, void* stream_)
     if (!b || !slot_ok(b, src) || dst < 0 || dst >= b->maxImages || src == dst) return set_err(SD_ERR_INVALID, "bad copy_frame slots");
     hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
     b->lastStream = s;
-    return copy_frames_impl(b, 1, nullptr, src, dst, &dst, s);
+    return copy_frames_impl(b, 1, nullptr, src, dst, &src, &dst, s);
 }
 
 int sd_batch_copy_frames(sd_batch* b, int n, const int32_t* src, const int32_t* dst, void* stream_)
@@ -1916,7 +2054,7 @@ int sd_batch_copy_frames(sd_batch* b, int n, const int32_t* src, const int32_t* 
         pr[i] = make_int2(src[i], dst[i]);
     }
     HIPCHK(hipMemcpyAsync(b->d_copyPairs, pr.data(), (size_t)n * sizeof(int2), hipMemcpyHostToDevice, s));
-    return copy_frames_impl(b, n, b->d_copyPairs, 0, 0, dst, s);
+    return copy_frames_impl(b, n, b->d_copyPairs, 0, 0, src, dst, s);
 }
 
 int sd_batch_matches_device(sd_batch* b, int32_t** d_match, int32_t** d_pairs, int32_t** d_npairs, int32_t** d_nmatches, int* cap)

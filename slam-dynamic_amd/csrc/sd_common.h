@@ -11,6 +11,7 @@ int sd_set_err(int code, const std::string& msg);        // defined in sd_api.hi
 // Raises the dynamic-LDS limit of `kernel` on the current device to `bytes`: nothing to do at or below the 64 KB default, and the limit only
 // ever grows (workspaces and detectors of different sizes share the kernels).  Defined in sd_api.hip.
 hipError_t sd_raise_lds_limit(const void* kernel, int bytes);
+#define SD_LDS_MAX_BYTES (160 * 1024)      // LDS of one gfx950 workgroup: above it a per-key-point table goes to device memory
 
 // Device memory owned by one object: hipFree on destruction, move-only, read as a plain T* wherever a pointer is expected.
 template <typename T>

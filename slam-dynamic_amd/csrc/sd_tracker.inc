@@ -410,7 +410,7 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
         HIPCHK(hipStreamWaitEvent(s, B.ready, 0));
         TRK(launch_copy_frames(frame_copy_table(bp, b, SD_FRAME_FRONT), 8, S, nullptr, B.next * t->nCur, ipl, 0, ipl, s));
         b->nExtracted = t->nCur; b->nStereo = t->p.sensor == SD_SENSOR_STEREO ? S : 0; b->lastStream = s;
-        for (int l = 0; l < S; l++) b->slotValid[l * ipl] = 1;
+        for (int l = 0; l < S; l++) { b->slotValid[l * ipl] = 1; b->gridValid[l * ipl] = 0; }
         if (++B.next == B.n) { t->blockHead ^= 1; t->blockCount--; }
     } else {
         int nIni = 0;
@@ -428,7 +428,7 @@ int sd_tracker_track(sd_tracker* t, const uint8_t* d_images, size_t stride, size
                 l0 = l1;
             }
             b->nExtracted = S; b->nStereo = 0; b->lastStream = s;
-            for (int l = 0; l < S; l++) b->slotValid[l] = 1;
+            for (int l = 0; l < S; l++) { b->slotValid[l] = 1; b->gridValid[l] = 0; }
         }
     }
     // ---- UndistortKeyPoints, then the stereo / RGB-D association (done ahead by sd_tracker_prefetch for a pool frame)

@@ -136,6 +136,9 @@ def lib():
         L.sd_batch_search_for_triangulation.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, i, vp]
         L.sd_batch_create_new_map_points.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp]
         L.sd_batch_download_new_map_points.argtypes = [vp, i, vp, i, C.POINTER(i)]
+        L.sd_batch_fuse.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, i, vp, vp, f, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
+        L.sd_batch_download_fuse.argtypes = [vp, i, vp, vp, i, C.POINTER(i), C.POINTER(i)]
+        L.sd_distinctive_descriptors_device.argtypes = [i, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -449,6 +452,31 @@ class Batch:
         check(lib().sd_batch_download_new_map_points(self.h, kf, _p(out), self.cap, C.byref(n)))
         return out[:n.value].copy()
 
+    # -- LocalMapping::SearchInNeighbors: the search part of ORBmatcher::Fuse(pKF, vpMapPoints, th)
+    def fuse(self, kf_index, Tcw, cand_offset, d_cand_point, d_points, d_point_desc, cam, th=3.0, d_kf_state=None, stream=None, *, n_points):
+        """Job j = Fuse(slot kf_index[j], entries [cand_offset[j], cand_offset[j+1]) of d_cand_point, th) with pose Tcw[j] (assign_grid must
+        have run on the slot).  An entry indexes the n_points records of d_points (sd_map_point) / d_point_desc, or is -1 for a point the
+        reference skips.  d_kf_state: [n_jobs][cap] u8 (0 empty, 1 holds a point, 2 holds a bad point), None = all empty.
+        -> (d_best, d_hits, d_nfused): device pointers of (bestIdx, bestDist) per entry, sd_fuse_hit per entry slot, the return values."""
+        c = camera_array(cam)
+        ki = np.ascontiguousarray(kf_index, np.int32).reshape(-1); off = np.ascontiguousarray(cand_offset, np.int32).reshape(-1)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 16)
+        if len(off) != len(ki) + 1 or len(T) != len(ki):
+            raise ValueError("fuse: one slot and one pose per job, one offset more than jobs")
+        d_best, d_hits, d_nfused = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().sd_batch_fuse(self.h, len(ki), _p(ki), _p(T), _p(off), C.c_void_p(d_cand_point or 0), C.c_void_p(d_points or 0),
+                                  C.c_void_p(d_point_desc or 0), int(n_points), C.c_void_p(d_kf_state or 0), _p(c), C.c_float(th),
+                                  C.byref(d_best), C.byref(d_hits), C.byref(d_nfused), C.c_void_p(stream or 0)))
+        self._fuse_sizes = np.diff(off)
+        return d_best.value, d_hits.value, d_nfused.value
+
+    def download_fuse(self, job):
+        """Job `job` of the last fuse -> (best (n, 2) i32: bestIdx, bestDist per entry; hits (FUSE_HIT_DTYPE) in entry order; nfused)."""
+        n = int(self._fuse_sizes[job]) if 0 <= job < len(getattr(self, "_fuse_sizes", ())) else 0
+        best = np.zeros((max(n, 1), 2), np.int32); hits = np.zeros(max(n, 1), FUSE_HIT_DTYPE); ne, nf = C.c_int(), C.c_int()
+        check(lib().sd_batch_download_fuse(self.h, job, _p(best), _p(hits), n, C.byref(ne), C.byref(nf)))
+        return best[:ne.value].copy(), hits[:nf.value].copy(), nf.value
+
     # -- Tracking::TrackHomo model fit (H / F from the projection matcher's point pairs)
     def estimate_motion(self, stream=None):
         check(lib().sd_batch_estimate_motion(self.h, C.c_void_p(stream or 0)))
@@ -574,6 +602,30 @@ class Batch:
             check(lib().sd_batch_kernel_times(self.h, i, C.byref(name), C.byref(ms), C.byref(cnt)))
             out[name.value.decode()] = (ms.value, cnt.value)
         return out
+
+
+FUSE_HIT_DTYPE = np.dtype([("cand", "<i4"), ("idx", "<i4"), ("dist", "<i4"), ("action", "<i4"), ("other", "<i4")])     # sd_fuse_hit
+FUSE_ADD, FUSE_MEET_KF, FUSE_MEET_BAD, FUSE_MEET_CANDIDATE = 1, 2, 3, 4
+MAP_POINT_DTYPE = np.dtype([("xw", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"), ("max_distance", "<f4"), ("flags", "<u4")])     # sd_map_point
+
+
+def distinctive_descriptors(obs_offset, d_obs_desc, d_best_obs, d_desc_out=None, n_points=None, stream=None):
+    """MapPoint::ComputeDistinctiveDescriptors for n points in one launch: point p owns observations [obs_offset[p], obs_offset[p+1]) of
+    d_obs_desc (32 B each, vDescriptors order).  obs_offset: a device pointer (int, with n_points) or a host array, which is uploaded
+    through torch; d_best_obs [n] i32 and d_desc_out (optional, [n][32] u8) are device pointers.  -> the uploaded offsets (keep them
+    alive until the launch has run) or None."""
+    keep = None
+    if isinstance(obs_offset, int):
+        if n_points is None:
+            raise ValueError("distinctive_descriptors: a device offset table needs n_points")
+        d_off, n = obs_offset, n_points
+    else:
+        import torch
+        off = np.ascontiguousarray(obs_offset, np.int32).reshape(-1)
+        keep = torch.from_numpy(off).cuda(); d_off, n = keep.data_ptr(), len(off) - 1
+    check(lib().sd_distinctive_descriptors_device(int(n), C.c_void_p(d_off or 0), C.c_void_p(d_obs_desc or 0), C.c_void_p(d_best_obs or 0),
+                                                  C.c_void_p(d_desc_out or 0), C.c_void_p(stream or 0)))
+    return keep
 
 
 NEW_MAP_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("xw", "<f4", (3,))])     # sd_new_map_point
