@@ -4,15 +4,12 @@
 //   k_cvt_gray                         cvtColor in GrabImage*        src/Tracking.cc:175-200,256-269
 //   k_depth_to_f32                     imDepth.convertTo(CV_32F,f)   src/Tracking.cc:271-272
 //   k_hamming_matrix                   ORBmatcher::DescriptorDistance src/ORBmatcher.cc:1804-1820
+// and, further down, the frame grid with the two matchers that search it by projection (k_proj_*, k_local_*): each keeps its own
+// reference logic, what they share with every window matcher (pose and scale helpers, the window, its walk, the best-64) is k_area.h.
 #pragma once
 #include "k_sort.h"
 #include "k_extract.h"
-
-__device__ __forceinline__ int sd_hamming256(const uint4 a0, const uint4 a1, const uint4 b0, const uint4 b1)
-{
-    return __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) +
-           __popc(a1.x ^ b1.x) + __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
-}
+#include "k_area.h"
 
 // Keypoints of BOTH eyes bucketed by integer row (counting sort in LDS, grid = (frames, 2 eyes)): rowStart[y] .. rowStart[y+1] are
 // the keypoints of that image with (int)y == y.  The order inside a bucket is irrelevant: the matcher takes the lexicographic minimum of
@@ -420,12 +417,7 @@ __global__ void __launch_bounds__(256) k_hamming_matrix(const uint8_t* __restric
 //   k_proj_candidates   ORBmatcher::SearchByProjection, search part   src/ORBmatcher.cc:407-485,1485-1570
 //   k_proj_resolve      ... assignment order, rotation histogram      src/ORBmatcher.cc:487-559,1572-1627
 // =====================================================================================
-#define SD_GRID_COLS 64   // FRAME_GRID_COLS, Frame.h:40
-#define SD_GRID_ROWS 48   // FRAME_GRID_ROWS, Frame.h:39
 #define SD_HISTO 30       // HISTO_LENGTH, ORBmatcher.cc:39
-#define SD_PROJ_K 64      // candidates kept per projected point (one per lane)
-
-struct SdCamera { float fx, fy, cx, cy, mbf, mb, mnMinX, mnMaxX, mnMinY, mnMaxY; };
 
 // cell id = posX*48 + posY, or -1 when the keypoint falls outside the 64x48 grid.  The reference's
 // per-cell index lists are ordered by keypoint index, so (cell id, index) is the visiting order of
@@ -436,8 +428,8 @@ __global__ void __launch_bounds__(256) k_grid_cells(const sd_keypoint* __restric
     const int img = blockIdx.y * imgStep, i = blockIdx.x * 256 + threadIdx.x;
     if (i >= count[img]) return;
     const sd_keypoint k = kp[(size_t)img * cap + i];
-    const float wInv = (float)SD_GRID_COLS / (cam.mnMaxX - cam.mnMinX);
-    const float hInv = (float)SD_GRID_ROWS / (cam.mnMaxY - cam.mnMinY);
+    float wInv, hInv;
+    sd_grid_inv(cam, wInv, hInv);
     const int px = (int)roundf((k.x - cam.mnMinX) * wInv), py = (int)roundf((k.y - cam.mnMinY) * hInv);
     const bool in = !(px < 0 || px >= SD_GRID_COLS || py < 0 || py >= SD_GRID_ROWS);
     cellOf[(size_t)img * cap + i] = (short)(in ? px * SD_GRID_ROWS + py : -1);
@@ -447,7 +439,6 @@ __global__ void __launch_bounds__(256) k_grid_cells(const sd_keypoint* __restric
 // reference's push_back order), + the start of every cell (cellStart[3072] = number of in-grid keypoints).
 // One workgroup per image: LDS histogram -> exclusive scan -> scatter -> per-cell insertion sort (cells hold
 // ~0.7 keypoints on average, so the sort is a handful of compares).
-#define SD_GRID_CELLS (SD_GRID_COLS * SD_GRID_ROWS)
 __global__ void __launch_bounds__(256) k_grid_sort(const short* __restrict__ cellOf, const int* __restrict__ count,
                                                    unsigned short* __restrict__ sortedIdx,
                                                    unsigned short* __restrict__ cellStart, int cap, int imgStep)
@@ -499,16 +490,6 @@ __global__ void __launch_bounds__(256) k_grid_sort(const short* __restrict__ cel
     for (int c = tid; c <= SD_GRID_CELLS; c += 256) cellStart[(size_t)img * (SD_GRID_CELLS + 8) + c] = (unsigned short)start[c];
 }
 
-__device__ __forceinline__ void sd_mat3_mul_add(const float* __restrict__ T /*row-major 4x4*/, float x, float y, float z,
-                                                float& ox, float& oy, float& oz)
-{
-    // t = (a0*b0 + a1*b1) + a2*b2 ; d = t + c   (f32, left to right, no contraction)
-    float s;
-    s = T[0] * x + T[1] * y; s = s + T[2] * z; ox = s + T[3];
-    s = T[4] * x + T[5] * y; s = s + T[6] * z; oy = s + T[7];
-    s = T[8] * x + T[9] * y; s = s + T[10] * z; oz = s + T[11];
-}
-
 __global__ void __launch_bounds__(256) k_unproject(const sd_keypoint* __restrict__ kp, const int* __restrict__ count,
                                                    const float* __restrict__ depth, const float* __restrict__ Twc,
                                                    float* __restrict__ xw, uint8_t* __restrict__ flags, SdCamera cam,
@@ -530,39 +511,6 @@ __global__ void __launch_bounds__(256) k_unproject(const sd_keypoint* __restrict
     }
     xw[3 * o] = X; xw[3 * o + 1] = Y; xw[3 * o + 2] = Z;
     flags[o] = f;
-}
-
-// wave-wide ascending bitonic sort of one 64-bit key per lane
-// (keys occupy lanes 0 .. n-1, the other lanes hold the maximum: a network over the first 2^ceil(log2 n) lanes suffices)
-__device__ __forceinline__ unsigned long long sd_wave_sort64(unsigned long long key, int lane, int n = 64)
-{
-    int m = 2;
-    while (m < n) m <<= 1;
-    for (int k = 2; k <= m && n > 1; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)key, j, 64);
-            const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), j, 64);
-            const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-            const bool takeMin = (((lane & k) == 0) == ((lane & j) == 0));
-            key = takeMin ? (key < other ? key : other) : (key > other ? key : other);
-        }
-    return key;
-}
-// merge two ascending 64-key sequences held one per lane, keep the 64 smallest (ascending)
-__device__ __forceinline__ unsigned long long sd_wave_merge_low64(unsigned long long a, unsigned long long b, int lane)
-{
-    const unsigned lo = (unsigned)__shfl((int)(unsigned)b, 63 - lane, 64);
-    const unsigned hi = (unsigned)__shfl((int)(unsigned)(b >> 32), 63 - lane, 64);
-    const unsigned long long br = ((unsigned long long)hi << 32) | lo;
-    unsigned long long key = a < br ? a : br;                 // bitonic: the 64 smallest of both
-#pragma unroll
-    for (int j = 32; j > 0; j >>= 1) {
-        const unsigned l2 = (unsigned)__shfl_xor((int)(unsigned)key, j, 64);
-        const unsigned h2 = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), j, 64);
-        const unsigned long long other = ((unsigned long long)h2 << 32) | l2;
-        key = ((lane & j) == 0) ? (key < other ? key : other) : (key > other ? key : other);
-    }
-    return key;
 }
 
 // Phase A.  Projects every Last-frame map point, scans the Current frame's keypoints for the members of
@@ -595,8 +543,6 @@ __device__ __forceinline__ int sd_proj_point(const SdProjArgs& A, int pair, int 
     const int imgC = A.pairIdx[pair].x, imgL = A.pairIdx[pair].y;
     const int cap = P.kpCap;
     const size_t oL = (size_t)imgL * cap + (live ? i : 0);
-    int n = 0;
-    tooWide = false;
     bool ok = live && (A.flags[oL] & 1) != 0;
     float u = 0.f, v = 0.f, invzc = 0.f, radius = 0.f;
     int minLevel = -1, maxLevel = -1;
@@ -614,12 +560,9 @@ __device__ __forceinline__ int sd_proj_point(const SdProjArgs& A, int pair, int 
         v = cam.fy * yc * invzc + cam.cy;
         if (u < cam.mnMinX || u > cam.mnMaxX) ok = false;
         if (v < cam.mnMinY || v > cam.mnMaxY) ok = false;
-        // bForward / bBackward (ORBmatcher.cc:1497-1510): tlc = Rlw*twc + tlw, twc = -Rcw^T * tcw
-        float twx, twy, twz, s_;
-        s_ = (-T[0]) * T[3] + (-T[4]) * T[7]; twx = s_ + (-T[8]) * T[11];
-        s_ = (-T[1]) * T[3] + (-T[5]) * T[7]; twy = s_ + (-T[9]) * T[11];
-        s_ = (-T[2]) * T[3] + (-T[6]) * T[7]; twz = s_ + (-T[10]) * T[11];
-        float lx, ly, lz;
+        // bForward / bBackward (ORBmatcher.cc:1497-1510): tlc = Rlw*twc + tlw
+        float twx, twy, twz, lx, ly, lz;
+        sd_cam_centre(T, twx, twy, twz);
         sd_mat3_mul_add(Tl, twx, twy, twz, lx, ly, lz);
         const bool bForward = lz > cam.mb && !A.bMono, bBackward = -lz > cam.mb && !A.bMono;
         radius = A.th * __shfl(scaleOfLane, nLastOctave, 64);         // lane l holds scale[l]: no load chained behind the octave
@@ -627,67 +570,30 @@ __device__ __forceinline__ int sd_proj_point(const SdProjArgs& A, int pair, int 
         else if (bBackward) { minLevel = 0; maxLevel = nLastOctave; }
         else { minLevel = nLastOctave - 1; maxLevel = nLastOctave + 1; }
     }
-    const float wInv = (float)SD_GRID_COLS / (cam.mnMaxX - cam.mnMinX);
-    const float hInv = (float)SD_GRID_ROWS / (cam.mnMaxY - cam.mnMinY);
-    const int nMinCellX = max(0, (int)floorf((u - cam.mnMinX - radius) * wInv));
-    const int nMaxCellX = min(SD_GRID_COLS - 1, (int)ceilf((u - cam.mnMinX + radius) * wInv));
-    const int nMinCellY = max(0, (int)floorf((v - cam.mnMinY - radius) * hInv));
-    const int nMaxCellY = min(SD_GRID_ROWS - 1, (int)ceilf((v - cam.mnMinY + radius) * hInv));
-    if (nMinCellX >= SD_GRID_COLS || nMaxCellX < 0 || nMinCellY >= SD_GRID_ROWS || nMaxCellY < 0) ok = false;
+    const SdAreaWindow W = sd_area_window(cam, u, v, radius);
+    if (W.empty) ok = false;
     const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
     const uint4* dl = (const uint4*)(A.dmp + oL * 32);
     const uint4 l0 = dl[0], l1 = dl[1];
-    const sd_keypoint* kC = A.kp + (size_t)imgC * cap;
-    const short* cellC = A.cellOf + (size_t)imgC * cap;
-    const float* urC = A.uRight + (size_t)imgC * cap;
-    const uint8_t* dC = A.desc + (size_t)imgC * cap * 32;
+    const SdImageArrays C = sd_image_arrays(A.kp, A.cellOf, A.uRight, A.desc, A.sortedIdx, A.cellStart, imgC, cap);
     const float ur = u - cam.mbf * invzc;
-    const unsigned short* sorted = A.sortedIdx + (size_t)imgC * cap;
-    const unsigned short* cs = A.cellStart + (size_t)imgC * (SD_GRID_CELLS + 8);
-    // GetFeaturesInArea visits cells ix-major / iy-minor: cells (ix, minY..maxY) are one contiguous run of the sorted list.
-    // Group lane j < nCols fetches the run of column ix = nMinCellX + j; a group prefix sum turns the runs into one flat range
-    // so that GW candidates are tested per step.
-    int nColsA = ok ? nMaxCellX - nMinCellX + 1 : 0;
-    if (nColsA > GW) { tooWide = true; nColsA = 0; }
-    int runS = 0, runN = 0;
-    if (gl < nColsA) {
-        const int ix = nMinCellX + gl;
-        runS = cs[ix * SD_GRID_ROWS + nMinCellY];
-        runN = cs[ix * SD_GRID_ROWS + nMaxCellY + 1] - runS;
-    }
-    int incl = runN;
-#pragma unroll
-    for (int o = 1; o < GW; o <<= 1) { const int t = __shfl_up(incl, o, GW); if (gl >= o) incl += t; }
-    const int total = __shfl(incl, GW - 1, GW);
-    const int excl = incl - runN;
-    int colsU = nColsA;                                            // wave-uniform bounds
-#pragma unroll
-    for (int o = GW; o < 64; o <<= 1) colsU = max(colsU, __shfl_xor(colsU, o, 64));
-    colsU = __builtin_amdgcn_readfirstlane(colsU);
-    // GW == 64 (the whole wave on one point): more than 64 hits are possible (wide windows over dense key points); the 64 SMALLEST keys are
-    // kept by a running merge, so that a truncated list is the true head of the full one (k_proj_resolve says so if it ever runs out)
-    unsigned long long best = ~0ull;
-    int nbuf = 0;
-    for (int base = 0; __any(base < total); base += GW) {
-        const int t = base + gl;
+    const SdAreaWalk<GW> walk(C, W, ok, gl);
+    tooWide = walk.tooWide;
+    // GW == 64 (the whole wave on one point): wide windows over dense key points hold more than 64 hits; k_proj_resolve says so if the kept 64 run out
+    SdBest64 top;
+    int n = 0;                                                     // GW < 64: the group's hits, compacted into keys[]
+    for (int base = 0; __any(base < walk.total); base += GW) {
         bool hit = false;
         unsigned long long key = 0;
-        // owner column of flat index t: the last group lane whose exclusive prefix is <= t
-        int col = 0;
-        for (int j = 1; j < colsU; j++) {
-            const int ej = __shfl(excl, j, GW);
-            if (j < nColsA && ej <= t) col = j;
-        }
-        const int cS = __shfl(runS, col, GW), cE = __shfl(excl, col, GW);
-        if (t < total) {
+        const int i2 = walk.member(base + gl);
+        if (i2 >= 0) {
             // everything a candidate needs is requested as soon as its index is known (one round trip, not one per test)
-            const int i2 = sorted[cS + (t - cE)];
-            const sd_keypoint* kq = kC + i2;
+            const sd_keypoint* kq = C.kp + i2;
             const float kx = kq->x, ky = kq->y;
             const int koct = kq->octave;
-            const float r2 = urC[i2];
-            const int cellKey = cellC[i2];
-            const uint4* dr = (const uint4*)(dC + (size_t)i2 * 32);
+            const float r2 = C.uRight[i2];
+            const int cellKey = C.cellOf[i2];
+            const uint4* dr = (const uint4*)(C.desc + (size_t)i2 * 32);
             const uint4 d0 = dr[0], d1 = dr[1];
             bool lv = true;
             if (bCheckLevels) {
@@ -703,22 +609,9 @@ __device__ __forceinline__ int sd_proj_point(const SdProjArgs& A, int pair, int 
                 key = ((unsigned long long)dist << 32) | ((unsigned long long)cellKey << 16) | (unsigned)i2;
             }
         }
-        const unsigned long long mAll = __ballot(hit);
-        const unsigned long long m = GW == 64 ? mAll : (mAll >> gshift) & ((1ull << (GW & 63)) - 1ull);
-        if (GW == 64) {
-            const int h = __popcll(m);
-            if (nbuf + h > 64) {                       // flush the waiting keys into the running best-64
-                __builtin_amdgcn_wave_barrier();
-                unsigned long long kb = gl < nbuf ? keys[gl] : ~0ull;
-                kb = sd_wave_sort64(kb, gl, nbuf);
-                best = sd_wave_merge_low64(best, kb, gl);
-                nbuf = 0;
-                __builtin_amdgcn_wave_barrier();
-            }
-            if (hit) keys[nbuf + __popcll(m & ((1ull << gl) - 1ull))] = key;
-            nbuf += h;
-            n += h;
-        } else {
+        if constexpr (GW == 64) top.push(keys, gl, hit, key);
+        else {
+            const unsigned long long m = (__ballot(hit) >> gshift) & ((1ull << GW) - 1ull);
             if (hit) {
                 const int pos = n + __popcll(m & ((1ull << gl) - 1ull));
                 if (pos < GW) keys[pos] = key;
@@ -726,37 +619,20 @@ __device__ __forceinline__ int sd_proj_point(const SdProjArgs& A, int pair, int 
             n += __popcll(m);
         }
     }
-    if (GW == 64) {
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xC07F);
-        unsigned long long kb = gl < nbuf ? keys[gl] : ~0ull;
-        kb = sd_wave_sort64(kb, gl, nbuf);
-        keyOut = sd_wave_merge_low64(best, kb, gl);
-        return n;
+    if constexpr (GW == 64) {
+        keyOut = top.finish(keys, gl);
+        return top.n;
     }
     __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0): this wave's LDS writes are done
-    // group-wide bitonic sort of <= GW keys (one per lane), ascending.  The keys sit in lanes 0 .. n-1 (the rest hold the
-    // maximum), so a network over the first m = 2^ceil(log2 n) lanes is enough: windows hold few candidates, which makes this
-    // 3-10 compare-exchange stages instead of 21.
+    __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0): this wave's LDS writes are done (why: SdBest64, k_area.h)
+    // group-wide sort of <= GW keys, one per lane: windows hold few candidates, so the network over the first 2^ceil(log2 n) lanes
+    // (n = the wave's largest group count, made uniform) is 3-10 compare-exchange stages instead of 21
     const int nk = min(n, GW);
     unsigned long long key = gl < nk ? keys[gl] : ~0ull;
     int mU = nk;
 #pragma unroll
     for (int o = GW; o < 64; o <<= 1) mU = max(mU, __shfl_xor(mU, o, 64));
-    mU = __builtin_amdgcn_readfirstlane(mU);
-    int m2 = 2;
-    while (m2 < mU) m2 <<= 1;
-    for (int k = 2; k <= m2 && mU > 1; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)key, j, 64);
-            const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)(key >> 32), j, 64);
-            const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-            const bool up = ((gl & k) == 0);
-            const bool lower = ((gl & j) == 0);
-            const bool takeMin = (up == lower);
-            key = takeMin ? (key < other ? key : other) : (key > other ? key : other);
-        }
+    key = sd_wave_sort64(key, gl, __builtin_amdgcn_readfirstlane(mU));
     keyOut = key;
     return n;
 }
@@ -959,12 +835,7 @@ __global__ void __launch_bounds__(64) k_proj_resolve(
 //                       ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>&, th)   ORBmatcher.cc:45-98
 //   k_local_resolve     ... best / second best in assignment order, ratio test            ORBmatcher.cc:99-129
 // =====================================================================================
-struct SdMapPoint { float xw[3]; float normal[3]; float minDistance, maxDistance; unsigned flags; };     // sd_map_point
 struct SdTrack { float projX, projY, projXR, viewCos; int level; int inView; };                          // sd_track_info
-
-// std::log(float), taken correctly rounded (the oracle's logf_cr)
-__device__ __forceinline__ float sd_logf_cr(float x) { return (float)log((double)x); }
-
 
 // One wave per local map point.  cand[m][k] = (dist << 16 | keypoint index) of the SD_PROJ_K nearest members of
 // GetFeaturesInArea (all distances: the second best may exceed TH_HIGH) ordered by (distance, visiting order);
@@ -985,92 +856,53 @@ __global__ void __launch_bounds__(256) k_local_candidates(
     const int ml = blockIdx.x * 4 + wv;
     if (ml >= M) return;
     const int m = m0 + ml;
-    const int img = frameOf[f];
-    const int cap = P.kpCap;
     const float* T = Tcw + (size_t)f * 16;
     const SdMapPoint mp = mps[m];
     // ---- Frame::isInFrustum
     SdTrack t; t.projX = t.projY = t.projXR = t.viewCos = 0.f; t.level = 0; t.inView = 0;
     bool ok = (mp.flags & 1u) != 0;
-    float invz = 0.f;
     if (ok) {
         float xc, yc, zc;
         sd_mat3_mul_add(T, mp.xw[0], mp.xw[1], mp.xw[2], xc, yc, zc);
         if (zc < 0.0f) ok = false;
-        invz = 1.0f / zc;
+        const float invz = 1.0f / zc;
         const float u = cam.fx * xc * invz + cam.cx;
         const float v = cam.fy * yc * invz + cam.cy;
         if (u < cam.mnMinX || u > cam.mnMaxX) ok = false;
         if (v < cam.mnMinY || v > cam.mnMaxY) ok = false;
-        // mOw = -mRcw.t()*mtcw (Frame.cc:667-674)
-        float ox, oy, oz, s;
-        s = (-T[0]) * T[3] + (-T[4]) * T[7]; ox = s + (-T[8]) * T[11];
-        s = (-T[1]) * T[3] + (-T[5]) * T[7]; oy = s + (-T[9]) * T[11];
-        s = (-T[2]) * T[3] + (-T[6]) * T[7]; oz = s + (-T[10]) * T[11];
-        const float px = mp.xw[0] - ox, py = mp.xw[1] - oy, pz = mp.xw[2] - oz;
-        double s2 = (double)px * (double)px; s2 += (double)py * (double)py; s2 += (double)pz * (double)pz;
-        const float dist = (float)sqrt(s2);
-        if (dist < 0.8f * mp.minDistance || dist > 1.2f * mp.maxDistance) ok = false;
-        double dot = (double)px * (double)mp.normal[0]; dot += (double)py * (double)mp.normal[1]; dot += (double)pz * (double)mp.normal[2];
-        const float viewCos = (float)(dot / (double)dist);
+        float ox, oy, oz;
+        sd_cam_centre(T, ox, oy, oz);
+        const SdPointView w = sd_view_of_point(mp, ox, oy, oz);
+        if (w.dist3D < 0.8f * mp.minDistance || w.dist3D > 1.2f * mp.maxDistance) ok = false;
+        const float viewCos = (float)(w.dot / (double)w.dist3D);
         if (viewCos < viewingCosLimit) ok = false;
         if (ok) {
-            const float ratio = mp.maxDistance / dist;
-            const float logScaleFactor = sd_logf_cr(P.lv[1].scale);
-            int nScale = (int)ceilf(sd_logf_cr(ratio) / logScaleFactor);
-            if (nScale < 0) nScale = 0; else if (nScale >= P.nlevels) nScale = P.nlevels - 1;
-            t.inView = 1; t.projX = u; t.projXR = u - cam.mbf * invz; t.projY = v; t.level = nScale; t.viewCos = viewCos;
+            t.inView = 1; t.projX = u; t.projXR = u - cam.mbf * invz; t.projY = v; t.viewCos = viewCos;
+            t.level = sd_predict_scale(mp.maxDistance, w.dist3D, P.lv[1].scale, P.nlevels);
         }
     }
     if (lane == 0) track[m] = t;
     // ---- candidates
-    unsigned long long best = ~0ull;           // lane k holds the k-th smallest key so far
-    int total_hits = 0;
+    SdBest64 top;                              // top.best: lane k holds the k-th smallest key
     if (ok) {
         float r = (double)t.viewCos > 0.998 ? 2.5f : 4.0f;
         if (th != 1.0f) r *= th;
         const float radius = r * P.lv[t.level].scale;
         const int minLevel = t.level - 1, maxLevel = t.level;
         const float u = t.projX, v = t.projY;
-        const float wInv = (float)SD_GRID_COLS / (cam.mnMaxX - cam.mnMinX);
-        const float hInv = (float)SD_GRID_ROWS / (cam.mnMaxY - cam.mnMinY);
-        const int nMinCellX = max(0, (int)floorf((u - cam.mnMinX - radius) * wInv));
-        const int nMaxCellX = min(SD_GRID_COLS - 1, (int)ceilf((u - cam.mnMinX + radius) * wInv));
-        const int nMinCellY = max(0, (int)floorf((v - cam.mnMinY - radius) * hInv));
-        const int nMaxCellY = min(SD_GRID_ROWS - 1, (int)ceilf((v - cam.mnMinY + radius) * hInv));
-        if (!(nMinCellX >= SD_GRID_COLS || nMaxCellX < 0 || nMinCellY >= SD_GRID_ROWS || nMaxCellY < 0)) {
+        const SdAreaWindow W = sd_area_window(cam, u, v, radius);
+        if (!W.empty) {
             const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
             const uint4* dl = (const uint4*)(mpDesc + (size_t)m * 32);
             const uint4 l0 = dl[0], l1 = dl[1];
-            const sd_keypoint* kC = kp + (size_t)img * cap;
-            const short* cellC = cellOf + (size_t)img * cap;
-            const float* urC = uRight + (size_t)img * cap;
-            const uint8_t* dC = desc + (size_t)img * cap * 32;
-            const unsigned short* sorted = sortedIdx + (size_t)img * cap;
-            const unsigned short* cs = cellStart + (size_t)img * (SD_GRID_CELLS + 8);
-            const int nColsA = nMaxCellX - nMinCellX + 1;
-            int runS = 0, runN = 0;
-            if (lane < nColsA) {
-                const int ix = nMinCellX + lane;
-                runS = cs[ix * SD_GRID_ROWS + nMinCellY];
-                runN = cs[ix * SD_GRID_ROWS + nMaxCellY + 1] - runS;
-            }
-            int incl = runN;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const int tt = __shfl_up(incl, o, 64); if (lane >= o) incl += tt; }
-            const int total = __shfl(incl, 63, 64);
-            const int excl = incl - runN;
-            int nbuf = 0;                          // keys waiting in s_keys[wv]
-            for (int base = 0; base < total; base += 64) {
-                const int tt = base + lane;
+            const SdImageArrays C = sd_image_arrays(kp, cellOf, uRight, desc, sortedIdx, cellStart, frameOf[f], P.kpCap);
+            const SdAreaWalk<64> walk(C, W, true, lane);
+            for (int base = 0; base < walk.total; base += 64) {
                 bool hit = false;
                 unsigned long long key = 0;
-                int col = 0;
-                for (int j = 1; j < nColsA; j++) { const int ej = __shfl(excl, j, 64); if (ej <= tt) col = j; }
-                const int cS = __shfl(runS, col, 64), cE = __shfl(excl, col, 64);
-                if (tt < total) {
-                    const int i2 = sorted[cS + (tt - cE)];
-                    const sd_keypoint k = kC[i2];
+                const int i2 = walk.member(base + lane);
+                if (i2 >= 0) {
+                    const sd_keypoint k = C.kp[i2];
                     bool lv = true;
                     if (bCheckLevels) {
                         if (k.octave < minLevel) lv = false;
@@ -1079,36 +911,24 @@ __global__ void __launch_bounds__(256) k_local_candidates(
                     const float distx = k.x - u, disty = k.y - v;
                     if (lv && fabsf(distx) < radius && fabsf(disty) < radius) {
                         bool rOk = true;
-                        const float r2 = urC[i2];
+                        const float r2 = C.uRight[i2];
                         if (r2 > 0) { const float er = fabsf(t.projXR - r2); if (er > radius) rOk = false; }
                         if (rOk) {
-                            const uint4* dr = (const uint4*)(dC + (size_t)i2 * 32);
+                            const uint4* dr = (const uint4*)(C.desc + (size_t)i2 * 32);
                             const int dist = sd_hamming256(l0, l1, dr[0], dr[1]);
                             hit = true;
-                            key = ((unsigned long long)dist << 32) | ((unsigned long long)cellC[i2] << 16) | (unsigned)i2;
+                            key = ((unsigned long long)dist << 32) | ((unsigned long long)C.cellOf[i2] << 16) | (unsigned)i2;
                         }
                     }
                 }
-                const unsigned long long hm = __ballot(hit);
-                const int h = __popcll(hm);
-                if (nbuf + h > SD_PROJ_K) {        // flush the waiting keys into the running best-64
-                    unsigned long long kb = lane < nbuf ? s_keys[wv][lane] : ~0ull;
-                    kb = sd_wave_sort64(kb, lane, nbuf);
-                    best = sd_wave_merge_low64(best, kb, lane);
-                    nbuf = 0;
-                }
-                if (hit) s_keys[wv][nbuf + __popcll(hm & ((1ull << lane) - 1ull))] = key;
-                nbuf += h;
-                total_hits += h;
+                top.push(s_keys[wv], lane, hit, key);
             }
-            unsigned long long kb = lane < nbuf ? s_keys[wv][lane] : ~0ull;
-            kb = sd_wave_sort64(kb, lane, nbuf);
-            best = sd_wave_merge_low64(best, kb, lane);
+            top.finish(s_keys[wv], lane);
         }
     }
-    const int n = total_hits < SD_PROJ_K ? total_hits : SD_PROJ_K;
-    if (lane < n) cand[(size_t)m * SD_PROJ_K + lane] = (unsigned)((best >> 32) << 16) | (unsigned)(best & 0xFFFFu);
-    if (lane == 0) { ncand[m] = (uint8_t)n; overflow[m] = total_hits > SD_PROJ_K; }
+    const int n = top.n < SD_PROJ_K ? top.n : SD_PROJ_K;
+    if (lane < n) cand[(size_t)m * SD_PROJ_K + lane] = (unsigned)((top.best >> 32) << 16) | (unsigned)(top.best & 0xFFFFu);
+    if (lane == 0) { ncand[m] = (uint8_t)n; overflow[m] = top.n > SD_PROJ_K; }
 }
 
 // One wave per frame walks its local map points in order (ORBmatcher.cc:51) in chunks of 64: lane = map point.  With the

@@ -5,14 +5,14 @@
 // The search of one candidate reads nothing another candidate writes (GetFeaturesInArea, the key points and the descriptors of pKF do
 // not change inside Fuse), so an entry is one wave.  The tail mutates the pointer graph and stays with the caller; k_fuse_resolve only
 // says, per hit, what the feature held when the call started and who among the job's entries reached an empty feature first.
-// Numerics: DESIGN.md Q31.
+// The point's view, PredictScale, the GetFeaturesInArea window and its walk are the shared ones of k_area.h; k_fuse_search keeps Fuse's
+// own gates, its chi-square test and the wave minimum.  Numerics: DESIGN.md Q31.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "k_frame.h"
+#include "k_area.h"
 #include "k_bow.h"
 
-struct SdFuseLevels { float scale[SD_MAX_LEVELS], invSigma2[SD_MAX_LEVELS]; int nlevels; };
 struct SdFuseHit { int cand, idx, dist, action, other; };       // sd_fuse_hit
 
 #define SD_FUSE_ERR_POINT 1      // an entry named a point outside [0, n_points)
@@ -23,7 +23,7 @@ __global__ void __launch_bounds__(256) k_fuse_search(
     const unsigned short* __restrict__ sortedIdx, const unsigned short* __restrict__ cellStart, const SdMapPoint* __restrict__ mps,
     const uint8_t* __restrict__ mpDesc, int nPoints, const int* __restrict__ frameOf /*[n_jobs] image slot*/,
     const int* __restrict__ candOff /*[n_jobs+1]*/, const int* __restrict__ candPoint, const float* __restrict__ Tcw,
-    int2* __restrict__ best, int* __restrict__ errFlag, SdFuseLevels L, SdCamera cam, float th, int cap)
+    int2* __restrict__ best, int* __restrict__ errFlag, SdLevelTables L, SdCamera cam, float th, int cap)
 {
     __shared__ float s_scale[SD_MAX_LEVELS], s_invSigma2[SD_MAX_LEVELS];
     if (threadIdx.x < SD_MAX_LEVELS) { s_scale[threadIdx.x] = L.scale[threadIdx.x]; s_invSigma2[threadIdx.x] = L.invSigma2[threadIdx.x]; }
@@ -35,7 +35,6 @@ __global__ void __launch_bounds__(256) k_fuse_search(
     if (el >= M) return;
     const int e = e0 + el;
     const int m = candPoint[e];
-    const int img = frameOf[job];
     const float* T = Tcw + (size_t)job * 16;
     bool ok = m >= 0 && m < nPoints;
     if ((m < -1 || m >= nPoints) && lane == 0) atomicOr(errFlag, SD_FUSE_ERR_POINT);
@@ -52,63 +51,28 @@ __global__ void __launch_bounds__(256) k_fuse_search(
         const float v = cam.fy * y + cam.cy;
         if (!(u >= cam.mnMinX && u < cam.mnMaxX && v >= cam.mnMinY && v < cam.mnMaxY)) ok = false;      // KeyFrame::IsInImage
         const float ur = u - cam.mbf * invz;
-        // Ow = -Rcw.t() * tcw (KeyFrame.cc:51-66)
-        float ox, oy, oz, s;
-        s = (-T[0]) * T[3] + (-T[4]) * T[7]; ox = s + (-T[8]) * T[11];
-        s = (-T[1]) * T[3] + (-T[5]) * T[7]; oy = s + (-T[9]) * T[11];
-        s = (-T[2]) * T[3] + (-T[6]) * T[7]; oz = s + (-T[10]) * T[11];
-        const float px = mp.xw[0] - ox, py = mp.xw[1] - oy, pz = mp.xw[2] - oz;
-        double s2 = (double)px * (double)px; s2 += (double)py * (double)py; s2 += (double)pz * (double)pz;
-        const float dist3D = (float)sqrt(s2);
-        if (dist3D < 0.8f * mp.minDistance || dist3D > 1.2f * mp.maxDistance) ok = false;
-        double dot = (double)px * (double)mp.normal[0]; dot += (double)py * (double)mp.normal[1]; dot += (double)pz * (double)mp.normal[2];
-        if (dot < 0.5 * (double)dist3D) ok = false;
+        float ox, oy, oz;
+        sd_cam_centre(T, ox, oy, oz);
+        const SdPointView w = sd_view_of_point(mp, ox, oy, oz);
+        if (w.dist3D < 0.8f * mp.minDistance || w.dist3D > 1.2f * mp.maxDistance) ok = false;
+        if (w.dot < 0.5 * (double)w.dist3D) ok = false;
         if (ok) {
-            // MapPoint::PredictScale(dist3D, pKF) (MapPoint.cc:399-414)
-            const float ratio = mp.maxDistance / dist3D;
-            const float logScaleFactor = sd_logf_cr(s_scale[1]);
-            int level = (int)ceilf(sd_logf_cr(ratio) / logScaleFactor);
-            if (level < 0) level = 0; else if (level >= L.nlevels) level = L.nlevels - 1;
+            const int level = sd_predict_scale(mp.maxDistance, w.dist3D, s_scale[1], L.nlevels);
             const float radius = th * s_scale[level];
-            // KeyFrame::GetFeaturesInArea (KeyFrame.cc:569-608)
-            const float wInv = (float)SD_GRID_COLS / (cam.mnMaxX - cam.mnMinX);
-            const float hInv = (float)SD_GRID_ROWS / (cam.mnMaxY - cam.mnMinY);
-            const int nMinCellX = max(0, (int)floorf((u - cam.mnMinX - radius) * wInv));
-            const int nMaxCellX = min(SD_GRID_COLS - 1, (int)ceilf((u - cam.mnMinX + radius) * wInv));
-            const int nMinCellY = max(0, (int)floorf((v - cam.mnMinY - radius) * hInv));
-            const int nMaxCellY = min(SD_GRID_ROWS - 1, (int)ceilf((v - cam.mnMinY + radius) * hInv));
-            if (!(nMinCellX >= SD_GRID_COLS || nMaxCellX < 0 || nMinCellY >= SD_GRID_ROWS || nMaxCellY < 0)) {
+            const SdAreaWindow W = sd_area_window(cam, u, v, radius);
+            if (!W.empty) {
                 const uint4* dl = (const uint4*)(mpDesc + (size_t)m * 32);
                 const uint4 l0 = dl[0], l1 = dl[1];
-                const sd_keypoint* kC = kp + (size_t)img * cap;
-                const float* urC = uRight + (size_t)img * cap;
-                const uint8_t* dC = desc + (size_t)img * cap * 32;
-                const unsigned short* sorted = sortedIdx + (size_t)img * cap;
-                const unsigned short* cs = cellStart + (size_t)img * (SD_GRID_CELLS + 8);
-                // the cells of one grid column are consecutive in the sorted list: one run per column, columns ascending = visiting order
-                const int nColsA = nMaxCellX - nMinCellX + 1;
-                int runS = 0, runN = 0;
-                if (lane < nColsA) {
-                    const int ix = nMinCellX + lane;
-                    runS = cs[ix * SD_GRID_ROWS + nMinCellY];
-                    runN = cs[ix * SD_GRID_ROWS + nMaxCellY + 1] - runS;
-                }
-                int incl = runN;
-#pragma unroll
-                for (int o = 1; o < 64; o <<= 1) { const int tt = __shfl_up(incl, o, 64); if (lane >= o) incl += tt; }
-                const int total = __shfl(incl, 63, 64);
-                const int excl = incl - runN;
-                for (int base = 0; base < total; base += 64) {      // a window of more than 64 features takes several passes
+                const SdImageArrays C = sd_image_arrays(kp, nullptr, uRight, desc, sortedIdx, cellStart, frameOf[job], cap);
+                const SdAreaWalk<64> walk(C, W, true, lane);
+                for (int base = 0; base < walk.total; base += 64) {      // a window of more than 64 features takes several passes
                     const int tt = base + lane;
-                    int col = 0;
-                    for (int j = 1; j < nColsA; j++) { const int ej = __shfl(excl, j, 64); if (ej <= tt) col = j; }
-                    const int cS = __shfl(runS, col, 64), cE = __shfl(excl, col, 64);
-                    if (tt < total) {
-                        const int i2 = sorted[cS + (tt - cE)];
-                        const sd_keypoint k = kC[i2];
+                    const int i2 = walk.member(tt);
+                    if (i2 >= 0) {
+                        const sd_keypoint k = C.kp[i2];
                         const float distx = k.x - u, disty = k.y - v;
                         if (fabsf(distx) < radius && fabsf(disty) < radius && k.octave >= level - 1 && k.octave <= level) {
-                            const float kr = urC[i2];
+                            const float kr = C.uRight[i2];
                             const float ex = u - k.x, ey = v - k.y;
                             const float inv = s_invSigma2[k.octave];
                             bool pass;
@@ -121,7 +85,7 @@ __global__ void __launch_bounds__(256) k_fuse_search(
                                 pass = !((double)(e2 * inv) > 5.99);
                             }
                             if (pass) {
-                                const uint4* dr = (const uint4*)(dC + (size_t)i2 * 32);
+                                const uint4* dr = (const uint4*)(C.desc + (size_t)i2 * 32);
                                 const int dist = sd_hamming256(l0, l1, dr[0], dr[1]);
                                 const unsigned key = ((unsigned)dist << 16) | (unsigned)tt;
                                 if (dist < 256 && key < bestKey) { bestKey = key; bestIdx = i2; }

@@ -18,8 +18,6 @@
 #define SD_TRI_REGF 128          // KF2 features of a node that the register path holds (two per lane); larger nodes stream from memory
 #define SD_TRI_SWEEPS 8          // Jacobi sweeps of the 4x4 null vector (Q29)
 
-struct SdTriLevels { float scale[SD_MAX_LEVELS], sigma2[SD_MAX_LEVELS]; };
-
 struct SdTriPair {
     int img1, img2;              // batch slots of KF1 (the current keyframe) and KF2
     int row1, row2;              // rows of the has-map-point tables
@@ -57,7 +55,7 @@ __global__ void __launch_bounds__(SD_TRI_THREADS) k_tri_match(
     const sd_keypoint* __restrict__ kpUn, const uint8_t* __restrict__ desc, const float* __restrict__ uRight, const int* __restrict__ count,
     const unsigned* __restrict__ fvFeat, const int* __restrict__ fvRunStart, const unsigned* __restrict__ fvRunNode,
     const int* __restrict__ meta, const uint8_t* __restrict__ hasMp1 /*nullable [row][cap]*/, const uint8_t* __restrict__ hasMp2,
-    const SdTriPair* __restrict__ pairsIn, SdTriLevels L, int cap, int onlyStereo, int checkOrientation,
+    const SdTriPair* __restrict__ pairsIn, SdLevelTables L, int cap, int onlyStereo, int checkOrientation,
     int* __restrict__ matchOut, int* __restrict__ pairsOut, int* __restrict__ npairsOut, int* __restrict__ nmatchOut /*nullable*/)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -318,7 +316,7 @@ __device__ __forceinline__ bool sd_tri_reproj(const float* T, const float (&X)[3
 // test, xw = the new point.
 __global__ void __launch_bounds__(256) k_tri_triangulate(
     const sd_keypoint* __restrict__ kpUn, const sd_keypoint* __restrict__ kpRaw, const float* __restrict__ uRight, const float* __restrict__ depth,
-    const SdTriPair* __restrict__ pairsIn, const int* __restrict__ pairList, const int* __restrict__ npairs, SdTriLevels L, SdCamera cam,
+    const SdTriPair* __restrict__ pairsIn, const int* __restrict__ pairList, const int* __restrict__ npairs, SdLevelTables L, SdCamera cam,
     float ratioFactor, int cap, uint8_t* __restrict__ okOut, float* __restrict__ xwOut)
 {
     __shared__ float s_scale[SD_MAX_LEVELS], s_sigma2[SD_MAX_LEVELS];

@@ -1542,10 +1542,13 @@ inline void tri_pair_setup(const float* Tcw1, const float* Tcw2, const sd_camera
     P.ex = cam.fx * C2[0] * invz + cam.cx;
     P.ey = cam.fy * C2[1] * invz + cam.cy;
 }
-SdTriLevels tri_levels(const sd_batch* b)
+// the per-level tables of the kernels that take them by value (k_tri_match, k_tri_triangulate, k_fuse_search): 1.f beyond nlevels
+SdLevelTables level_tables(const sd_batch* b)
 {
-    SdTriLevels L;
-    for (int l = 0; l < SD_MAX_LEVELS; l++) { const bool in = l < b->ex->prm.nlevels; L.scale[l] = in ? b->ex->prm.scale[l] : 1.f; L.sigma2[l] = in ? b->ex->prm.sigma2[l] : 1.f; }
+    const SdParams& prm = b->ex->prm;
+    SdLevelTables L;
+    for (int l = 0; l < SD_MAX_LEVELS; l++) { const bool in = l < prm.nlevels; L.scale[l] = in ? prm.scale[l] : 1.f; L.sigma2[l] = in ? prm.sigma2[l] : 1.f; L.invSigma2[l] = in ? prm.invSigma2[l] : 1.f; }
+    L.nlevels = prm.nlevels;
     return L;
 }
 int tri_ensure_pairs(sd_batch* b, int n)
@@ -1564,7 +1567,7 @@ int tri_launch_match(sd_batch* b, int n, const uint8_t* h1, const uint8_t* h2, i
     if (lds > 64 * 1024) HIPCHK(sd_raise_lds_limit((const void*)k_tri_match, (int)lds));
     ProfScope ps(b, s, K_TRI_M);
     hipLaunchKernelGGL(k_tri_match, dim3(n), dim3(SD_TRI_THREADS), lds, s, KPUN(b), b->d_desc, b->d_uright, b->d_count, b->d_fvFeat, b->d_fvRunStart,
-                       b->d_fvRunNode, b->d_bowMeta, h1, h2, b->d_triPairs, tri_levels(b), cap, onlyStereo, checkOrientation, match, pairs, np, nm);
+                       b->d_fvRunNode, b->d_bowMeta, h1, h2, b->d_triPairs, level_tables(b), cap, onlyStereo, checkOrientation, match, pairs, np, nm);
     LAUNCH_CHECK("k_tri_match");
     return SD_OK;
 }
@@ -1664,7 +1667,7 @@ int sd_batch_create_new_map_points(sd_batch* b, int n_kf, const int32_t* kf_inde
         HIPCHK(hipMemsetAsync(b->d_triOk, 0, (size_t)nP * cap, s));
         ProfScope ps(b, s, K_TRI_T);
         hipLaunchKernelGGL(k_tri_triangulate, dim3((unsigned)((cap + 255) / 256), nP), dim3(256), 0, s, KPUN(b), b->d_kp, b->d_uright, b->d_depth,
-                           b->d_triPairs, b->d_triPairList, b->d_triNp, tri_levels(b), c, ratioFactor, (int)cap, b->d_triOk, b->d_triXw);
+                           b->d_triPairs, b->d_triPairList, b->d_triNp, level_tables(b), c, ratioFactor, (int)cap, b->d_triOk, b->d_triXw);
         LAUNCH_CHECK("k_tri_triangulate");
     }
     {
@@ -1766,14 +1769,10 @@ int sd_batch_fuse(sd_batch* b, int n_jobs, const int32_t* kf_index, const float*
     HIPCHK(hipMemcpyAsync(dOff, cand_offset, ((size_t)n_jobs + 1) * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(b->d_fuseT, Tcw_host, (size_t)n_jobs * 64, hipMemcpyHostToDevice, s));
     if (maxM > 0) {
-        SdFuseLevels L;
-        const SdParams& prm = b->ex->prm;
-        for (int l = 0; l < SD_MAX_LEVELS; l++) { const bool in = l < prm.nlevels; L.scale[l] = in ? prm.scale[l] : 1.f; L.invSigma2[l] = in ? prm.invSigma2[l] : 1.f; }
-        L.nlevels = prm.nlevels;
         ProfScope ps(b, s, K_FUSE_S);
         hipLaunchKernelGGL(k_fuse_search, dim3((maxM + 3) / 4, n_jobs), dim3(256), 0, s, KPUN(b), b->d_desc, b->d_uright, b->d_sortedIdx, b->d_cellStart,
                            (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->d_fuseT, b->d_fuseBest.get(),
-                           b->d_fuseErr.get(), L, to_cam(cam), th, cap);
+                           b->d_fuseErr.get(), level_tables(b), to_cam(cam), th, cap);
         LAUNCH_CHECK("k_fuse_search");
     }
     {
