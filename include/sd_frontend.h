@@ -215,6 +215,74 @@ int sd_pose_optimize_device(int n_problems, const int32_t* d_edge_offset, const 
 /* The same from host arrays (edge_offset [n_problems + 1], edges, Tcw in / out, outlier, n_good): uploads, runs, synchronises. */
 int sd_pose_optimize_host(int n_problems, const int32_t* edge_offset, const sd_pose_edge* edges, const sd_camera* cams,
                           float* Tcw, uint8_t* outlier, int32_t* n_good);
+/* ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778) and MapPoint::UpdateNormalAndDepth (src/MapPoint.cc:330-371) ----
+ * Many independent local bundle adjustments in one launch, from the point where the reference calls initializeOptimization():
+ * optimize(5) with Huber kernels, classification (chi2 > 5.991 | 7.815 or non-positive depth -> level 1), optimize(10) over the
+ * level-0 edges without kernels, the same test once more (the erase flag), then normal and distance of the optimised points.
+ * pbStopFlag is not modelled: the caller tests it before the call (DESIGN Q32-Q38).  A problem is three tables:
+ *   keyframes: lLocalKeyFrames first (n_local of them), then lFixedCameras.  Tcw = GetPose() row-major; fx .. mbf as the edges take
+ *              them from pKFi; fixed = (mnId == 0) for a local keyframe, ignored (always fixed) for a fixed camera.  Table order is
+ *              the order of the pose blocks in the reduced camera system.
+ *   points:    xw = GetWorldPos() in lLocalMapPoints order; every point is marginalised.
+ *   edges:     in insertion order (which orders the sums).  kf / point index the problem's own tables; ur < 0 = monocular edge;
+ *              inv_sigma2 = mvInvLevelSigma2[octave]; tag is carried, not read. */
+typedef struct sd_ba_keyframe {
+    float Tcw[16];
+    float fx, fy, cx, cy, mbf;
+    uint8_t fixed;
+    uint8_t reserved[3];
+} sd_ba_keyframe;                                 /* 88 bytes */
+typedef struct sd_ba_edge {
+    int32_t kf, point;
+    float u, v, ur;
+    float inv_sigma2;
+    int32_t tag;
+    int32_t reserved;
+} sd_ba_edge;                                     /* 32 bytes */
+/* Per problem; index 0 = optimize(5), 1 = optimize(10).  iterations: LM iterations run; trials: linear solves tried; rejected: trials
+ * undone; chi2: the active chi2 the round ended with; n_level1 / n_erased: edges the two classifications flagged.
+ * iterations = {-1, -1} marks a problem whose device tables held an index out of range (device entry point only): nothing else of
+ * that problem is written. */
+typedef struct sd_ba_stats {
+    int32_t iterations[2], trials[2], rejected[2];
+    int32_t n_level1, n_erased;
+    double chi2[2];
+} sd_ba_stats;                                    /* 48 bytes */
+#define SD_BA_MAX_LOCAL_KEYFRAMES 64
+#define SD_BA_MAX_FIXED_KEYFRAMES 128
+#define SD_BA_MAX_POINTS_PER_PROBLEM 8192
+#define SD_BA_MAX_EDGES_PER_PROBLEM 65536
+/* Problem p owns keyframes [kf_offset[p], kf_offset[p+1]) (the first n_local[p] local), points [point_offset[p], ..) and edges
+ * [edge_offset[p], ..); the four tables are HOST arrays (n_problems + 1, n_problems, n_problems + 1, n_problems + 1 entries), every
+ * d_ array is device memory.  d_ref_kf [points]: keyframe index of the point's reference keyframe for the distance, -1 = skip.
+ * Out: d_Tcw [keyframes][16]: Converter::toCvMat of the optimised pose in the rows of LOCAL keyframes (rows of fixed cameras are not
+ * written); d_xw_out [points][3]; d_normal [points][3] = mean over the point's edges that were not erased of the unit vector from
+ * the keyframe's centre (zero when none is left); d_dist [points] = |xw - Ow(ref_kf)| or -1; d_level1 / d_erase [edges] u8; d_stats
+ * [n_problems].  A problem without edges is a no-op: poses and points come back as given.  Anything over the caps above, offsets
+ * that decrease or n_local beyond the problem's keyframes: SD_ERR_INVALID before anything is launched.
+ * Stateless with respect to sd_batch.  Asynchronous on `stream`: no host synchronisation, except that the problem table goes through
+ * a ring of 8 library-owned device tables per device (as the cameras of sd_pose_optimize_device) and that the library-owned workspace
+ * is shared by the calls on one device -- a call waits on the device for the previous one, and on the host only when the workspace
+ * has to grow. */
+int sd_local_ba_device(int n_problems, const int32_t* kf_offset, const int32_t* n_local, const int32_t* point_offset,
+                       const int32_t* edge_offset, const sd_ba_keyframe* d_kfs, const float* d_xw, const sd_ba_edge* d_edges,
+                       const int32_t* d_ref_kf, float* d_Tcw, float* d_xw_out, float* d_normal, float* d_dist, uint8_t* d_level1,
+                       uint8_t* d_erase, sd_ba_stats* d_stats, void* stream);
+/* The same from host arrays: checks every edge's and ref_kf's index (out of range: SD_ERR_INVALID, nothing launched), uploads, runs,
+ * synchronises. */
+int sd_local_ba_host(int n_problems, const int32_t* kf_offset, const int32_t* n_local, const int32_t* point_offset,
+                     const int32_t* edge_offset, const sd_ba_keyframe* kfs, const float* xw, const sd_ba_edge* edges,
+                     const int32_t* ref_kf, float* Tcw, float* xw_out, float* normal, float* dist, uint8_t* level1, uint8_t* erase,
+                     sd_ba_stats* stats);
+/* Profiling (a developer switch, off by default, process-wide): with it on, every sd_local_ba_device call also records, per problem, the
+ * device wall-clock time its workgroup spent in each phase, summed over both rounds and all LM trials: 0 index lists, 1 linearisation
+ * (edge records and the gathers of Hpp / Hll), 2 Schur assembly (landmark inverses, S, b_schur), 3 factorisation, 4 the triangular
+ * solves and the landmark back-substitution, 5 update and chi2.  The marks add one barrier each, so a profiled call is slightly slower.
+ * sd_local_ba_profile waits for the last profiled call on the current device and returns its figures in milliseconds
+ * (ms [n_problems][SD_BA_PROFILE_PHASES]); SD_ERR_STATE when there is none, SD_ERR_INVALID when n_problems is not that call's. */
+#define SD_BA_PROFILE_PHASES 6
+int sd_local_ba_set_profiling(int on);
+int sd_local_ba_profile(int n_problems, double* ms);
 /* PoseOptimization of mCurrentFrame after ORBmatcher::SearchByProjection(mCurrentFrame, mLastFrame, ...) for projection pairs
  * pair_index[k] (host, k < n_pairs) of the last sd_batch_search_by_projection: the edges are built on the device from the pair's
  * Current slot (mvKeysUn, mvuRight, octave -> the extractor's mvInvLevelSigma2), its match array (mvpMapPoints) and the Last

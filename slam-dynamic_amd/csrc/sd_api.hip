@@ -22,6 +22,7 @@
 #include "k_pose.h"
 #include "k_triangulate.h"
 #include "k_fuse.h"
+#include "k_ba.h"
 #include "sd_common.h"
 #include "sd_vocab.h"
 
@@ -2157,6 +2158,181 @@ int sd_pose_optimize_host(int n_problems, const int32_t* edge_offset, const sd_p
     HIPCHK(hipMemcpy(Tcw, d_T, (size_t)n_problems * 64, hipMemcpyDeviceToHost));
     if (nE) HIPCHK(hipMemcpy(outlier, d_o, nE, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(n_good, d_g, (size_t)n_problems * 4, hipMemcpyDeviceToHost));
+    return SD_OK;
+}
+
+// ---------------------------------------------------------------- Optimizer::LocalBundleAdjustment (k_ba.h)
+static_assert(sizeof(sd_ba_keyframe) == 88 && sizeof(sd_ba_edge) == 32 && sizeof(sd_ba_stats) == 48, "local BA records");
+static_assert(SD_BA_MAX_LOCAL == SD_BA_MAX_LOCAL_KEYFRAMES && SD_BA_MAX_FIXED == SD_BA_MAX_FIXED_KEYFRAMES &&
+              SD_BA_MAX_POINTS == SD_BA_MAX_POINTS_PER_PROBLEM && SD_BA_MAX_EDGES == SD_BA_MAX_EDGES_PER_PROBLEM, "local BA caps");
+#define SD_BA_RING 8
+namespace {
+struct BaState {
+    SdDevBuf<SdBaProblem> prob[SD_BA_RING]; size_t probCap[SD_BA_RING] = {}; hipEvent_t done[SD_BA_RING] = {}; int next = 0;
+    SdDevBuf<double> wsD; SdDevBuf<int> wsI; size_t capD = 0, capI = 0; hipEvent_t wsDone = nullptr;
+    SdDevBuf<long long> prof; size_t capProf = 0; int profProblems = 0;      // the last profiled call
+};
+BaState* const g_ba = new BaState[SD_POSE_MAX_DEVICES];       // never destroyed, as g_poseCams
+std::mutex g_baMu;
+bool g_baProfiling = false;
+}
+static_assert(SD_BA_PHASES == SD_BA_PROFILE_PHASES, "local BA phases");
+
+// the host-side checks both entry points share; fills the problem table and the workspace sizes
+static int ba_plan(int n, const int32_t* kfOff, const int32_t* nLocal, const int32_t* ptOff, const int32_t* eOff, std::vector<SdBaProblem>& tab,
+                   size_t& needD, size_t& needI, int& maxLocal)
+{
+    if (!kfOff || !nLocal || !ptOff || !eOff) return set_err(SD_ERR_INVALID, "bad local_ba arguments");
+    if (kfOff[0] != 0 || ptOff[0] != 0 || eOff[0] != 0) return set_err(SD_ERR_INVALID, "local_ba offsets must start at 0");
+    tab.resize(n);
+    needD = needI = 0; maxLocal = 0;
+    for (int p = 0; p < n; p++) {
+        const long long nk = (long long)kfOff[p + 1] - kfOff[p], np = (long long)ptOff[p + 1] - ptOff[p], ne = (long long)eOff[p + 1] - eOff[p];
+        if (nk < 0 || np < 0 || ne < 0) return set_err(SD_ERR_INVALID, "local_ba offsets must not decrease");
+        if (nLocal[p] < 0 || nLocal[p] > nk) return set_err(SD_ERR_INVALID, "n_local outside the problem's keyframes");
+        if (nLocal[p] > SD_BA_MAX_LOCAL || nk - nLocal[p] > SD_BA_MAX_FIXED || np > SD_BA_MAX_POINTS || ne > SD_BA_MAX_EDGES)
+            return set_err(SD_ERR_INVALID, "local_ba problem " + std::to_string(p) + " is over the caps (64 local / 128 fixed keyframes, 8192 points, 65536 edges)");
+        SdBaProblem& q = tab[p];
+        q.kf0 = kfOff[p]; q.nKF = (int)nk; q.nLocal = nLocal[p]; q.pt0 = ptOff[p]; q.nPt = (int)np; q.e0 = eOff[p]; q.nE = (int)ne; q.pad = 0;
+        q.wsD = needD; q.wsI = needI;
+        needD += (sd_ba_ws_doubles(nk, nLocal[p], np, ne) + 1) & ~(size_t)1;
+        needI += (sd_ba_ws_ints(nk, nLocal[p], np, ne) + 3) & ~(size_t)3;
+        maxLocal = std::max(maxLocal, nLocal[p]);
+    }
+    if (sd_ba_lds_bytes(maxLocal) > SD_LDS_MAX_BYTES) return set_err(SD_ERR_INVALID, "local_ba reduced system beyond the LDS of a workgroup");
+    return SD_OK;
+}
+
+int sd_local_ba_device(int n_problems, const int32_t* kf_offset, const int32_t* n_local, const int32_t* point_offset,
+                       const int32_t* edge_offset, const sd_ba_keyframe* d_kfs, const float* d_xw, const sd_ba_edge* d_edges,
+                       const int32_t* d_ref_kf, float* d_Tcw, float* d_xw_out, float* d_normal, float* d_dist, uint8_t* d_level1,
+                       uint8_t* d_erase, sd_ba_stats* d_stats, void* stream_)
+{
+    if (n_problems < 0) return set_err(SD_ERR_INVALID, "bad local_ba arguments");
+    if (n_problems == 0) return SD_OK;
+    std::vector<SdBaProblem> tab;
+    size_t needD = 0, needI = 0;
+    int maxLocal = 0;
+    int rc = ba_plan(n_problems, kf_offset, n_local, point_offset, edge_offset, tab, needD, needI, maxLocal);
+    if (rc != SD_OK) return rc;
+    const bool anyKf = kf_offset[n_problems] > 0, anyPt = point_offset[n_problems] > 0, anyE = edge_offset[n_problems] > 0;
+    if (!d_stats || (anyKf && (!d_kfs || !d_Tcw)) || (anyPt && (!d_xw || !d_ref_kf || !d_xw_out || !d_normal || !d_dist)) ||
+        (anyE && (!d_edges || !d_level1 || !d_erase)))
+        return set_err(SD_ERR_INVALID, "bad local_ba arguments");
+    hipStream_t s = (hipStream_t)stream_;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the local_ba tables");
+    std::lock_guard<std::mutex> lk(g_baMu);
+    BaState& B = g_ba[dev];
+    const int k = B.next;
+    if (B.done[k]) HIPCHK(hipEventSynchronize(B.done[k]));
+    else HIPCHK(hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
+    if (B.probCap[k] < (size_t)n_problems) {
+        B.probCap[k] = 0;
+        HIPCHK(B.prob[k].alloc((size_t)n_problems * sizeof(SdBaProblem)));
+        B.probCap[k] = (size_t)n_problems;
+    }
+    if (!B.wsDone) HIPCHK(hipEventCreateWithFlags(&B.wsDone, hipEventDisableTiming));
+    else if (B.capD < needD || B.capI < needI) HIPCHK(hipEventSynchronize(B.wsDone));     // growing: the last launch must be done with it
+    else HIPCHK(hipStreamWaitEvent(s, B.wsDone, 0));
+    if (B.capD < needD) { B.capD = 0; HIPCHK(B.wsD.alloc(needD * sizeof(double))); B.capD = needD; }
+    if (B.capI < needI) { B.capI = 0; HIPCHK(B.wsI.alloc(needI * sizeof(int))); B.capI = needI; }
+    HIPCHK(hipMemcpyAsync(B.prob[k], tab.data(), (size_t)n_problems * sizeof(SdBaProblem), hipMemcpyHostToDevice, s));
+    const int lds = (int)sd_ba_lds_bytes(maxLocal);
+    HIPCHK(sd_raise_lds_limit((const void*)k_local_ba, lds));
+    SdBaArgs A;
+    A.prob = B.prob[k]; A.kfs = d_kfs; A.xw = d_xw; A.edges = d_edges; A.refKf = d_ref_kf; A.Tcw = d_Tcw; A.xwOut = d_xw_out; A.normal = d_normal;
+    A.dist = d_dist; A.level1 = d_level1; A.erase = d_erase; A.stats = d_stats; A.wsD = B.wsD; A.wsI = B.wsI; A.prof = nullptr;
+    if (g_baProfiling) {                                       // (the wait on wsDone above also covers the previous call's use of `prof`)
+        const size_t need = (size_t)n_problems * SD_BA_PHASES;
+        if (B.capProf < need) { HIPCHK(hipEventSynchronize(B.wsDone)); B.capProf = 0; HIPCHK(B.prof.alloc(need * sizeof(long long))); B.capProf = need; }
+        HIPCHK(hipMemsetAsync(B.prof, 0, need * sizeof(long long), s));
+        A.prof = B.prof; B.profProblems = n_problems;
+    }
+    hipLaunchKernelGGL(k_local_ba, dim3(n_problems), dim3(SD_BA_THREADS), lds, s, A);
+    LAUNCH_CHECK("k_local_ba");
+    HIPCHK(hipEventRecord(B.done[k], s));
+    HIPCHK(hipEventRecord(B.wsDone, s));
+    B.next = (k + 1) % SD_BA_RING;
+    return SD_OK;
+}
+
+int sd_local_ba_set_profiling(int on)
+{
+    std::lock_guard<std::mutex> lk(g_baMu);
+    g_baProfiling = on != 0;
+    return SD_OK;
+}
+
+int sd_local_ba_profile(int n_problems, double* ms)
+{
+    if (!ms) return set_err(SD_ERR_INVALID, "bad local_ba_profile arguments");
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the local_ba tables");
+    std::lock_guard<std::mutex> lk(g_baMu);
+    BaState& B = g_ba[dev];
+    if (B.profProblems == 0 || !B.wsDone) return set_err(SD_ERR_STATE, "no profiled sd_local_ba_device call on this device");
+    if (n_problems != B.profProblems) return set_err(SD_ERR_INVALID, "n_problems is not that of the last profiled call");
+    HIPCHK(hipEventSynchronize(B.wsDone));
+    std::vector<long long> t((size_t)n_problems * SD_BA_PHASES);
+    HIPCHK(hipMemcpy(t.data(), B.prof, t.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    int khz = 0;
+    HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
+    if (khz <= 0) return set_err(SD_ERR_UNSUPPORTED, "the device reports no wall-clock rate");
+    for (size_t i = 0; i < t.size(); i++) ms[i] = (double)t[i] / (double)khz;
+    return SD_OK;
+}
+
+int sd_local_ba_host(int n_problems, const int32_t* kf_offset, const int32_t* n_local, const int32_t* point_offset,
+                     const int32_t* edge_offset, const sd_ba_keyframe* kfs, const float* xw, const sd_ba_edge* edges,
+                     const int32_t* ref_kf, float* Tcw, float* xw_out, float* normal, float* dist, uint8_t* level1, uint8_t* erase,
+                     sd_ba_stats* stats)
+{
+    if (n_problems < 0) return set_err(SD_ERR_INVALID, "bad local_ba arguments");
+    if (n_problems == 0) return SD_OK;
+    std::vector<SdBaProblem> tab;
+    size_t needD = 0, needI = 0;
+    int maxLocal = 0;
+    int rc = ba_plan(n_problems, kf_offset, n_local, point_offset, edge_offset, tab, needD, needI, maxLocal);
+    if (rc != SD_OK) return rc;
+    const size_t nK = (size_t)kf_offset[n_problems], nP = (size_t)point_offset[n_problems], nE = (size_t)edge_offset[n_problems];
+    if (!stats || (nK && (!kfs || !Tcw)) || (nP && (!xw || !ref_kf || !xw_out || !normal || !dist)) || (nE && (!edges || !level1 || !erase)))
+        return set_err(SD_ERR_INVALID, "bad local_ba arguments");
+    for (int p = 0; p < n_problems; p++) {
+        const SdBaProblem& q = tab[p];
+        for (int i = 0; i < q.nE; i++) {
+            const sd_ba_edge& e = edges[(size_t)q.e0 + i];
+            if (e.kf < 0 || e.kf >= q.nKF || e.point < 0 || e.point >= q.nPt)
+                return set_err(SD_ERR_INVALID, "local_ba problem " + std::to_string(p) + ": edge " + std::to_string(i) + " indexes outside its tables");
+        }
+        for (int i = 0; i < q.nPt; i++)
+            if (ref_kf[(size_t)q.pt0 + i] < -1 || ref_kf[(size_t)q.pt0 + i] >= q.nKF)
+                return set_err(SD_ERR_INVALID, "local_ba problem " + std::to_string(p) + ": ref_kf outside its keyframes");
+    }
+    rc = require_device();
+    if (rc != SD_OK) return rc;
+    SdDevBuf<sd_ba_keyframe> d_k; SdDevBuf<float> d_x, d_T, d_xo, d_n, d_d; SdDevBuf<sd_ba_edge> d_e; SdDevBuf<int32_t> d_r; SdDevBuf<uint8_t> d_l, d_er;
+    SdDevBuf<sd_ba_stats> d_s;
+    const size_t mK = std::max<size_t>(nK, 1), mP = std::max<size_t>(nP, 1), mE = std::max<size_t>(nE, 1);
+    HIPCHK(d_k.alloc(mK * sizeof(sd_ba_keyframe))); HIPCHK(d_T.alloc(mK * 64)); HIPCHK(d_x.alloc(mP * 12)); HIPCHK(d_xo.alloc(mP * 12));
+    HIPCHK(d_n.alloc(mP * 12)); HIPCHK(d_d.alloc(mP * 4)); HIPCHK(d_r.alloc(mP * 4)); HIPCHK(d_e.alloc(mE * sizeof(sd_ba_edge)));
+    HIPCHK(d_l.alloc(mE)); HIPCHK(d_er.alloc(mE)); HIPCHK(d_s.alloc((size_t)n_problems * sizeof(sd_ba_stats)));
+    if (nK) HIPCHK(hipMemcpy(d_k, kfs, nK * sizeof(sd_ba_keyframe), hipMemcpyHostToDevice));
+    if (nP) { HIPCHK(hipMemcpy(d_x, xw, nP * 12, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(d_r, ref_kf, nP * 4, hipMemcpyHostToDevice)); }
+    if (nE) HIPCHK(hipMemcpy(d_e, edges, nE * sizeof(sd_ba_edge), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_T, 0, mK * 64)); HIPCHK(hipMemset(d_l, 0, mE)); HIPCHK(hipMemset(d_er, 0, mE));
+    rc = sd_local_ba_device(n_problems, kf_offset, n_local, point_offset, edge_offset, d_k, d_x, d_e, d_r, d_T, d_xo, d_n, d_d, d_l, d_er, d_s, nullptr);
+    if (rc != SD_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    if (nK) HIPCHK(hipMemcpy(Tcw, d_T, nK * 64, hipMemcpyDeviceToHost));
+    if (nP) {
+        HIPCHK(hipMemcpy(xw_out, d_xo, nP * 12, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(normal, d_n, nP * 12, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(dist, d_d, nP * 4, hipMemcpyDeviceToHost));
+    }
+    if (nE) { HIPCHK(hipMemcpy(level1, d_l, nE, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(erase, d_er, nE, hipMemcpyDeviceToHost)); }
+    HIPCHK(hipMemcpy(stats, d_s, (size_t)n_problems * sizeof(sd_ba_stats), hipMemcpyDeviceToHost));
     return SD_OK;
 }
 

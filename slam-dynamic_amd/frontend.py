@@ -129,6 +129,10 @@ def lib():
         L.sd_batch_backproject_dense.argtypes = [vp, i, vp, vp, sz, sz, vp, sz, sz, f, vp, sz, sz, vp, vp, vp, i, vp, vp]
         L.sd_pose_optimize_device.argtypes = [i, vp, vp, vp, vp, vp, vp, vp]
         L.sd_pose_optimize_host.argtypes = [i, vp, vp, vp, vp, vp, vp]
+        L.sd_local_ba_device.argtypes = [i] + [vp] * 16
+        L.sd_local_ba_host.argtypes = [i] + [vp] * 15
+        L.sd_local_ba_set_profiling.argtypes = [i]
+        L.sd_local_ba_profile.argtypes = [i, vp]
         L.sd_batch_pose_optimize.argtypes = [vp, i, vp, vp, vp]
         L.sd_batch_download_pose.argtypes = [vp, i, vp, vp, i, C.POINTER(i), C.POINTER(i)]
         L.sd_tracker_set_pose_optimization.argtypes = [vp, i]
@@ -986,3 +990,58 @@ def pose_optimize(edge_offset, edges, cams, Tcw):
     out = np.zeros(max(len(e), 1), np.uint8); good = np.zeros(max(n, 1), np.int32)
     check(lib().sd_pose_optimize_host(n, _p(off), _p(e), _p(c), _p(T), _p(out), _p(good)))
     return T.reshape(n, 4, 4), out[:len(e)], good[:n]
+
+
+# ---- Optimizer::LocalBundleAdjustment on the device (include/sd_frontend.h: sd_local_ba_*) ----
+BA_KEYFRAME_DTYPE = np.dtype([("Tcw", "<f4", (16,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("mbf", "<f4"), ("fixed", "u1"),
+                              ("reserved", "u1", (3,))])                                                # sd_ba_keyframe
+BA_EDGE_DTYPE = np.dtype([("kf", "<i4"), ("point", "<i4"), ("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("inv_sigma2", "<f4"), ("tag", "<i4"),
+                          ("reserved", "<i4")])                                                         # sd_ba_edge
+BA_STATS_DTYPE = np.dtype([("iterations", "<i4", (2,)), ("trials", "<i4", (2,)), ("rejected", "<i4", (2,)), ("n_level1", "<i4"),
+                           ("n_erased", "<i4"), ("chi2", "<f8", (2,))])                                 # sd_ba_stats
+
+
+def pack_ba_problems(problems):
+    """The tables of sd_local_ba_*: (kf_offset, n_local, point_offset, edge_offset, kfs, xw, edges, ref_kf) of a list of problems, each
+    dict(kfs (BA_KEYFRAME_DTYPE, local keyframes first), n_local, xw (P, 3), edges (BA_EDGE_DTYPE, insertion order), ref_kf (P,))."""
+    kfs = [np.ascontiguousarray(p["kfs"]).view(BA_KEYFRAME_DTYPE).reshape(-1) for p in problems]
+    xw = [np.ascontiguousarray(p["xw"], np.float32).reshape(-1, 3) for p in problems]
+    ed = [np.ascontiguousarray(p["edges"]).view(BA_EDGE_DTYPE).reshape(-1) for p in problems]
+    ref = [np.ascontiguousarray(p["ref_kf"], np.int32).reshape(-1) for p in problems]
+    for x, r in zip(xw, ref):
+        assert len(x) == len(r)
+    off = lambda parts: np.concatenate([[0], np.cumsum([len(a) for a in parts])]).astype(np.int32)
+    cat = lambda parts, dt, tail: np.ascontiguousarray(np.concatenate(parts)) if parts else np.zeros((0,) + tail, dt)
+    return (off(kfs), np.array([int(p["n_local"]) for p in problems], np.int32), off(xw), off(ed), cat(kfs, BA_KEYFRAME_DTYPE, ()),
+            cat(xw, np.float32, (3,)), cat(ed, BA_EDGE_DTYPE, ()), cat(ref, np.int32, ()))
+
+
+BA_PHASES = ("index_lists", "linearisation", "schur_assembly", "factorisation", "solves", "update_chi2")
+
+
+def local_ba_profile(n_problems, on=None):
+    """on = True / False: the profiling switch of sd_local_ba_device.  on = None: (n_problems, 6) milliseconds per phase (BA_PHASES) of the
+    last profiled call on this device."""
+    if on is not None:
+        check(lib().sd_local_ba_set_profiling(int(bool(on))))
+        return None
+    ms = np.zeros((n_problems, len(BA_PHASES)), np.float64)
+    check(lib().sd_local_ba_profile(n_problems, _p(ms)))
+    return ms
+
+
+def local_bundle_adjustment(problems):
+    """Independent LocalBundleAdjustment problems in one launch (sd_local_ba_host); see pack_ba_problems for a problem.  Returns one dict
+    per problem: Tcw (n_local, 4, 4) f32, xw (P, 3), normal (P, 3), dist (P,), level1 (E,) u8, erase (E,) u8, stats (BA_STATS_DTYPE)."""
+    n = len(problems)
+    if n == 0:
+        return []
+    ko, nl, po, eo, kfs, xw, ed, ref = pack_ba_problems(problems)
+    nK, nP, nE = max(len(kfs), 1), max(len(xw), 1), max(len(ed), 1)
+    T = np.zeros((nK, 16), np.float32); xo = np.zeros((nP, 3), np.float32); nrm = np.zeros((nP, 3), np.float32); dist = np.zeros(nP, np.float32)
+    l1 = np.zeros(nE, np.uint8); er = np.zeros(nE, np.uint8); st = np.zeros(n, BA_STATS_DTYPE)
+    check(lib().sd_local_ba_host(n, _p(ko), _p(nl), _p(po), _p(eo), _p(kfs), _p(xw), _p(ed), _p(ref), _p(T), _p(xo), _p(nrm), _p(dist), _p(l1),
+                                 _p(er), _p(st)))
+    return [dict(Tcw=T[ko[q]:ko[q] + nl[q]].reshape(-1, 4, 4).copy(), xw=xo[po[q]:po[q + 1]].copy(), normal=nrm[po[q]:po[q + 1]].copy(),
+                 dist=dist[po[q]:po[q + 1]].copy(), level1=l1[eo[q]:eo[q + 1]].copy(), erase=er[eo[q]:eo[q + 1]].copy(), stats=st[q])
+            for q in range(n)]
