@@ -283,6 +283,74 @@ int sd_local_ba_host(int n_problems, const int32_t* kf_offset, const int32_t* n_
 #define SD_BA_PROFILE_PHASES 6
 int sd_local_ba_set_profiling(int on);
 int sd_local_ba_profile(int n_problems, double* ms);
+/* ---- Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc), as LoopClosing::ComputeSim3 drives it (src/LoopClosing.cc:232-400) ----
+ * Up to SD_SIM3_MAX_PROBLEMS independent Sim3Solver problems in one launch sequence: the 3-point Horn RANSAC of one (keyframe, loop candidate)
+ * pair each.  A problem is what the constructor gathers (Sim3Solver.cc:36-112): one record per kept correspondence, in i1 order --
+ * xw1 / xw2 = GetWorldPos() of pMP1 / pMP2, sigma2_1 / sigma2_2 = mvLevelSigma2[octave] of the two key points, tag = i1 (carried,
+ * never read) -- plus Tcw1 / Tcw2 = GetPose() row-major, the two cameras (mK1, mK2), bFixScale and a 64-bit seed.  The sampler is
+ * counter-based (DUtils::Random's rand() stream cannot be specified): draw d of iteration it is sd_splitmix64 of (seed, it, d)
+ * reduced modulo the current size of vAvailableIndices and mapped through the swap-with-back removal of :163-177 (DESIGN Q39). */
+typedef struct sd_sim3_corr {
+    float xw1[3], xw2[3];
+    float sigma2_1, sigma2_2;
+    int32_t tag;
+} sd_sim3_corr;                                   /* 36 bytes */
+typedef struct sd_sim3_problem {
+    float Tcw1[16], Tcw2[16];
+    float fx1, fy1, cx1, cy1;                     /* pKF1->mK */
+    float fx2, fy2, cx2, cy2;                     /* pKF2->mK */
+    int32_t fix_scale;                            /* mbFixScale */
+    int32_t reserved;
+    uint64_t seed;
+} sd_sim3_problem;                                /* 176 bytes */
+/* What find() == iterate(mRansacMaxIts) leaves (Sim3Solver.cc:140-213).  found = 1: the hypothesis of the LOWEST iteration whose
+ * inlier count is > min_inliers (:183-199); iteration is its 1-based index (mnIterations at the return), n_inliers its count, no_more
+ * = 0.  found = 0: no_more = 1 and iteration / n_inliers / T12 .. s12 are mnBestInliers / mBestT12 ..: the largest count and, among
+ * equal counts, the LATEST iteration (:183 compares with >=).  A problem with fewer correspondences than min_inliers (:146-150), or
+ * fewer than the 3 a sample needs, runs no hypothesis: found = 0, no_more = 1, iteration = 0, everything else zero.
+ * max_its = mRansacMaxIts after SetRansacParameters (:114-138).  T12 = [s12 R12 | t12] row-major 4x4. */
+typedef struct sd_sim3_result {
+    int32_t found, no_more, iteration, n_inliers, max_its, reserved;
+    float T12[16], R12[9], t12[3], s12;
+} sd_sim3_result;                                 /* 140 bytes */
+#define SD_SIM3_MAX_CORRESPONDENCES 4096          /* per problem */
+#define SD_SIM3_MAX_ITERATIONS 4096               /* max_iterations */
+#define SD_SIM3_MAX_PROBLEMS 65535                /* per call */
+/* Problem p owns correspondences [corr_offset[p], corr_offset[p+1]) of d_corr; corr_offset [n_problems + 1] and problems
+ * [n_problems] are HOST arrays, d_ arrays device memory.  probability / min_inliers / max_iterations: SetRansacParameters' arguments
+ * (the reference passes 0.99, 20, 300); its formula is evaluated on the host as written and the effective count comes back in
+ * max_its_out [n_problems] (host, nullable) and in every result.  Out: d_results [n_problems]; d_inliers [correspondences] u8, indexed
+ * like d_corr: entry e is vbInliers[d_corr[e].tag] of find() (the winning hypothesis' mask; all zero when found = 0).
+ * More than SD_SIM3_MAX_PROBLEMS problems, more than SD_SIM3_MAX_CORRESPONDENCES in a problem, max_iterations outside
+ * [1, SD_SIM3_MAX_ITERATIONS], min_inliers < 0, probability outside (0, 1), offsets that do not start at 0 or decrease: SD_ERR_INVALID before anything is launched, never a
+ * truncation.  Stateless with respect to sd_batch.  Asynchronous on `stream` with no host synchronisation, except that the problem
+ * table goes through a ring of 8 library-owned device tables per device and the library-owned workspace (grown with the largest call
+ * seen) is shared by the calls on one device, as for sd_local_ba_device. */
+int sd_sim3_ransac_device(int n_problems, const int32_t* corr_offset, const sd_sim3_corr* d_corr, const sd_sim3_problem* problems,
+                          double probability, int min_inliers, int max_iterations, sd_sim3_result* d_results, uint8_t* d_inliers,
+                          int32_t* max_its_out, void* stream);
+/* The same from host arrays: uploads, runs, synchronises. */
+int sd_sim3_ransac_host(int n_problems, const int32_t* corr_offset, const sd_sim3_corr* corr, const sd_sim3_problem* problems,
+                        double probability, int min_inliers, int max_iterations, sd_sim3_result* results, uint8_t* inliers);
+/* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1259-1483; LoopClosing.cc:362 passes th =
+ * 7.5) for n_pairs independent (KF1 slot, KF2 slot) pairs of one batch; sd_batch_assign_grid must have run on both slots of every
+ * pair (SD_ERR_STATE otherwise).  Host, per pair: kf1_index / kf2_index (slots), Tcw1 / Tcw2 (GetPose(), row-major 4x4), s12, R12
+ * (row-major 3x3), t12.  `cam` serves both directions, as the reference takes fx .. cy from pKF1 for both (:1262-1265).
+ * Device: the point table d_points / d_point_desc (GetDescriptor(), 32 B each) of n_points entries as for sd_batch_fuse (xw and
+ * min_distance / max_distance are read: GetMinDistanceInvariance() = 0.8f * min_distance, GetMaxDistanceInvariance() = 1.2f *
+ * max_distance); d_kf1_point / d_kf2_point [n_pairs][cap]: GetMapPointMatches() of the two key frames as indices into the point
+ * table, -1 for NULL or isBad(); d_matched12 [n_pairs][cap]: -1 where vpMatches12[i1] is NULL, else GetIndexInKeyFrame(pKF2) of that
+ * point -- -2 when the point is not in KF2; a value outside [0, N2) marks vbAlreadyMatched1 only (:1289-1299).
+ * Results stay in library-owned device memory (sd_batch_download_sim3_matches): match12[i1] = idx2 for the pairs the function ADDS
+ * to vpMatches12 (-1 elsewhere: vpMatches12[i1] = vpMapPoints2[idx2] is the caller's to perform), vnMatch1 / vnMatch2 as they stand
+ * before the agreement loop (:1464-1480), n_found = the return value.  A point index outside [-1, n_points) cannot be seen by the
+ * host: the kernel treats it as -1 and the download of EVERY pair of that call returns SD_ERR_INVALID (the next call starts clean). */
+int sd_batch_search_by_sim3(sd_batch* b, int n_pairs, const int32_t* kf1_index, const int32_t* kf2_index, const float* Tcw1_host,
+                            const float* Tcw2_host, const float* s12, const float* R12, const float* t12, const sd_camera* cam, float th,
+                            const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points, const int32_t* d_kf1_point,
+                            const int32_t* d_kf2_point, const int32_t* d_matched12, void* stream);
+/* match12 / vnMatch1 / vnMatch2: `cap` >= kp_capacity entries each (nullable); entries beyond N1 / N2 are -1. */
+int sd_batch_download_sim3_matches(sd_batch* b, int pair, int32_t* match12, int32_t* vnMatch1, int32_t* vnMatch2, int cap, int* n_found);
 /* PoseOptimization of mCurrentFrame after ORBmatcher::SearchByProjection(mCurrentFrame, mLastFrame, ...) for projection pairs
  * pair_index[k] (host, k < n_pairs) of the last sd_batch_search_by_projection: the edges are built on the device from the pair's
  * Current slot (mvKeysUn, mvuRight, octave -> the extractor's mvInvLevelSigma2), its match array (mvpMapPoints) and the Last

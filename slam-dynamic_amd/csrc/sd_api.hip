@@ -23,6 +23,7 @@
 #include "k_triangulate.h"
 #include "k_fuse.h"
 #include "k_ba.h"
+#include "k_sim3.h"
 #include "sd_common.h"
 #include "sd_vocab.h"
 
@@ -47,11 +48,11 @@ struct sd_extractor {
     SdParams prm;
 };
 
-enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_TRI_M, K_TRI_T, K_TRI_R, K_FUSE_S, K_FUSE_R, K_COUNT };
+enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_TRI_M, K_TRI_T, K_TRI_R, K_FUSE_S, K_FUSE_R, K_SIM3_M, K_SIM3_S, K_SIM3_A, K_COUNT };
 static const char* kKernelNames[K_COUNT] = {"k_pyr_level0", "k_pyr_level", "k_fast_cells", "k_quadtree", "k_orient",
                                             "k_blur", "k_describe", "k_stereo_match", "k_stereo_filter", "k_rgbd",
                                             "k_grid_cells", "k_unproject", "k_proj_candidates", "k_proj_resolve",
-                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select", "k_tri_match", "k_tri_triangulate", "k_tri_resolve", "k_fuse_search", "k_fuse_resolve"};
+                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select", "k_tri_match", "k_tri_triangulate", "k_tri_resolve", "k_fuse_search", "k_fuse_resolve", "k_sim3_mark", "k_sim3_search", "k_sim3_agree"};
 
 #define SD_PT_TW 256
 #define SD_PT_TH 16
@@ -133,6 +134,9 @@ struct sd_batch {
     // first-taker table of k_fuse_resolve where [cap] ints do not fit the LDS
     SdDevBuf<int> d_fuseJobs; SdDevBuf<float> d_fuseT; SdDevBuf<int> d_fuseN; SdDevBuf<int> d_fuseFirst; int fuseJobCap = 0, fuseFirstCap = 0, fuseJobs = 0;
     SdDevBuf<int2> d_fuseBest; SdDevBuf<SdFuseHit> d_fuseHits; int fuseEntryCap = 0; SdDevBuf<int> d_fuseErr; std::vector<int32_t> fuseOff;
+    // sd_batch_search_by_sim3: pair table and per-pair rows [pairs][cap], grown with the largest call seen
+    SdDevBuf<SdSim3Pair> d_s3Pairs; SdDevBuf<int> d_s3Match1, d_s3Match2, d_s3Match12, d_s3Found, d_s3Err; SdDevBuf<uint8_t> d_s3Already;
+    int s3PairCap = 0, s3Pairs = 0; std::vector<SdSim3Pair> s3Host;
     std::vector<sd_camera> pairCam, hPoseCam; std::vector<int32_t> hPoseMap;
     int nPairs = 0;
     int dlPairs = 0;          // pairs sd_batch_download_matches may read (the tracker also keeps pairs at [n_lanes, 2 * n_lanes))
@@ -2333,6 +2337,267 @@ int sd_local_ba_host(int n_problems, const int32_t* kf_offset, const int32_t* n_
     }
     if (nE) { HIPCHK(hipMemcpy(level1, d_l, nE, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(erase, d_er, nE, hipMemcpyDeviceToHost)); }
     HIPCHK(hipMemcpy(stats, d_s, (size_t)n_problems * sizeof(sd_ba_stats), hipMemcpyDeviceToHost));
+    return SD_OK;
+}
+
+// ---------------------------------------------------------------- Sim3Solver RANSAC (k_sim3.h)
+static_assert(sizeof(sd_sim3_corr) == 36 && sizeof(sd_sim3_problem) == 176 && sizeof(sd_sim3_result) == 140, "sim3 records");
+static_assert(sizeof(SdSim3Pt) == 48 && sizeof(SdSim3Hyp) == 192 && sizeof(SdSim3Prob) == 208, "sim3 workspace records");
+static_assert(SD_SIM3_MAX_N == SD_SIM3_MAX_CORRESPONDENCES && SD_SIM3_MAX_ITS == SD_SIM3_MAX_ITERATIONS, "sim3 caps");
+static_assert(SD_SIM3_MAX_N < (1 << 15) && SD_SIM3_MAX_ITS < (1 << 16), "a (count, iteration) key is 32 bits");
+static_assert(SD_SIM3_MAX_PROBLEMS <= 65535, "a problem is a grid row");
+#define SD_SIM3_RING 8
+namespace {
+struct Sim3State {
+    SdDevBuf<SdSim3Prob> prob[SD_SIM3_RING]; size_t probCap[SD_SIM3_RING] = {}; hipEvent_t done[SD_SIM3_RING] = {}; int next = 0;
+    SdDevBuf<SdSim3Pt> pts; SdDevBuf<SdSim3Hyp> hyp; SdDevBuf<int> count; size_t capPts = 0, capHyp = 0; hipEvent_t wsDone = nullptr;
+};
+Sim3State* const g_sim3 = new Sim3State[SD_POSE_MAX_DEVICES];       // never destroyed, as g_poseCams
+std::mutex g_sim3Mu;
+}
+
+// Sim3Solver::SetRansacParameters (Sim3Solver.cc:114-138) as written; the double is clamped before the conversion to int so that no
+// value of it is undefined (N < minInliers makes it NaN, a tiny epsilon makes it -inf)
+static int sim3_max_its(double probability, int minInliers, int maxIterations, int N)
+{
+    const float epsilon = (float)minInliers / N;
+    int nIterations;
+    if (minInliers == N) nIterations = 1;
+    else {
+        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
+        nIterations = !(v < (double)maxIterations) ? maxIterations : (v <= 1.0 ? 1 : (int)v);
+    }
+    return std::max(1, std::min(nIterations, maxIterations));
+}
+
+// the host-side checks both entry points share; fills the problem table
+static int sim3_plan(int n, const int32_t* off, const sd_sim3_problem* problems, double probability, int minInliers, int maxIterations,
+                     std::vector<SdSim3Prob>& tab, size_t& nHyp, int& maxN, int& maxIts)
+{
+    if (!off || !problems) return set_err(SD_ERR_INVALID, "bad sim3_ransac arguments");
+    if (!(probability > 0.0 && probability < 1.0)) return set_err(SD_ERR_INVALID, "sim3_ransac probability must lie in (0, 1)");
+    if (minInliers < 0) return set_err(SD_ERR_INVALID, "sim3_ransac min_inliers must not be negative");
+    if (maxIterations < 1 || maxIterations > SD_SIM3_MAX_ITS) return set_err(SD_ERR_INVALID, "sim3_ransac max_iterations outside [1, 4096]");
+    if (n > SD_SIM3_MAX_PROBLEMS) return set_err(SD_ERR_INVALID, "sim3_ransac: more than 65535 problems in one call");
+    if (off[0] != 0) return set_err(SD_ERR_INVALID, "sim3_ransac corr_offset[0] must be 0");
+    tab.resize(n);
+    nHyp = 0; maxN = 0; maxIts = 0;
+    for (int p = 0; p < n; p++) {
+        const long long N = (long long)off[p + 1] - off[p];
+        if (N < 0) return set_err(SD_ERR_INVALID, "sim3_ransac offsets must not decrease");
+        if (N > SD_SIM3_MAX_N) return set_err(SD_ERR_INVALID, "sim3_ransac problem " + std::to_string(p) + " holds more than 4096 correspondences");
+        SdSim3Prob& q = tab[p];
+        q.P = problems[p]; q.c0 = off[p]; q.n = (int)N; q.minInliers = minInliers; q.pad[0] = q.pad[1] = 0;
+        q.ransacMaxIts = sim3_max_its(probability, minInliers, maxIterations, (int)N);
+        q.maxIts = (N < minInliers || N < 3) ? 0 : q.ransacMaxIts;
+        q.h0 = (int)nHyp;
+        nHyp += (size_t)q.maxIts;
+        maxN = std::max(maxN, q.n); maxIts = std::max(maxIts, q.maxIts);
+    }
+    if (nHyp > (size_t)0x7FFFFFFF) return set_err(SD_ERR_INVALID, "sim3_ransac: more than 2^31 hypotheses in one call");
+    return SD_OK;
+}
+
+int sd_sim3_ransac_device(int n_problems, const int32_t* corr_offset, const sd_sim3_corr* d_corr, const sd_sim3_problem* problems,
+                          double probability, int min_inliers, int max_iterations, sd_sim3_result* d_results, uint8_t* d_inliers,
+                          int32_t* max_its_out, void* stream_)
+{
+    if (n_problems < 0) return set_err(SD_ERR_INVALID, "bad sim3_ransac arguments");
+    if (n_problems == 0) return SD_OK;
+    std::vector<SdSim3Prob> tab;
+    size_t nHyp = 0;
+    int maxN = 0, maxIts = 0;
+    int rc = sim3_plan(n_problems, corr_offset, problems, probability, min_inliers, max_iterations, tab, nHyp, maxN, maxIts);
+    if (rc != SD_OK) return rc;
+    const size_t nC = (size_t)corr_offset[n_problems];
+    if (!d_results || (nC && (!d_corr || !d_inliers))) return set_err(SD_ERR_INVALID, "bad sim3_ransac arguments");
+    if (max_its_out)
+        for (int p = 0; p < n_problems; p++)
+            max_its_out[p] = tab[p].ransacMaxIts;
+    hipStream_t s = (hipStream_t)stream_;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the sim3 tables");
+    std::lock_guard<std::mutex> lk(g_sim3Mu);
+    Sim3State& B = g_sim3[dev];
+    const int k = B.next;
+    if (B.done[k]) HIPCHK(hipEventSynchronize(B.done[k]));
+    else HIPCHK(hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
+    if (B.probCap[k] < (size_t)n_problems) {
+        B.probCap[k] = 0;
+        HIPCHK(B.prob[k].alloc((size_t)n_problems * sizeof(SdSim3Prob)));
+        B.probCap[k] = (size_t)n_problems;
+    }
+    const size_t needPts = std::max<size_t>(nC, 1), needHyp = std::max<size_t>(nHyp, 1);
+    if (!B.wsDone) HIPCHK(hipEventCreateWithFlags(&B.wsDone, hipEventDisableTiming));
+    else if (B.capPts < needPts || B.capHyp < needHyp) HIPCHK(hipEventSynchronize(B.wsDone));   // growing: the last launch must be done with it
+    else HIPCHK(hipStreamWaitEvent(s, B.wsDone, 0));
+    if (B.capPts < needPts) { B.capPts = 0; HIPCHK(B.pts.alloc(needPts * sizeof(SdSim3Pt))); B.capPts = needPts; }
+    if (B.capHyp < needHyp) {
+        B.capHyp = 0;
+        HIPCHK(B.hyp.alloc(needHyp * sizeof(SdSim3Hyp))); HIPCHK(B.count.alloc(needHyp * sizeof(int)));
+        B.capHyp = needHyp;
+    }
+    HIPCHK(hipMemcpyAsync(B.prob[k], tab.data(), (size_t)n_problems * sizeof(SdSim3Prob), hipMemcpyHostToDevice, s));
+    SdSim3Args A;
+    A.prob = B.prob[k]; A.corr = d_corr; A.pts = B.pts; A.hyp = B.hyp; A.count = B.count; A.result = d_results; A.inlier = d_inliers;
+    const int rowBlocks = std::max(1, (maxN + 255) / 256);
+    if (maxN > 0) {
+        hipLaunchKernelGGL(k_sim3_prepare, dim3(rowBlocks, n_problems), dim3(256), 0, s, A);
+        LAUNCH_CHECK("k_sim3_prepare");
+    }
+    if (maxIts > 0) {
+        hipLaunchKernelGGL(k_sim3_hypotheses, dim3((maxIts + 63) / 64, n_problems), dim3(64), 0, s, A);
+        LAUNCH_CHECK("k_sim3_hypotheses");
+        hipLaunchKernelGGL(k_sim3_count, dim3((maxIts + SD_SIM3_HYP_PER_BLOCK - 1) / SD_SIM3_HYP_PER_BLOCK, n_problems), dim3(256), 0, s, A);
+        LAUNCH_CHECK("k_sim3_count");
+    }
+    hipLaunchKernelGGL(k_sim3_select, dim3(n_problems), dim3(64), 0, s, A);
+    LAUNCH_CHECK("k_sim3_select");
+    if (maxN > 0) {
+        hipLaunchKernelGGL(k_sim3_inliers, dim3(rowBlocks, n_problems), dim3(256), 0, s, A);
+        LAUNCH_CHECK("k_sim3_inliers");
+    }
+    HIPCHK(hipEventRecord(B.done[k], s));
+    HIPCHK(hipEventRecord(B.wsDone, s));
+    B.next = (k + 1) % SD_SIM3_RING;
+    return SD_OK;
+}
+
+int sd_sim3_ransac_host(int n_problems, const int32_t* corr_offset, const sd_sim3_corr* corr, const sd_sim3_problem* problems,
+                        double probability, int min_inliers, int max_iterations, sd_sim3_result* results, uint8_t* inliers)
+{
+    if (n_problems < 0) return set_err(SD_ERR_INVALID, "bad sim3_ransac arguments");
+    if (n_problems == 0) return SD_OK;
+    std::vector<SdSim3Prob> tab;
+    size_t nHyp = 0;
+    int maxN = 0, maxIts = 0;
+    int rc = sim3_plan(n_problems, corr_offset, problems, probability, min_inliers, max_iterations, tab, nHyp, maxN, maxIts);
+    if (rc != SD_OK) return rc;
+    const size_t nC = (size_t)corr_offset[n_problems];
+    if (!results || (nC && (!corr || !inliers))) return set_err(SD_ERR_INVALID, "bad sim3_ransac arguments");
+    rc = require_device();
+    if (rc != SD_OK) return rc;
+    SdDevBuf<sd_sim3_corr> d_c; SdDevBuf<sd_sim3_result> d_r; SdDevBuf<uint8_t> d_i;
+    HIPCHK(d_c.alloc(std::max<size_t>(nC, 1) * sizeof(sd_sim3_corr))); HIPCHK(d_r.alloc((size_t)n_problems * sizeof(sd_sim3_result)));
+    HIPCHK(d_i.alloc(std::max<size_t>(nC, 1)));
+    if (nC) HIPCHK(hipMemcpy(d_c, corr, nC * sizeof(sd_sim3_corr), hipMemcpyHostToDevice));
+    rc = sd_sim3_ransac_device(n_problems, corr_offset, d_c, problems, probability, min_inliers, max_iterations, d_r, d_i, nullptr, nullptr);
+    if (rc != SD_OK) return rc;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(results, d_r, (size_t)n_problems * sizeof(sd_sim3_result), hipMemcpyDeviceToHost));
+    if (nC) HIPCHK(hipMemcpy(inliers, d_i, nC, hipMemcpyDeviceToHost));
+    return SD_OK;
+}
+
+// ---------------------------------------------------------------- ORBmatcher::SearchBySim3 (k_sim3.h)
+// `prev`: the stream of the batch's previous call, which may still be reading the rows that growth frees
+static int ensure_sim3(sd_batch* b, int n_pairs, hipStream_t s, hipStream_t prev)
+{
+    if (!b->d_s3Err) HIPCHK(b->d_s3Err.alloc(4));
+    if (n_pairs <= b->s3PairCap) return SD_OK;
+    if (prev != s) HIPCHK(hipStreamSynchronize(prev));
+    HIPCHK(hipStreamSynchronize(s));
+    const size_t want = (size_t)std::max(n_pairs, 2 * b->s3PairCap), rows = want * b->plan.kpCap;
+    b->s3PairCap = 0;
+    b->d_s3Pairs.reset(); b->d_s3Match1.reset(); b->d_s3Match2.reset(); b->d_s3Match12.reset(); b->d_s3Found.reset(); b->d_s3Already.reset();
+    HIPCHK(b->d_s3Pairs.alloc(want * sizeof(SdSim3Pair))); HIPCHK(b->d_s3Match1.alloc(rows * 4)); HIPCHK(b->d_s3Match2.alloc(rows * 4));
+    HIPCHK(b->d_s3Match12.alloc(rows * 4)); HIPCHK(b->d_s3Found.alloc(want * 4)); HIPCHK(b->d_s3Already.alloc(rows));
+    b->s3PairCap = (int)want;
+    return SD_OK;
+}
+
+int sd_batch_search_by_sim3(sd_batch* b, int n_pairs, const int32_t* kf1_index, const int32_t* kf2_index, const float* Tcw1_host,
+                            const float* Tcw2_host, const float* s12, const float* R12, const float* t12, const sd_camera* cam, float th,
+                            const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points, const int32_t* d_kf1_point,
+                            const int32_t* d_kf2_point, const int32_t* d_matched12, void* stream_)
+{
+    static_assert(sizeof(SdSim3Pair) == 272, "sim3 pair record");
+    if (!b || n_pairs < 0 || n_pairs > 32767 || n_points < 0 || !cam_ok(cam) || !(th > 0) ||
+        (n_pairs > 0 && (!kf1_index || !kf2_index || !Tcw1_host || !Tcw2_host || !s12 || !R12 || !t12 || !d_kf1_point || !d_kf2_point || !d_matched12)))
+        return set_err(SD_ERR_INVALID, "bad search_by_sim3 arguments");
+    b->s3Pairs = 0;
+    if (n_pairs == 0) return SD_OK;
+    if (n_points > 0 && (!d_points || !d_point_desc)) return set_err(SD_ERR_INVALID, "search_by_sim3: n_points but no point table");
+    for (int p = 0; p < n_pairs; p++)
+        if (kf1_index[p] < 0 || kf1_index[p] >= b->maxImages || kf2_index[p] < 0 || kf2_index[p] >= b->maxImages)
+            return set_err(SD_ERR_INVALID, "search_by_sim3: slot out of range");
+    for (int p = 0; p < n_pairs; p++) {
+        if (!slot_ok(b, kf1_index[p]) || !slot_ok(b, kf2_index[p])) return set_err(SD_ERR_STATE, "search_by_sim3: slot holds no results");
+        if (!b->gridValid[kf1_index[p]] || !b->gridValid[kf2_index[p]])
+            return set_err(SD_ERR_STATE, "search_by_sim3: sd_batch_assign_grid has not run on both slots");
+    }
+    const int cap = b->plan.kpCap;
+    if (cap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
+    const hipStream_t prev = b->lastStream;
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : prev;
+    b->lastStream = s;
+    int rc = ensure_sim3(b, n_pairs, s, prev);
+    if (rc != SD_OK) return rc;
+    HIPCHK(hipMemsetAsync(b->d_s3Err, 0, 4, s));               // the flag belongs to this call: every pair's download reports it
+    // the transformation between the cameras (ORBmatcher.cc:1276-1278), as DESIGN Q39 freezes it
+    b->s3Host.resize(n_pairs);
+    for (int p = 0; p < n_pairs; p++) {
+        SdSim3Pair& P = b->s3Host[p];
+        memcpy(P.T1, Tcw1_host + (size_t)p * 16, 64); memcpy(P.T2, Tcw2_host + (size_t)p * 16, 64);
+        const float sc = s12[p];
+        const float* R = R12 + (size_t)p * 9;
+        const float* t = t12 + (size_t)p * 3;
+        const double inv = 1.0 / (double)sc;
+        float sR21[3][3];
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) { P.T12[4 * i + j] = sc * R[3 * i + j]; sR21[i][j] = (float)(inv * (double)R[3 * j + i]); P.T21[4 * i + j] = sR21[i][j]; }
+            P.T12[4 * i + 3] = t[i];
+        }
+        for (int i = 0; i < 3; i++) { float a = (-sR21[i][0]) * t[0] + (-sR21[i][1]) * t[1]; P.T21[4 * i + 3] = a + (-sR21[i][2]) * t[2]; }
+        for (int j = 0; j < 3; j++) { P.T12[12 + j] = 0.f; P.T21[12 + j] = 0.f; }
+        P.T12[15] = 1.f; P.T21[15] = 1.f;
+        P.slot1 = kf1_index[p]; P.slot2 = kf2_index[p]; P.pad[0] = P.pad[1] = 0;
+    }
+    const size_t rows = (size_t)n_pairs * cap;
+    HIPCHK(hipMemcpyAsync(b->d_s3Pairs, b->s3Host.data(), (size_t)n_pairs * sizeof(SdSim3Pair), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(b->d_s3Already, 0, rows, s));
+    HIPCHK(hipMemsetAsync(b->d_s3Match1, 0xFF, rows * 4, s)); HIPCHK(hipMemsetAsync(b->d_s3Match2, 0xFF, rows * 4, s));
+    HIPCHK(hipMemsetAsync(b->d_s3Match12, 0xFF, rows * 4, s));
+    SdSim3SearchArgs A;
+    A.kp = KPUN(b); A.desc = b->d_desc; A.uRight = b->d_uright; A.sortedIdx = b->d_sortedIdx; A.cellStart = b->d_cellStart; A.count = b->d_count;
+    A.pairs = b->d_s3Pairs; A.mps = (const SdMapPoint*)d_points; A.mpDesc = d_point_desc; A.nPoints = n_points;
+    A.kfPoint[0] = d_kf1_point; A.kfPoint[1] = d_kf2_point; A.matched12 = d_matched12; A.already2 = b->d_s3Already;
+    A.vnMatch[0] = b->d_s3Match1; A.vnMatch[1] = b->d_s3Match2; A.match12 = b->d_s3Match12; A.nFound = b->d_s3Found; A.errFlag = b->d_s3Err; A.cap = cap;
+    {
+        ProfScope ps(b, s, K_SIM3_M);
+        hipLaunchKernelGGL(k_sim3_mark, dim3((cap + 255) / 256, n_pairs), dim3(256), 0, s, A);
+        LAUNCH_CHECK("k_sim3_mark");
+    }
+    {
+        ProfScope ps(b, s, K_SIM3_S);
+        hipLaunchKernelGGL(k_sim3_search, dim3((cap + 3) / 4, 2 * n_pairs), dim3(256), 0, s, A, level_tables(b), to_cam(cam), th);
+        LAUNCH_CHECK("k_sim3_search");
+    }
+    {
+        ProfScope ps(b, s, K_SIM3_A);
+        hipLaunchKernelGGL(k_sim3_agree, dim3(n_pairs), dim3(256), 0, s, A);
+        LAUNCH_CHECK("k_sim3_agree");
+    }
+    b->s3Pairs = n_pairs;
+    return SD_OK;
+}
+
+int sd_batch_download_sim3_matches(sd_batch* b, int pair, int32_t* match12, int32_t* vnMatch1, int32_t* vnMatch2, int cap, int* n_found)
+{
+    if (!b || !n_found) return set_err(SD_ERR_INVALID, "bad download_sim3_matches arguments");
+    if (pair < 0 || pair >= b->s3Pairs) return set_err(SD_ERR_INVALID, "download_sim3_matches: no such pair in the last sd_batch_search_by_sim3");
+    int rc = sd_batch_sync(b);
+    if (rc != SD_OK) return rc;
+    int err = 0;
+    HIPCHK(hipMemcpy(&err, b->d_s3Err, 4, hipMemcpyDeviceToHost));
+    if (err) return set_err(SD_ERR_INVALID, "search_by_sim3: a feature names a point outside [-1, n_points)");
+    if (cap < b->plan.kpCap) return set_err(SD_ERR_CAPACITY, "sim3 match buffers need kp_capacity entries");
+    const size_t row = (size_t)pair * b->plan.kpCap, bytes = (size_t)b->plan.kpCap * 4;
+    if (match12) HIPCHK(hipMemcpy(match12, b->d_s3Match12 + row, bytes, hipMemcpyDeviceToHost));
+    if (vnMatch1) HIPCHK(hipMemcpy(vnMatch1, b->d_s3Match1 + row, bytes, hipMemcpyDeviceToHost));
+    if (vnMatch2) HIPCHK(hipMemcpy(vnMatch2, b->d_s3Match2 + row, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n_found, b->d_s3Found + pair, 4, hipMemcpyDeviceToHost));
     return SD_OK;
 }
 

@@ -133,6 +133,8 @@ def lib():
         L.sd_local_ba_host.argtypes = [i] + [vp] * 15
         L.sd_local_ba_set_profiling.argtypes = [i]
         L.sd_local_ba_profile.argtypes = [i, vp]
+        L.sd_sim3_ransac_device.argtypes = [i, vp, vp, vp, C.c_double, i, i, vp, vp, vp, vp]
+        L.sd_sim3_ransac_host.argtypes = [i, vp, vp, vp, C.c_double, i, i, vp, vp]
         L.sd_batch_pose_optimize.argtypes = [vp, i, vp, vp, vp]
         L.sd_batch_download_pose.argtypes = [vp, i, vp, vp, i, C.POINTER(i), C.POINTER(i)]
         L.sd_tracker_set_pose_optimization.argtypes = [vp, i]
@@ -142,6 +144,8 @@ def lib():
         L.sd_batch_download_new_map_points.argtypes = [vp, i, vp, i, C.POINTER(i)]
         L.sd_batch_fuse.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, i, vp, vp, f, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
         L.sd_batch_download_fuse.argtypes = [vp, i, vp, vp, i, C.POINTER(i), C.POINTER(i)]
+        L.sd_batch_search_by_sim3.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp, vp]
+        L.sd_batch_download_sim3_matches.argtypes = [vp, i, vp, vp, vp, i, C.POINTER(i)]
         L.sd_distinctive_descriptors_device.argtypes = [i, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
@@ -480,6 +484,30 @@ class Batch:
         best = np.zeros((max(n, 1), 2), np.int32); hits = np.zeros(max(n, 1), FUSE_HIT_DTYPE); ne, nf = C.c_int(), C.c_int()
         check(lib().sd_batch_download_fuse(self.h, job, _p(best), _p(hits), n, C.byref(ne), C.byref(nf)))
         return best[:ne.value].copy(), hits[:nf.value].copy(), nf.value
+
+    # -- ORBmatcher::SearchBySim3 (LoopClosing::ComputeSim3)
+    def search_by_sim3(self, kf1_index, kf2_index, Tcw1, Tcw2, s12, R12, t12, cam, d_points, d_point_desc, d_kf1_point, d_kf2_point,
+                       d_matched12, th=7.5, stream=None, *, n_points):
+        """Pair p = SearchBySim3(slot kf1_index[p], slot kf2_index[p], vpMatches12, s12[p], R12[p], t12[p], th) with poses Tcw1[p] /
+        Tcw2[p] (assign_grid must have run on both slots).  d_points / d_point_desc: n_points sd_map_point records and descriptors;
+        d_kf1_point / d_kf2_point / d_matched12: [n_pairs][cap] int32 device tables (include/sd_frontend.h).  Results: download_sim3_matches."""
+        c = camera_array(cam)
+        k1 = np.ascontiguousarray(kf1_index, np.int32).reshape(-1); k2 = np.ascontiguousarray(kf2_index, np.int32).reshape(-1)
+        n = len(k1)
+        T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(-1, 16); T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(-1, 16)
+        s = np.ascontiguousarray(s12, np.float32).reshape(-1); R = np.ascontiguousarray(R12, np.float32).reshape(-1, 9)
+        t = np.ascontiguousarray(t12, np.float32).reshape(-1, 3)
+        if not (len(k2) == len(T1) == len(T2) == len(s) == len(R) == len(t) == n):
+            raise ValueError("search_by_sim3: one slot pair, two poses and one similarity per pair")
+        check(lib().sd_batch_search_by_sim3(self.h, n, _p(k1), _p(k2), _p(T1), _p(T2), _p(s), _p(R), _p(t), _p(c), C.c_float(th),
+                                            C.c_void_p(d_points or 0), C.c_void_p(d_point_desc or 0), int(n_points), C.c_void_p(d_kf1_point or 0),
+                                            C.c_void_p(d_kf2_point or 0), C.c_void_p(d_matched12 or 0), C.c_void_p(stream or 0)))
+
+    def download_sim3_matches(self, pair):
+        """Pair `pair` of the last search_by_sim3 -> (match12 (cap,), vnMatch1 (cap,), vnMatch2 (cap,), nFound); -1 beyond N1 / N2."""
+        m12 = np.zeros(self.cap, np.int32); m1 = np.zeros(self.cap, np.int32); m2 = np.zeros(self.cap, np.int32); nf = C.c_int()
+        check(lib().sd_batch_download_sim3_matches(self.h, pair, _p(m12), _p(m1), _p(m2), self.cap, C.byref(nf)))
+        return m12, m1, m2, nf.value
 
     # -- Tracking::TrackHomo model fit (H / F from the projection matcher's point pairs)
     def estimate_motion(self, stream=None):
@@ -990,6 +1018,41 @@ def pose_optimize(edge_offset, edges, cams, Tcw):
     out = np.zeros(max(len(e), 1), np.uint8); good = np.zeros(max(n, 1), np.int32)
     check(lib().sd_pose_optimize_host(n, _p(off), _p(e), _p(c), _p(T), _p(out), _p(good)))
     return T.reshape(n, 4, 4), out[:len(e)], good[:n]
+
+
+# ---- Sim3Solver RANSAC on the device (include/sd_frontend.h: sd_sim3_ransac_*) ----
+SIM3_CORR_DTYPE = np.dtype([("xw1", "<f4", (3,)), ("xw2", "<f4", (3,)), ("sigma2_1", "<f4"), ("sigma2_2", "<f4"), ("tag", "<i4")])     # sd_sim3_corr
+SIM3_PROBLEM_DTYPE = np.dtype([("Tcw1", "<f4", (16,)), ("Tcw2", "<f4", (16,)), ("K1", "<f4", (4,)), ("K2", "<f4", (4,)), ("fix_scale", "<i4"),
+                               ("reserved", "<i4"), ("seed", "<u8")])                                   # sd_sim3_problem; K = fx fy cx cy
+SIM3_RESULT_DTYPE = np.dtype([("found", "<i4"), ("no_more", "<i4"), ("iteration", "<i4"), ("n_inliers", "<i4"), ("max_its", "<i4"),
+                              ("reserved", "<i4"), ("T12", "<f4", (16,)), ("R12", "<f4", (9,)), ("t12", "<f4", (3,)), ("s12", "<f4")])   # sd_sim3_result
+SIM3_MAX_CORRESPONDENCES, SIM3_MAX_ITERATIONS, SIM3_MAX_PROBLEMS = 4096, 4096, 65535
+
+
+def sim3_ransac(corr_offset, corr, problems, probability=0.99, min_inliers=20, max_iterations=300, device=False):
+    """n independent Sim3Solver::find problems in one launch sequence (sd_sim3_ransac_host; device=True goes through
+    sd_sim3_ransac_device with torch-owned device arrays and one explicit synchronisation).  corr_offset (n + 1,) int32, corr (E,)
+    SIM3_CORR_DTYPE, problems (n,) SIM3_PROBLEM_DTYPE.  Returns (results (n,) SIM3_RESULT_DTYPE, inliers (E,) u8, in the order of corr)
+    in either form; the effective iteration count is results["max_its"]."""
+    off = np.ascontiguousarray(corr_offset, np.int32).reshape(-1)
+    n = len(off) - 1
+    c = np.ascontiguousarray(corr, SIM3_CORR_DTYPE).reshape(-1)
+    pr = np.ascontiguousarray(problems, SIM3_PROBLEM_DTYPE).reshape(-1)
+    assert len(pr) == n
+    res = np.zeros(max(n, 1), SIM3_RESULT_DTYPE); inl = np.zeros(max(len(c), 1), np.uint8)
+    if not device:
+        check(lib().sd_sim3_ransac_host(n, _p(off), _p(c), _p(pr), probability, min_inliers, max_iterations, _p(res), _p(inl)))
+        return res[:n], inl[:len(c)]
+    import torch
+    lib()
+    d_c = torch.from_numpy(c.view(np.uint8).reshape(-1).copy() if len(c) else np.zeros(1, np.uint8)).cuda()
+    d_r = torch.zeros(max(n, 1) * SIM3_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    d_i = torch.zeros(max(len(c), 1), dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    check(lib().sd_sim3_ransac_device(n, _p(off), C.c_void_p(d_c.data_ptr()), _p(pr), probability, min_inliers, max_iterations,
+                                      C.c_void_p(d_r.data_ptr()), C.c_void_p(d_i.data_ptr()), None, C.c_void_p(stream)))
+    torch.cuda.synchronize()
+    return d_r.cpu().numpy().view(SIM3_RESULT_DTYPE)[:n].copy(), d_i.cpu().numpy()[:len(c)].copy()
 
 
 # ---- Optimizer::LocalBundleAdjustment on the device (include/sd_frontend.h: sd_local_ba_*) ----
