@@ -130,10 +130,12 @@ static void ComputeThreeMaxima(const int* histoSize, const int L, int& ind1, int
 //   occupied[i2] (optional): CurrentFrame.mvpMapPoints[i2] already holds a point with Observations() > 0
 //   match[i2]: index i of the Last-frame point now in CurrentFrame.mvpMapPoints[i2], or -1
 //   pairs: (i, i2) for every accepted match, in order of i (points_last / points_current, :505-506)
-int orc_search_by_projection(const void* kpC_, const uint8_t* descC, const float* uRightC, int Nc, const void* kpL_,
-                             const uint8_t* dMP, int Nl, const float* xw, const uint8_t* flags, const float* Tcw,
-                             const float* Tlw, const float* cam10, const float* scaleFactors, float th, int bMono,
-                             int checkOrientation, const uint8_t* occupied, int* match, int* pairs, int* npairs)
+//   outcome[i] (optional, the _ex entry): where Last-frame point i left the function, in the order of the reference's exits
+enum { FF_NO_POINT, FF_BEHIND, FF_U_OUT, FF_V_OUT, FF_WINDOW_EMPTY, FF_NO_CANDIDATE, FF_DIST_HIGH, FF_MATCHED, FF_MATCHED_THEN_CULLED };
+static int search_by_projection_impl(const void* kpC_, const uint8_t* descC, const float* uRightC, int Nc, const void* kpL_,
+                                     const uint8_t* dMP, int Nl, const float* xw, const uint8_t* flags, const float* Tcw,
+                                     const float* Tlw, const float* cam10, const float* scaleFactors, float th, int bMono,
+                                     int checkOrientation, const uint8_t* occupied, int* match, int* pairs, int* npairs, int* outcome)
 {
     const KeyPoint* kpC = (const KeyPoint*)kpC_; const KeyPoint* kpL = (const KeyPoint*)kpL_;
     OrcCamera c; memcpy(&c, cam10, sizeof(c));
@@ -141,6 +143,7 @@ int orc_search_by_projection(const void* kpC_, const uint8_t* descC, const float
     AssignFeaturesToGrid(kpC, Nc, c, grid);
     int nmatches = 0;
     std::vector<int> rotHist[HISTO_LENGTH];
+    std::vector<int> rotHistPoint[HISTO_LENGTH];      // the Last-frame point behind every rotHist entry (for outcome[] only)
     const float factor = 1.0f / HISTO_LENGTH;
     // twc = -Rcw.t()*tcw ; tlc = Rlw*twc + tlw
     float twc[3], tlc[3];
@@ -156,24 +159,25 @@ int orc_search_by_projection(const void* kpC_, const uint8_t* descC, const float
     std::vector<uint8_t> taken(Nc, 0);      // mvpMapPoints[i2] && Observations() > 0
     for (int i = 0; i < Nc; i++) { match[i] = -1; if (occupied) taken[i] = occupied[i]; }
     int np = 0;
+#define FF_EXIT(code) { if (outcome) outcome[i] = (code); continue; }
     for (int i = 0; i < Nl; i++) {
-        if (!(flags[i] & 1)) continue;
+        if (!(flags[i] & 1)) FF_EXIT(FF_NO_POINT)
         float x3Dc[3];
         mat3_mul_add(Tcw, 4, &xw[3 * i], tcw, x3Dc);
         const float xc = x3Dc[0], yc = x3Dc[1];
         const float invzc = 1.0f / x3Dc[2];
-        if (invzc < 0) continue;
+        if (invzc < 0) FF_EXIT(FF_BEHIND)
         float u = c.fx * xc * invzc + c.cx;
         float v = c.fy * yc * invzc + c.cy;
-        if (u < c.mnMinX || u > c.mnMaxX) continue;
-        if (v < c.mnMinY || v > c.mnMaxY) continue;
+        if (u < c.mnMinX || u > c.mnMaxX) FF_EXIT(FF_U_OUT)
+        if (v < c.mnMinY || v > c.mnMaxY) FF_EXIT(FF_V_OUT)
         int nLastOctave = kpL[i].octave;
         float radius = th * scaleFactors[nLastOctave];
         std::vector<size_t> vIndices2;
         if (bForward) vIndices2 = GetFeaturesInArea(grid, kpC, c, u, v, radius, nLastOctave, -1);
         else if (bBackward) vIndices2 = GetFeaturesInArea(grid, kpC, c, u, v, radius, 0, nLastOctave);
         else vIndices2 = GetFeaturesInArea(grid, kpC, c, u, v, radius, nLastOctave - 1, nLastOctave + 1);
-        if (vIndices2.empty()) continue;
+        if (vIndices2.empty()) FF_EXIT(FF_WINDOW_EMPTY)
         const uint8_t* d1 = dMP + (size_t)i * 32;
         int bestDist = 256, bestIdx2 = -1;
         for (size_t k = 0; k < vIndices2.size(); k++) {
@@ -199,9 +203,12 @@ int orc_search_by_projection(const void* kpC_, const uint8_t* descC, const float
                 int bin = (int)roundf(rot * factor);
                 if (bin == HISTO_LENGTH) bin = 0;
                 rotHist[bin].push_back(bestIdx2);
+                rotHistPoint[bin].push_back(i);
             }
-        }
+            if (outcome) outcome[i] = FF_MATCHED;
+        } else if (outcome) outcome[i] = bestIdx2 < 0 ? FF_NO_CANDIDATE : FF_DIST_HIGH;
     }
+#undef FF_EXIT
     if (checkOrientation) {
         int ind1 = -1, ind2 = -1, ind3 = -1;
         int sizes[HISTO_LENGTH];
@@ -209,10 +216,31 @@ int orc_search_by_projection(const void* kpC_, const uint8_t* descC, const float
         ComputeThreeMaxima(sizes, HISTO_LENGTH, ind1, ind2, ind3);
         for (int i = 0; i < HISTO_LENGTH; i++)
             if (i != ind1 && i != ind2 && i != ind3)
-                for (size_t j = 0; j < rotHist[i].size(); j++) { match[rotHist[i][j]] = -1; nmatches--; }
+                for (size_t j = 0; j < rotHist[i].size(); j++) {
+                    match[rotHist[i][j]] = -1; nmatches--;
+                    if (outcome) outcome[rotHistPoint[i][j]] = FF_MATCHED_THEN_CULLED;
+                }
     }
     if (npairs) *npairs = np;
     return nmatches;
+}
+
+int orc_search_by_projection(const void* kpC_, const uint8_t* descC, const float* uRightC, int Nc, const void* kpL_,
+                             const uint8_t* dMP, int Nl, const float* xw, const uint8_t* flags, const float* Tcw,
+                             const float* Tlw, const float* cam10, const float* scaleFactors, float th, int bMono,
+                             int checkOrientation, const uint8_t* occupied, int* match, int* pairs, int* npairs)
+{
+    return search_by_projection_impl(kpC_, descC, uRightC, Nc, kpL_, dMP, Nl, xw, flags, Tcw, Tlw, cam10, scaleFactors, th, bMono,
+                                     checkOrientation, occupied, match, pairs, npairs, 0);
+}
+
+int orc_search_by_projection_ex(const void* kpC_, const uint8_t* descC, const float* uRightC, int Nc, const void* kpL_,
+                                const uint8_t* dMP, int Nl, const float* xw, const uint8_t* flags, const float* Tcw,
+                                const float* Tlw, const float* cam10, const float* scaleFactors, float th, int bMono,
+                                int checkOrientation, const uint8_t* occupied, int* match, int* pairs, int* npairs, int* outcome)
+{
+    return search_by_projection_impl(kpC_, descC, uRightC, Nc, kpL_, dMP, Nl, xw, flags, Tcw, Tlw, cam10, scaleFactors, th, bMono,
+                                     checkOrientation, occupied, match, pairs, npairs, outcome);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -243,31 +271,35 @@ static inline int PredictScale(float maxDistance, float currentDist, float logSc
     return nScale;
 }
 
+// why: the exit taken (LM_*), LM_MATCHED standing for "in view" until the search decides
+enum { LM_FLAG_OFF, LM_BEHIND, LM_U_OUT, LM_V_OUT, LM_DIST_BELOW_MIN, LM_DIST_ABOVE_MAX, LM_VIEW_ANGLE, LM_WINDOW_EMPTY, LM_NO_CANDIDATE,
+       LM_DIST_HIGH, LM_RATIO, LM_MATCHED };
 static bool isInFrustum(const OrcMapPoint& mp, const float* Tcw, const float* Ow, const OrcCamera& c, float logScaleFactor,
-                        int nScaleLevels, float viewingCosLimit, OrcTrack& t)
+                        int nScaleLevels, float viewingCosLimit, OrcTrack& t, int& why)
 {
     t.inView = 0;
     const float tcw[3] = {Tcw[3], Tcw[7], Tcw[11]};
     float Pc[3];
     mat3_mul_add(Tcw, 4, mp.xw, tcw, Pc);
     const float PcX = Pc[0], PcY = Pc[1], PcZ = Pc[2];
-    if (PcZ < 0.0f) return false;
+    if (PcZ < 0.0f) { why = LM_BEHIND; return false; }
     const float invz = 1.0f / PcZ;
     const float u = c.fx * PcX * invz + c.cx;
     const float v = c.fy * PcY * invz + c.cy;
-    if (u < c.mnMinX || u > c.mnMaxX) return false;
-    if (v < c.mnMinY || v > c.mnMaxY) return false;
+    if (u < c.mnMinX || u > c.mnMaxX) { why = LM_U_OUT; return false; }
+    if (v < c.mnMinY || v > c.mnMaxY) { why = LM_V_OUT; return false; }
     const float maxDistance = 1.2f * mp.maxDistance;
     const float minDistance = 0.8f * mp.minDistance;
     const float PO[3] = {mp.xw[0] - Ow[0], mp.xw[1] - Ow[1], mp.xw[2] - Ow[2]};
     double s2 = 0;
     for (int i = 0; i < 3; i++) s2 += (double)PO[i] * (double)PO[i];
     const float dist = (float)sqrt(s2);
-    if (dist < minDistance || dist > maxDistance) return false;
+    if (dist < minDistance || dist > maxDistance) { why = dist < minDistance ? LM_DIST_BELOW_MIN : LM_DIST_ABOVE_MAX; return false; }
     double dot = 0;
     for (int i = 0; i < 3; i++) dot += (double)PO[i] * (double)mp.normal[i];
     const float viewCos = (float)(dot / (double)dist);
-    if (viewCos < viewingCosLimit) return false;
+    if (viewCos < viewingCosLimit) { why = LM_VIEW_ANGLE; return false; }
+    why = LM_MATCHED;
     const int nPredictedLevel = PredictScale(mp.maxDistance, dist, logScaleFactor, nScaleLevels);
     t.inView = 1;
     t.projX = u;
@@ -281,10 +313,12 @@ static bool isInFrustum(const OrcMapPoint& mp, const float* Tcw, const float* Ow
 // Returns nmatches.  occupied[i] (optional): F.mvpMapPoints[i] holds a point with Observations() > 0 before the call.
 // mpMatch[m] = keypoint index given to map point m (or -1); kpMatch[i] = map point finally stored in F.mvpMapPoints[i] by
 // this call (or -1); track[m] = the isInFrustum outputs.
-int orc_search_local_map(const void* kpF_, const uint8_t* descF, const float* uRightF, int N, const void* mps_,
-                         const uint8_t* mpDesc, int M, const float* Tcw, const float* cam10, const float* scaleFactors,
-                         int nScaleLevels, float th, float nnratio, float viewingCosLimit, const uint8_t* occupied,
-                         void* track_, int* mpMatch, int* kpMatch)
+// outcome[m] (optional, the _ex entry): LM_*; best[4 * m ..] (optional): bestDist, bestDist2, bestLevel, bestLevel2 as they stood at
+// the ratio test (256 / -1 where the search was not reached or found nothing).
+static int search_local_map_impl(const void* kpF_, const uint8_t* descF, const float* uRightF, int N, const void* mps_,
+                                 const uint8_t* mpDesc, int M, const float* Tcw, const float* cam10, const float* scaleFactors,
+                                 int nScaleLevels, float th, float nnratio, float viewingCosLimit, const uint8_t* occupied,
+                                 void* track_, int* mpMatch, int* kpMatch, int* outcome, int* best)
 {
     const KeyPoint* kpF = (const KeyPoint*)kpF_;
     const OrcMapPoint* mps = (const OrcMapPoint*)mps_;
@@ -305,7 +339,10 @@ int orc_search_local_map(const void* kpF_, const uint8_t* descF, const float* uR
     for (int m = 0; m < M; m++) {
         mpMatch[m] = -1;
         memset(&track[m], 0, sizeof(OrcTrack));
-        if (mps[m].flags & 1) isInFrustum(mps[m], Tcw, Ow, c, logScaleFactor, nScaleLevels, viewingCosLimit, track[m]);
+        int why = LM_FLAG_OFF;
+        if (mps[m].flags & 1) isInFrustum(mps[m], Tcw, Ow, c, logScaleFactor, nScaleLevels, viewingCosLimit, track[m], why);
+        if (outcome) outcome[m] = why;
+        if (best) { best[4 * m] = 256; best[4 * m + 1] = 256; best[4 * m + 2] = -1; best[4 * m + 3] = -1; }
     }
     int nmatches = 0;
     const bool bFactor = th != 1.0;
@@ -317,7 +354,7 @@ int orc_search_local_map(const void* kpF_, const uint8_t* descF, const float* uR
         if (bFactor) r *= th;
         const std::vector<size_t> vIndices =
             GetFeaturesInArea(grid, kpF, c, t.projX, t.projY, r * scaleFactors[nPredictedLevel], nPredictedLevel - 1, nPredictedLevel);
-        if (vIndices.empty()) continue;
+        if (vIndices.empty()) { if (outcome) outcome[iMP] = LM_WINDOW_EMPTY; continue; }
         const uint8_t* MPdescriptor = mpDesc + (size_t)iMP * 32;
         int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
         for (size_t k = 0; k < vIndices.size(); k++) {
@@ -334,15 +371,36 @@ int orc_search_local_map(const void* kpF_, const uint8_t* descF, const float* uR
                 bestLevel2 = kpF[idx].octave; bestDist2 = dist;
             }
         }
+        if (best) { best[4 * iMP] = bestDist; best[4 * iMP + 1] = bestDist2; best[4 * iMP + 2] = bestLevel; best[4 * iMP + 3] = bestLevel2; }
+        if (outcome) outcome[iMP] = bestIdx < 0 ? LM_NO_CANDIDATE : LM_DIST_HIGH;
         if (bestDist <= TH_HIGH) {
-            if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
+            if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) { if (outcome) outcome[iMP] = LM_RATIO; continue; }
             kpMatch[bestIdx] = iMP;
             if (mps[iMP].flags & 2) taken[bestIdx] = 1;
             mpMatch[iMP] = bestIdx;
             nmatches++;
+            if (outcome) outcome[iMP] = LM_MATCHED;
         }
     }
     return nmatches;
+}
+
+int orc_search_local_map(const void* kpF_, const uint8_t* descF, const float* uRightF, int N, const void* mps_,
+                         const uint8_t* mpDesc, int M, const float* Tcw, const float* cam10, const float* scaleFactors,
+                         int nScaleLevels, float th, float nnratio, float viewingCosLimit, const uint8_t* occupied,
+                         void* track_, int* mpMatch, int* kpMatch)
+{
+    return search_local_map_impl(kpF_, descF, uRightF, N, mps_, mpDesc, M, Tcw, cam10, scaleFactors, nScaleLevels, th, nnratio,
+                                 viewingCosLimit, occupied, track_, mpMatch, kpMatch, 0, 0);
+}
+
+int orc_search_local_map_ex(const void* kpF_, const uint8_t* descF, const float* uRightF, int N, const void* mps_,
+                            const uint8_t* mpDesc, int M, const float* Tcw, const float* cam10, const float* scaleFactors,
+                            int nScaleLevels, float th, float nnratio, float viewingCosLimit, const uint8_t* occupied,
+                            void* track_, int* mpMatch, int* kpMatch, int* outcome, int* best)
+{
+    return search_local_map_impl(kpF_, descF, uRightF, N, mps_, mpDesc, M, Tcw, cam10, scaleFactors, nScaleLevels, th, nnratio,
+                                 viewingCosLimit, occupied, track_, mpMatch, kpMatch, outcome, best);
 }
 
 // ---------------------------------------------------------------------------------------------------------

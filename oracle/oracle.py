@@ -237,6 +237,30 @@ def search_by_projection(kpC, descC, uRightC, kpL, dMP, xw, flags, Tcw, Tlw, cam
     return match, pairs[:npairs.value].copy(), nm
 
 
+# outcome codes of search_by_projection_ex, in the order of the exits of ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, ...)
+FF_NAMES = ("no_point", "behind", "u_out", "v_out", "window_empty", "no_candidate", "dist>TH_HIGH", "matched", "matched_then_culled")
+
+
+def search_by_projection_ex(kpC, descC, uRightC, kpL, dMP, xw, flags, Tcw, Tlw, cam10, scale_factors, th, bMono=False,
+                            checkOrientation=True, occupied=None):
+    """search_by_projection plus, per Last-frame point, the exit it took (an index into FF_NAMES) -> (match, pairs, nm, outcome)."""
+    kpC = np.ascontiguousarray(kpC); kpL = np.ascontiguousarray(kpL)
+    descC = np.ascontiguousarray(descC, np.uint8); dMP = np.ascontiguousarray(dMP, np.uint8)
+    uR = np.ascontiguousarray(uRightC, np.float32); xw = np.ascontiguousarray(xw, np.float32)
+    flags = np.ascontiguousarray(flags, np.uint8)
+    Tc = np.ascontiguousarray(Tcw, np.float32).reshape(16); Tl = np.ascontiguousarray(Tlw, np.float32).reshape(16)
+    c = np.ascontiguousarray(cam10, np.float32); sf = np.ascontiguousarray(scale_factors, np.float32)
+    Nc, Nl = len(kpC), len(kpL)
+    match = np.zeros(Nc, np.int32); pairs = np.zeros((Nl, 2), np.int32); npairs = C.c_int(); outcome = np.zeros(Nl, np.int32)
+    occ = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+    f = lib().orc_search_by_projection_ex
+    f.restype = C.c_int
+    nm = f(_p(kpC), _p(descC), _p(uR), Nc, _p(kpL), _p(dMP), Nl, _p(xw), _p(flags), _p(Tc), _p(Tl), _p(c), _p(sf),
+           C.c_float(th), int(bMono), int(checkOrientation), _p(occ) if occ is not None else None, _p(match), _p(pairs),
+           C.byref(npairs), _p(outcome))
+    return match, pairs[:npairs.value].copy(), nm, outcome
+
+
 MAP_POINT_DTYPE = np.dtype([("xw", "<f4", 3), ("normal", "<f4", 3), ("min_distance", "<f4"), ("max_distance", "<f4"),
                             ("flags", "<u4")])          # sd_map_point, 36 B
 TRACK_DTYPE = np.dtype([("proj_x", "<f4"), ("proj_y", "<f4"), ("proj_xr", "<f4"), ("view_cos", "<f4"), ("level", "<i4"),
@@ -259,6 +283,31 @@ def search_local_map(kpF, descF, uRightF, mps, mp_desc, Tcw, cam10, scale_factor
     nm = f(_p(kpF), _p(descF), _p(uR), N, _p(mps), _p(md), M, _p(T), _p(c), _p(sf), len(sf), C.c_float(th), C.c_float(nnratio),
            C.c_float(viewing_cos_limit), _p(occ) if occ is not None else None, _p(track), _p(mpm), _p(kpm))
     return track, mpm, kpm, nm
+
+
+# outcome codes of search_local_map_ex, in the order of the exits of Frame::isInFrustum and ORBmatcher::SearchByProjection(F, MapPoints, th)
+LM_NAMES = ("flag_off", "behind", "u_out", "v_out", "dist_below_min", "dist_above_max", "view_angle", "window_empty", "no_candidate",
+            "dist>TH_HIGH", "ratio", "matched")
+
+
+def search_local_map_ex(kpF, descF, uRightF, mps, mp_desc, Tcw, cam10, scale_factors, th, nnratio, viewing_cos_limit=0.5,
+                        occupied=None):
+    """search_local_map plus, per map point, the exit it took (an index into LM_NAMES) and best (M, 4) i32: bestDist, bestDist2,
+    bestLevel, bestLevel2 at the ratio test (256 / -1 where unset) -> (track, mp_match, kp_match, nmatches, outcome, best)."""
+    kpF = np.ascontiguousarray(kpF); descF = np.ascontiguousarray(descF, np.uint8)
+    uR = np.ascontiguousarray(uRightF, np.float32)
+    mps = np.ascontiguousarray(mps, MAP_POINT_DTYPE); md = np.ascontiguousarray(mp_desc, np.uint8)
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    c = np.ascontiguousarray(cam10, np.float32); sf = np.ascontiguousarray(scale_factors, np.float32)
+    N, M = len(kpF), len(mps)
+    track = np.zeros(M, TRACK_DTYPE); mpm = np.zeros(M, np.int32); kpm = np.zeros(N, np.int32)
+    outcome = np.zeros(M, np.int32); best = np.zeros((M, 4), np.int32)
+    occ = None if occupied is None else np.ascontiguousarray(occupied, np.uint8)
+    f = lib().orc_search_local_map_ex
+    f.restype = C.c_int
+    nm = f(_p(kpF), _p(descF), _p(uR), N, _p(mps), _p(md), M, _p(T), _p(c), _p(sf), len(sf), C.c_float(th), C.c_float(nnratio),
+           C.c_float(viewing_cos_limit), _p(occ) if occ is not None else None, _p(track), _p(mpm), _p(kpm), _p(outcome), _p(best))
+    return track, mpm, kpm, nm, outcome, best
 
 
 def box_track(boxes, last_objects, last_box_idx, last_omit, last_velocity, img_cols, img_rows, cap=None):
