@@ -4,47 +4,26 @@ import math
 import numpy as np
 import pytest
 
-RING = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -3), (-1, -3), (-2, -2), (-3, -1), (-3, 0),
-        (-3, 1), (-2, 2), (-1, 3)]
+# FAST-9/16 + NMS from the definition, one copy shared with the crafted extractor cases.  It states the rule this file used to state pixel
+# by pixel (corner iff 9 contiguous ring pixels are all darker than v - t or all brighter than v + t; score = the largest such t, >= thr;
+# strict 3 x 3 maximum, zero outside the map; row-major output) as array operations: the largest t of an arc is the minimum of its nine
+# differences less one.  test_definition_by_hand pins that form on literal values.
+from extract_cases import RING, brute_fast
 
 
-def brute_fast(img, thr):
-    """FAST-9/16 straight from its definition: corner iff >= 9 contiguous ring pixels all darker than v-t or all
-    brighter than v+t; score = the largest t for which that still holds; 3x3 strict-maximum NMS; row-major output."""
-    h, w = img.shape
-    I = img.astype(np.int32)
-
-    def is_corner(y, x, t):
-        v = I[y, x]
-        d = [v - I[y + dy, x + dx] for dx, dy in RING]
-        for sign in (1, -1):
-            flags = [sign * e > t for e in d] * 2
-            run = 0
-            for f in flags:
-                run = run + 1 if f else 0
-                if run >= 9:
-                    return True
-        return False
-
-    score = np.zeros((h, w), np.int32)
-    for y in range(3, h - 3):
-        for x in range(3, w - 3):
-            if is_corner(y, x, thr):
-                t = thr
-                while t < 255 and is_corner(y, x, t + 1):
-                    t += 1
-                score[y, x] = t
-    out = []
-    for y in range(3, h - 3):
-        for x in range(3, w - 3):
-            s = score[y, x]
-            if s == 0:
-                continue
-            nb = score[y - 1:y + 2, x - 1:x + 2].copy()
-            nb[1, 1] = -1
-            if (s > nb).all():
-                out.append((x, y, s))
-    return np.array(out, np.int32).reshape(-1, 3)
+def test_definition_by_hand():
+    img = np.full((7, 7), 50, np.uint8); img[3, 3] = 150
+    assert brute_fast(img, 99).tolist() == [[3, 3, 99]] and len(brute_fast(img, 100)) == 0       # all 16 ring pixels darker by 100
+    img = np.full((9, 9), 90, np.uint8)
+    for k, (dx, dy) in enumerate(RING[3:12]):            # nine contiguous ring pixels brighter than the centre by 31 .. 39
+        img[4 + dy, 4 + dx] = 121 + k
+    assert brute_fast(img, 20).tolist() == [[4, 4, 30]]                                          # the weakest of the nine decides: 31 - 1
+    img[4 + RING[7][1], 4 + RING[7][0]] = 90             # a gap in the middle: arcs of 4 and 4
+    assert len(brute_fast(img, 1)) == 0
+    img = np.full((9, 12), 60, np.uint8); img[4, 4] = img[4, 5] = 200
+    assert len(brute_fast(img, 20)) == 0                                                         # equal neighbours: neither is a strict maximum
+    img[4, 5] = 199
+    assert brute_fast(img, 20).tolist() == [[4, 4, 139]]
 
 
 def test_fast_against_definition(orc):
