@@ -463,6 +463,51 @@ int sd_batch_fuse(sd_batch* b, int n_jobs, const int32_t* kf_index, const float*
 /* best [n][2] (nullable), hits (nullable) with room for cap_entries records, n_entries = the job's entry count, nfused = its return
  * value.  SD_ERR_CAPACITY when the job has more than cap_entries entries. */
 int sd_batch_download_fuse(sd_batch* b, int job, int32_t* best, sd_fuse_hit* hits, int cap_entries, int* n_entries, int* nfused);
+
+/* ---- LoopClosing::ComputeSim3 (src/LoopClosing.cc:240-400) and SearchAndFuse (:586-620): the matchers ----
+ * Both Scw functions decompose the similarity on the host per job, as DESIGN.md Q41 freezes it: scw = (float)sqrt(f64 sum of the squares
+ * of row 0), inv = (float)(1.0 / (double)scw), Rcw = sRcw * inv and tcw = t * inv element-wise in f32; Ow follows as for any pose.
+ *
+ * ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1134-1257).  Job tables, entries, d_kf_state, outputs and
+ * the sd_batch_download_fuse records are those of sd_batch_fuse (Scw_host: n_jobs row-major 4x4 similarities); an entry is -1 for isBad()
+ * or a member of pKF->GetMapPoints().  The search has no chi-square and no uRight test, and bestDist starts at INT_MAX: a lone member at
+ * distance 256 is reported as (idx, 256) and is not a hit.  Action codes: SD_FUSE_MEET_KF = vpReplacePoint[cand] = the feature's point;
+ * SD_FUSE_MEET_BAD = counted only; SD_FUSE_ADD = AddObservation + AddMapPoint; SD_FUSE_MEET_CANDIDATE = the feature now holds the
+ * earlier candidate `other`, which is what vpReplacePoint[cand] becomes. */
+int sd_batch_fuse_sim3(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Scw_host, const int32_t* cand_offset,
+                       const int32_t* d_cand_point, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
+                       const uint8_t* d_kf_state, const sd_camera* cam, float th, int32_t** d_best, sd_fuse_hit** d_hits,
+                       int32_t** d_nfused, void* stream);
+/* ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12) (src/ORBmatcher.cc:679-812) for n_pairs (at most max_images) independent pairs of
+ * slots; sd_batch_compute_bow must have run on both (SD_ERR_STATE otherwise).  d_valid1 / d_valid2 (nullable, [n_pairs][cap] u8): the
+ * feature's map point is non-NULL and not bad.  Results through sd_batch_download_matches: match[idx1] = idx2 or -1 (the assignment
+ * vpMatches12[idx1] = vpMapPoints2[idx2] stays the caller's), nmatches = the return value, no pairs.  Unlike the keyframe-frame
+ * function the acceptance is bestDist1 < TH_LOW. */
+int sd_batch_search_by_bow_kf(sd_batch* b, int n_pairs, const int32_t* kf1_index, const int32_t* kf2_index, const uint8_t* d_valid1,
+                              const uint8_t* d_valid2, float nnratio, int check_orientation, void* stream);
+/* ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) (src/ORBmatcher.cc:290-403) for n_jobs calls at once.  Job j = slot
+ * kf_index[j] (sd_batch_assign_grid must have run on it), Scw_host[j], entries [cand_offset[j], cand_offset[j+1]) of d_cand_point (indices
+ * into d_points / d_point_desc as for sd_batch_fuse, -1 where isBad()) and row j of d_matched ([n_jobs][cap] i32, the incoming vpMatched:
+ * -1 NULL, a point index, or -2 for a point outside the table).  A candidate that occurs in its job's row is in spAlreadyFound and is
+ * skipped; a feature whose row value is not -1 is never a target.  The function is a sequential greedy (a feature taken by an earlier
+ * candidate is invisible to the later ones) and the result is what the sequential loop gives.
+ * Outputs (library-owned device memory, valid until the next call): d_assigned [n_jobs][cap] = position in the job's list of the
+ * candidate that took the feature, -1 elsewhere (features matched on entry stay -1); d_best[e] = (bestIdx, bestDist) as found at the
+ * entry's turn, (-1, 256) when it was rejected or nothing passed; d_nmatches[j] = the return value.
+ * Per candidate the 64 smallest (distance, visiting order) keys of its window are kept.  A candidate that finds all 64 taken while its
+ * window held more is not answered: the next sd_batch_sync (and with it every download) returns SD_ERR_UNSUPPORTED with flag 128.
+ * An entry outside [-1, n_points) or a d_matched value outside [-2, n_points) on any feature of a job's slot (a job with at least one
+ * entry scans its whole row) is read as -1 and turns the downloads of the call into SD_ERR_INVALID.  Other errors as for sd_batch_fuse
+ * (th <= 0 is SD_ERR_INVALID).  No host synchronisation inside the call, except when a call has more jobs or entries than any before it:
+ * the library-owned tables then grow, and the stream is synchronised once before the old ones are freed (as in sd_batch_fuse). */
+int sd_batch_search_by_projection_sim3(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Scw_host, const int32_t* cand_offset,
+                                       const int32_t* d_cand_point, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
+                                       const int32_t* d_matched, const sd_camera* cam, int th, int32_t** d_assigned, int32_t** d_best,
+                                       int32_t** d_nmatches, void* stream);
+/* assigned (nullable) with room for cap >= kp_capacity entries, best [n][2] (nullable) with room for cap_entries pairs; SD_ERR_CAPACITY
+ * when a buffer that was given is too small.  n_entries = the job's entry count, nmatches = its return value. */
+int sd_batch_download_projection_sim3(sd_batch* b, int job, int32_t* assigned, int cap, int32_t* best, int cap_entries, int* n_entries,
+                                      int* nmatches);
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307) for n_points points in one launch (the "Update points" loop of
  * SearchInNeighbors, Replace, CreateNewMapPoints).  Point p owns observations [d_obs_offset[p], d_obs_offset[p+1]) of d_obs_desc (32 B
  * each, 16-byte aligned) in the order the reference fills vDescriptors: the caller's std::map order, bad keyframes left out.

@@ -24,6 +24,8 @@
 #include "k_fuse.h"
 #include "k_ba.h"
 #include "k_sim3.h"
+#include "k_loop.h"
+#include "sd_scw.h"
 #include "sd_common.h"
 #include "sd_vocab.h"
 
@@ -48,11 +50,11 @@ struct sd_extractor {
     SdParams prm;
 };
 
-enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_TRI_M, K_TRI_T, K_TRI_R, K_FUSE_S, K_FUSE_R, K_SIM3_M, K_SIM3_S, K_SIM3_A, K_COUNT };
+enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_TRI_M, K_TRI_T, K_TRI_R, K_FUSE_S, K_FUSE_R, K_SIM3_M, K_SIM3_S, K_SIM3_A, K_LOOP_BOW, K_LOOP_F, K_LOOP_P, K_LOOP_A, K_COUNT };
 static const char* kKernelNames[K_COUNT] = {"k_pyr_level0", "k_pyr_level", "k_fast_cells", "k_quadtree", "k_orient",
                                             "k_blur", "k_describe", "k_stereo_match", "k_stereo_filter", "k_rgbd",
                                             "k_grid_cells", "k_unproject", "k_proj_candidates", "k_proj_resolve",
-                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select", "k_tri_match", "k_tri_triangulate", "k_tri_resolve", "k_fuse_search", "k_fuse_resolve", "k_sim3_mark", "k_sim3_search", "k_sim3_agree"};
+                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select", "k_tri_match", "k_tri_triangulate", "k_tri_resolve", "k_fuse_search", "k_fuse_resolve", "k_sim3_mark", "k_sim3_search", "k_sim3_agree", "k_search_by_bow_kf", "k_loop_search<0>", "k_loop_search<1>", "k_loop_assign"};
 
 #define SD_PT_TW 256
 #define SD_PT_TH 16
@@ -137,6 +139,12 @@ struct sd_batch {
     // sd_batch_search_by_sim3: pair table and per-pair rows [pairs][cap], grown with the largest call seen
     SdDevBuf<SdSim3Pair> d_s3Pairs; SdDevBuf<int> d_s3Match1, d_s3Match2, d_s3Match12, d_s3Found, d_s3Err; SdDevBuf<uint8_t> d_s3Already;
     int s3PairCap = 0, s3Pairs = 0; std::vector<SdSim3Pair> s3Host;
+    // the Scw matchers of loop closing (k_loop.h), grown with the largest call seen: the decomposed poses of sd_batch_fuse_sim3 and
+    // sd_batch_search_by_projection_sim3 (host staging that outlives the upload), and for the projection its job tables, the kept keys
+    // per candidate, the per-entry results and the per-job rows [jobs][cap]
+    std::vector<float> loopT; std::vector<int32_t> loopOff;
+    SdDevBuf<int> d_loopJobs; SdDevBuf<float> d_loopT; SdDevBuf<int> d_loopNm; SdDevBuf<int> d_loopAssigned; SdDevBuf<int> d_loopErr;
+    SdDevBuf<unsigned> d_loopList; SdDevBuf<int> d_loopListN; SdDevBuf<int2> d_loopBest; int loopJobCap = 0, loopEntryCap = 0, loopJobs = 0;
     std::vector<sd_camera> pairCam, hPoseCam; std::vector<int32_t> hPoseMap;
     int nPairs = 0;
     int dlPairs = 0;          // pairs sd_batch_download_matches may read (the tracker also keeps pairs at [n_lanes, 2 * n_lanes))
@@ -724,7 +732,7 @@ int sd_batch_sync(sd_batch* b)
     HIPCHK(hipMemcpy(&err, b->d_err, 4, hipMemcpyDeviceToHost));
     if (err) {
         (void)hipMemset(b->d_err, 0, 4);
-        return set_err(SD_ERR_UNSUPPORTED, "device capacity exceeded: 1|2 quadtree nodes, 4 projection candidates, 8|16|32 box tables, 64 local-map candidates (flag " + std::to_string(err) + ")");
+        return set_err(SD_ERR_UNSUPPORTED, "device capacity exceeded: 1|2 quadtree nodes, 4 projection candidates, 8|16|32 box tables, 64 local-map candidates, 128 Sim3 projection keys (flag " + std::to_string(err) + ")");
     }
     return SD_OK;
 }
@@ -1731,10 +1739,12 @@ static int ensure_fuse(sd_batch* b, int n_jobs, int total, bool firstInMemory, h
     return SD_OK;
 }
 
-int sd_batch_fuse(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Tcw_host, const int32_t* cand_offset,
-                  const int32_t* d_cand_point, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
-                  const uint8_t* d_kf_state, const sd_camera* cam, float th, int32_t** d_best, sd_fuse_hit** d_hits,
-                  int32_t** d_nfused, void* stream_)
+// sim3 = the job's pose is a similarity Scw (ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)): decomposed here (sd_scw.h), searched
+// by k_loop_search<0>; the tail is the same k_fuse_resolve
+static int fuse_impl(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Tcw_host, const int32_t* cand_offset,
+                     const int32_t* d_cand_point, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
+                     const uint8_t* d_kf_state, const sd_camera* cam, float th, int32_t** d_best, sd_fuse_hit** d_hits,
+                     int32_t** d_nfused, void* stream_, bool sim3)
 {
     static_assert(sizeof(SdFuseHit) == sizeof(sd_fuse_hit) && sizeof(sd_fuse_hit) == 20, "sd_fuse_hit is 20 bytes");
     if (d_best) *d_best = nullptr;
@@ -1772,8 +1782,19 @@ int sd_batch_fuse(sd_batch* b, int n_jobs, const int32_t* kf_index, const float*
     b->fuseOff.assign(cand_offset, cand_offset + n_jobs + 1);
     HIPCHK(hipMemcpyAsync(dFrameOf, kf_index, (size_t)n_jobs * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dOff, cand_offset, ((size_t)n_jobs + 1) * 4, hipMemcpyHostToDevice, s));
+    if (sim3) {
+        b->loopT.resize((size_t)n_jobs * 16);
+        for (int j = 0; j < n_jobs; j++) sd_scw_decompose(Tcw_host + (size_t)j * 16, b->loopT.data() + (size_t)j * 16);
+        Tcw_host = b->loopT.data();
+    }
     HIPCHK(hipMemcpyAsync(b->d_fuseT, Tcw_host, (size_t)n_jobs * 64, hipMemcpyHostToDevice, s));
-    if (maxM > 0) {
+    if (maxM > 0 && sim3) {
+        ProfScope ps(b, s, K_LOOP_F);
+        hipLaunchKernelGGL(k_loop_search<0>, dim3((maxM + 3) / 4, n_jobs), dim3(256), 0, s, KPUN(b), b->d_desc, b->d_uright, b->d_sortedIdx, b->d_cellStart,
+                           b->d_count, (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->d_fuseT, (const int*)nullptr,
+                           b->d_fuseBest.get(), (unsigned*)nullptr, (int*)nullptr, b->d_fuseErr.get(), level_tables(b), to_cam(cam), th, cap);
+        LAUNCH_CHECK("k_loop_search<0>");
+    } else if (maxM > 0) {
         ProfScope ps(b, s, K_FUSE_S);
         hipLaunchKernelGGL(k_fuse_search, dim3((maxM + 3) / 4, n_jobs), dim3(256), 0, s, KPUN(b), b->d_desc, b->d_uright, b->d_sortedIdx, b->d_cellStart,
                            (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->d_fuseT, b->d_fuseBest.get(),
@@ -1791,6 +1812,170 @@ int sd_batch_fuse(sd_batch* b, int n_jobs, const int32_t* kf_index, const float*
     if (d_best) *d_best = (int32_t*)b->d_fuseBest.get();
     if (d_hits) *d_hits = (sd_fuse_hit*)b->d_fuseHits.get();
     if (d_nfused) *d_nfused = b->d_fuseN;
+    return SD_OK;
+}
+
+int sd_batch_fuse(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Tcw_host, const int32_t* cand_offset,
+                  const int32_t* d_cand_point, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
+                  const uint8_t* d_kf_state, const sd_camera* cam, float th, int32_t** d_best, sd_fuse_hit** d_hits,
+                  int32_t** d_nfused, void* stream_)
+{
+    return fuse_impl(b, n_jobs, kf_index, Tcw_host, cand_offset, d_cand_point, d_points, d_point_desc, n_points, d_kf_state, cam, th, d_best, d_hits,
+                     d_nfused, stream_, false);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// LoopClosing::ComputeSim3 / SearchAndFuse: the matchers that take a similarity or two keyframes (k_loop.h)
+// ---------------------------------------------------------------------------------------------------------
+// ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1134-1257)
+int sd_batch_fuse_sim3(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Scw_host, const int32_t* cand_offset,
+                       const int32_t* d_cand_point, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
+                       const uint8_t* d_kf_state, const sd_camera* cam, float th, int32_t** d_best, sd_fuse_hit** d_hits,
+                       int32_t** d_nfused, void* stream_)
+{
+    return fuse_impl(b, n_jobs, kf_index, Scw_host, cand_offset, d_cand_point, d_points, d_point_desc, n_points, d_kf_state, cam, th, d_best, d_hits,
+                     d_nfused, stream_, true);
+}
+
+// ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches12) (src/ORBmatcher.cc:679-812)
+int sd_batch_search_by_bow_kf(sd_batch* b, int n_pairs, const int32_t* kf1_index, const int32_t* kf2_index, const uint8_t* d_valid1,
+                              const uint8_t* d_valid2, float nnratio, int check_orientation, void* stream_)
+{
+    if (!b || n_pairs < 0 || n_pairs > b->maxImages || (n_pairs > 0 && (!kf1_index || !kf2_index)))
+        return set_err(SD_ERR_INVALID, "bad search_by_bow_kf arguments");
+    std::vector<int2> idx(n_pairs);
+    for (int p = 0; p < n_pairs; p++) {
+        if (kf1_index[p] < 0 || kf1_index[p] >= b->maxImages || kf2_index[p] < 0 || kf2_index[p] >= b->maxImages)
+            return set_err(SD_ERR_INVALID, "search_by_bow_kf: slot out of range");
+        idx[p] = make_int2(kf1_index[p], kf2_index[p]);
+    }
+    for (int p = 0; p < n_pairs; p++) {
+        if (!slot_ok(b, kf1_index[p]) || !slot_ok(b, kf2_index[p])) return set_err(SD_ERR_STATE, "search_by_bow_kf: slot holds no results");
+        if (!b->d_bowWordF || !b->bowValid[kf1_index[p]] || !b->bowValid[kf2_index[p]])
+            return set_err(SD_ERR_STATE, "search_by_bow_kf: sd_batch_compute_bow has not run on these slots");
+    }
+    const int cap = b->plan.kpCap;
+    const size_t lds = (size_t)cap * 4 + 2 * (size_t)cap + 16;
+    if (lds > SD_LDS_MAX_BYTES - 1024) return set_err(SD_ERR_UNSUPPORTED, "search_by_bow_kf: the key-point capacity exceeds the LDS tables");
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
+    b->lastStream = s;
+    b->nPairs = 0; b->dlPairs = 0;
+    if (n_pairs == 0) return SD_OK;
+    HIPCHK(hipMemcpyAsync(b->d_pairIdx, idx.data(), (size_t)n_pairs * sizeof(int2), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(b->d_npairs, 0, (size_t)n_pairs * 4, s));
+    {
+        if (lds > 64 * 1024) HIPCHK(sd_raise_lds_limit((const void*)k_search_by_bow_kf, (int)lds));
+        ProfScope ps(b, s, K_LOOP_BOW);
+        hipLaunchKernelGGL(k_search_by_bow_kf, dim3(n_pairs), dim3(64 * SD_BOW_WAVES), lds, s, KPUN(b), b->d_desc, b->d_count, b->d_fvFeat, b->d_fvRunStart,
+                           b->d_fvRunNode, b->d_bowMeta, d_valid1, d_valid2, b->d_pairIdx, cap, nnratio, check_orientation, b->d_match, b->d_nmatch);
+        LAUNCH_CHECK("k_search_by_bow_kf");
+    }
+    b->nPairs = n_pairs; b->dlPairs = n_pairs;
+    return SD_OK;
+}
+
+// Job tables and scratch of sd_batch_search_by_projection_sim3: they grow with the largest call seen (old ones freed first), as ensure_fuse does
+static int ensure_loop(sd_batch* b, int n_jobs, int total, hipStream_t s)
+{
+    const size_t cap = b->plan.kpCap;
+    if (!b->d_loopErr) { HIPCHK(b->d_loopErr.alloc(4)); HIPCHK(hipMemset(b->d_loopErr, 0, 4)); }
+    if (n_jobs > b->loopJobCap || total > b->loopEntryCap) HIPCHK(hipStreamSynchronize(s));
+    if (n_jobs > b->loopJobCap) {
+        const int want = std::max(n_jobs, 2 * b->loopJobCap);
+        b->loopJobCap = 0; b->d_loopJobs.reset(); b->d_loopT.reset(); b->d_loopNm.reset(); b->d_loopAssigned.reset();
+        HIPCHK(b->d_loopJobs.alloc(((size_t)2 * want + 1) * 4)); HIPCHK(b->d_loopT.alloc((size_t)want * 64)); HIPCHK(b->d_loopNm.alloc((size_t)want * 4));
+        HIPCHK(b->d_loopAssigned.alloc((size_t)want * cap * 4));
+        b->loopJobCap = want;
+    }
+    if (total > b->loopEntryCap) {
+        const int want = std::max(total, 2 * b->loopEntryCap);
+        b->loopEntryCap = 0; b->d_loopList.reset(); b->d_loopListN.reset(); b->d_loopBest.reset();
+        HIPCHK(b->d_loopList.alloc((size_t)want * SD_PROJ_K * 4)); HIPCHK(b->d_loopListN.alloc((size_t)want * 4)); HIPCHK(b->d_loopBest.alloc((size_t)want * sizeof(int2)));
+        b->loopEntryCap = want;
+    }
+    return SD_OK;
+}
+
+// ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched, int th)
+// (src/ORBmatcher.cc:290-403)
+int sd_batch_search_by_projection_sim3(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Scw_host, const int32_t* cand_offset,
+                                       const int32_t* d_cand_point, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
+                                       const int32_t* d_matched, const sd_camera* cam, int th, int32_t** d_assigned, int32_t** d_best,
+                                       int32_t** d_nmatches, void* stream_)
+{
+    if (d_assigned) *d_assigned = nullptr;
+    if (d_best) *d_best = nullptr;
+    if (d_nmatches) *d_nmatches = nullptr;
+    if (!b || n_jobs < 0 || n_jobs > 65535 || n_points < 0 || !cam_ok(cam) || th <= 0 || (n_jobs > 0 && (!kf_index || !Scw_host || !cand_offset || !d_matched)))
+        return set_err(SD_ERR_INVALID, "bad search_by_projection_sim3 arguments");
+    b->loopJobs = 0;
+    if (n_jobs == 0) return SD_OK;
+    if (cand_offset[0] != 0) return set_err(SD_ERR_INVALID, "search_by_projection_sim3: candidate offsets must start at 0 and ascend");
+    int maxM = 0;
+    for (int j = 0; j < n_jobs; j++) {
+        const int M = cand_offset[j + 1] - cand_offset[j];
+        if (M < 0 || cand_offset[j] < 0) return set_err(SD_ERR_INVALID, "search_by_projection_sim3: candidate offsets must start at 0 and ascend");
+        maxM = std::max(maxM, M);
+        if (kf_index[j] < 0 || kf_index[j] >= b->maxImages) return set_err(SD_ERR_INVALID, "search_by_projection_sim3: slot out of range");
+    }
+    for (int j = 0; j < n_jobs; j++) {
+        if (!slot_ok(b, kf_index[j])) return set_err(SD_ERR_STATE, "search_by_projection_sim3: slot holds no results");
+        if (!b->gridValid[kf_index[j]]) return set_err(SD_ERR_STATE, "search_by_projection_sim3: sd_batch_assign_grid has not run on this slot");
+    }
+    const int total = cand_offset[n_jobs];
+    if (total > 0 && (!d_cand_point || !d_points || !d_point_desc || n_points == 0))
+        return set_err(SD_ERR_INVALID, "search_by_projection_sim3: entries but no map points given");
+    const int cap = b->plan.kpCap;
+    if (cap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
+    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
+    b->lastStream = s;
+    int rc = ensure_loop(b, n_jobs, total, s);
+    if (rc != SD_OK) return rc;
+    int* dFrameOf = b->d_loopJobs;
+    int* dOff = b->d_loopJobs + n_jobs;
+    b->loopOff.assign(cand_offset, cand_offset + n_jobs + 1);
+    b->loopT.resize((size_t)n_jobs * 16);
+    for (int j = 0; j < n_jobs; j++) sd_scw_decompose(Scw_host + (size_t)j * 16, b->loopT.data() + (size_t)j * 16);
+    HIPCHK(hipMemsetAsync(b->d_loopErr, 0, 4, s));               // the flag belongs to this call: every job's download reports it
+    HIPCHK(hipMemcpyAsync(dFrameOf, kf_index, (size_t)n_jobs * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dOff, cand_offset, ((size_t)n_jobs + 1) * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b->d_loopT, b->loopT.data(), (size_t)n_jobs * 64, hipMemcpyHostToDevice, s));
+    if (maxM > 0) {
+        ProfScope ps(b, s, K_LOOP_P);
+        hipLaunchKernelGGL(k_loop_search<1>, dim3((maxM + 3) / 4, n_jobs), dim3(256), 0, s, KPUN(b), b->d_desc, b->d_uright, b->d_sortedIdx, b->d_cellStart,
+                           b->d_count, (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->d_loopT, d_matched,
+                           (int2*)nullptr, b->d_loopList.get(), b->d_loopListN.get(), b->d_loopErr.get(), level_tables(b), to_cam(cam), (float)th, cap);
+        LAUNCH_CHECK("k_loop_search<1>");
+    }
+    {
+        ProfScope ps(b, s, K_LOOP_A);
+        hipLaunchKernelGGL(k_loop_assign, dim3(n_jobs), dim3(64), (size_t)((cap + 31) / 32) * 4 + 16, s, dOff, b->d_loopList.get(), b->d_loopListN.get(), cap,
+                           b->d_loopAssigned.get(), b->d_loopBest.get(), b->d_loopNm.get(), b->d_err.get());
+        LAUNCH_CHECK("k_loop_assign");
+    }
+    b->loopJobs = n_jobs;
+    if (d_assigned) *d_assigned = b->d_loopAssigned;
+    if (d_best) *d_best = (int32_t*)b->d_loopBest.get();
+    if (d_nmatches) *d_nmatches = b->d_loopNm;
+    return SD_OK;
+}
+
+int sd_batch_download_projection_sim3(sd_batch* b, int job, int32_t* assigned, int cap, int32_t* best, int cap_entries, int* n_entries, int* nmatches)
+{
+    if (!b || !n_entries || !nmatches || cap_entries < 0) return set_err(SD_ERR_INVALID, "bad download_projection_sim3 arguments");
+    if (job < 0 || job >= b->loopJobs) return set_err(SD_ERR_INVALID, "download_projection_sim3: no such job in the last sd_batch_search_by_projection_sim3");
+    int rc = sd_batch_sync(b);
+    if (rc != SD_OK) return rc;
+    int err = 0;
+    HIPCHK(hipMemcpy(&err, b->d_loopErr, 4, hipMemcpyDeviceToHost));
+    if (err) return set_err(SD_ERR_INVALID, "search_by_projection_sim3: a candidate or a matched entry names a point outside its table");
+    const int e0 = b->loopOff[job], n = b->loopOff[job + 1] - e0;
+    *n_entries = n;
+    HIPCHK(hipMemcpy(nmatches, b->d_loopNm + job, 4, hipMemcpyDeviceToHost));
+    if (best && n > cap_entries) return set_err(SD_ERR_CAPACITY, "projection_sim3 result buffers too small");
+    if (assigned && cap < b->plan.kpCap) return set_err(SD_ERR_CAPACITY, "the assigned row needs kp_capacity entries");
+    if (assigned) HIPCHK(hipMemcpy(assigned, b->d_loopAssigned + (size_t)job * b->plan.kpCap, (size_t)b->plan.kpCap * 4, hipMemcpyDeviceToHost));
+    if (best && n > 0) HIPCHK(hipMemcpy(best, b->d_loopBest + e0, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
     return SD_OK;
 }
 

@@ -144,6 +144,10 @@ def lib():
         L.sd_batch_download_new_map_points.argtypes = [vp, i, vp, i, C.POINTER(i)]
         L.sd_batch_fuse.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, i, vp, vp, f, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
         L.sd_batch_download_fuse.argtypes = [vp, i, vp, vp, i, C.POINTER(i), C.POINTER(i)]
+        L.sd_batch_fuse_sim3.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, i, vp, vp, f, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
+        L.sd_batch_search_by_bow_kf.argtypes = [vp, i, vp, vp, vp, vp, f, i, vp]
+        L.sd_batch_search_by_projection_sim3.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, i, vp, vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
+        L.sd_batch_download_projection_sim3.argtypes = [vp, i, vp, i, vp, i, C.POINTER(i), C.POINTER(i)]
         L.sd_batch_search_by_sim3.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp, vp]
         L.sd_batch_download_sim3_matches.argtypes = [vp, i, vp, vp, vp, i, C.POINTER(i)]
         L.sd_distinctive_descriptors_device.argtypes = [i, vp, vp, vp, vp, vp]
@@ -484,6 +488,54 @@ class Batch:
         best = np.zeros((max(n, 1), 2), np.int32); hits = np.zeros(max(n, 1), FUSE_HIT_DTYPE); ne, nf = C.c_int(), C.c_int()
         check(lib().sd_batch_download_fuse(self.h, job, _p(best), _p(hits), n, C.byref(ne), C.byref(nf)))
         return best[:ne.value].copy(), hits[:nf.value].copy(), nf.value
+
+    # -- LoopClosing::ComputeSim3 / SearchAndFuse: the matchers that take a similarity Scw or two keyframes
+    def fuse_sim3(self, kf_index, Scw, cand_offset, d_cand_point, d_points, d_point_desc, cam, th=4.0, d_kf_state=None, stream=None, *, n_points):
+        """Job j = Fuse(slot kf_index[j], Scw[j], entries, th, vpReplacePoint): the tables and outputs of fuse(), the search without the
+        chi-square and uRight tests.  Results through download_fuse."""
+        c = camera_array(cam)
+        ki = np.ascontiguousarray(kf_index, np.int32).reshape(-1); off = np.ascontiguousarray(cand_offset, np.int32).reshape(-1)
+        T = np.ascontiguousarray(Scw, np.float32).reshape(-1, 16)
+        if len(off) != len(ki) + 1 or len(T) != len(ki):
+            raise ValueError("fuse_sim3: one slot and one similarity per job, one offset more than jobs")
+        d_best, d_hits, d_nfused = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().sd_batch_fuse_sim3(self.h, len(ki), _p(ki), _p(T), _p(off), C.c_void_p(d_cand_point or 0), C.c_void_p(d_points or 0),
+                                       C.c_void_p(d_point_desc or 0), int(n_points), C.c_void_p(d_kf_state or 0), _p(c), C.c_float(th),
+                                       C.byref(d_best), C.byref(d_hits), C.byref(d_nfused), C.c_void_p(stream or 0)))
+        self._fuse_sizes = np.diff(off)
+        return d_best.value, d_hits.value, d_nfused.value
+
+    def search_by_bow_kf(self, kf1_index, kf2_index, nnratio, checkOrientation=True, d_valid1=None, d_valid2=None, stream=None):
+        """Pair p = SearchByBoW(slot kf1_index[p], slot kf2_index[p], vpMatches12) (compute_bow must have run on both).  d_valid1 / d_valid2:
+        [n_pairs][cap] u8 device tables or None.  Results: download_matches(pair) -> match[idx1] = idx2 or -1, no pairs, nmatches."""
+        k1 = np.ascontiguousarray(kf1_index, np.int32).reshape(-1); k2 = np.ascontiguousarray(kf2_index, np.int32).reshape(-1)
+        if len(k1) != len(k2):
+            raise ValueError("search_by_bow_kf: one slot per pair and side")
+        check(lib().sd_batch_search_by_bow_kf(self.h, len(k1), _p(k1), _p(k2), C.c_void_p(d_valid1 or 0), C.c_void_p(d_valid2 or 0),
+                                              C.c_float(nnratio), int(checkOrientation), C.c_void_p(stream or 0)))
+
+    def search_by_projection_sim3(self, kf_index, Scw, cand_offset, d_cand_point, d_points, d_point_desc, d_matched, cam, th=10, stream=None, *,
+                                  n_points):
+        """Job j = SearchByProjection(slot kf_index[j], Scw[j], entries, vpMatched = row j of d_matched ([n_jobs][cap] i32), th).
+        -> (d_assigned, d_best, d_nmatches) device pointers; results through download_projection_sim3."""
+        c = camera_array(cam)
+        ki = np.ascontiguousarray(kf_index, np.int32).reshape(-1); off = np.ascontiguousarray(cand_offset, np.int32).reshape(-1)
+        T = np.ascontiguousarray(Scw, np.float32).reshape(-1, 16)
+        if len(off) != len(ki) + 1 or len(T) != len(ki):
+            raise ValueError("search_by_projection_sim3: one slot and one similarity per job, one offset more than jobs")
+        d_assigned, d_best, d_nm = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().sd_batch_search_by_projection_sim3(self.h, len(ki), _p(ki), _p(T), _p(off), C.c_void_p(d_cand_point or 0), C.c_void_p(d_points or 0),
+                                                       C.c_void_p(d_point_desc or 0), int(n_points), C.c_void_p(d_matched or 0), _p(c), int(th),
+                                                       C.byref(d_assigned), C.byref(d_best), C.byref(d_nm), C.c_void_p(stream or 0)))
+        self._loop_sizes = np.diff(off)
+        return d_assigned.value, d_best.value, d_nm.value
+
+    def download_projection_sim3(self, job):
+        """Job `job` of the last search_by_projection_sim3 -> (assigned (cap,) i32, best (n, 2) i32, nmatches)."""
+        n = int(self._loop_sizes[job]) if 0 <= job < len(getattr(self, "_loop_sizes", ())) else 0
+        assigned = np.zeros(self.cap, np.int32); best = np.zeros((max(n, 1), 2), np.int32); ne, nm = C.c_int(), C.c_int()
+        check(lib().sd_batch_download_projection_sim3(self.h, job, _p(assigned), self.cap, _p(best), n, C.byref(ne), C.byref(nm)))
+        return assigned, best[:ne.value].copy(), nm.value
 
     # -- ORBmatcher::SearchBySim3 (LoopClosing::ComputeSim3)
     def search_by_sim3(self, kf1_index, kf2_index, Tcw1, Tcw2, s12, R12, t12, cam, d_points, d_point_desc, d_kf1_point, d_kf2_point,
