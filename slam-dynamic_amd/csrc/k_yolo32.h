@@ -37,7 +37,8 @@ struct SdConvArgsF {
 // The measurements against the tiles tried and dropped (8-wave 128 x 256, 32-channel steps, 8-wave small tiles): DESIGN.md 4.1.
 // LDS holds TWO stages: while the MFMAs of stage s run, the tiles of stage s + 1 (fetched into registers one
 // step earlier) are written to the other buffer and the global loads of stage s + 2 are issued -- one barrier per step, and
-// neither the address arithmetic of the gather nor the LDS writes sit between two barriers with the MFMA pipe idle.
+// neither the address arithmetic of the gather nor the LDS writes sit between two barriers with the MFMA pipe idle.  Behind the two
+// stages lie the tile's BM bias floats (SD_F32_LDS counts them), written once by the prologue and read by the epilogue.
 template <int BK, int WM, int MT, int NW>
 __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 3 : 2)) k_conv_f32(SdConvArgsF A)
 {
@@ -171,8 +172,18 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     // DEEP: stage s lives in register set s & 1 from its request (two steps ahead: ~12 000 cycles with three waves per SIMD, against an
     // L2 / HBM latency of several thousand under load -- with ONE step of distance the ds_writes waited on their loads for 11 % of
     // the kernel time) until it is written to LDS buffer s & 1 during step s - 1.
+    // The tile's BM bias floats are staged in LDS behind the two stages (requested first, written with stage 0): the epilogue reads them with
+    // ds_read_b128, which counts in lgkmcnt -- a bias load from global memory there shares vmcnt with the tile's stores and made every
+    // store wait for the one before it (see the epilogue).
+    float* const sBias = smemf + 2 * STAGE;
+    sd_f4 bq = sd_f4{0.f, 0.f, 0.f, 0.f};
+    if (tid < BM / 4 && co0 + 4 * tid < A.cout) bq = *(const sd_f4*)(A.bias + co0 + 4 * tid);     // bias rows are padded to the filter tile
+    // The order below exposes two latencies (stage 1 is requested only behind store(0, 0)'s wait).  Requesting stages 0 AND 1 before the first
+    // wait was measured and is not kept: headline 1085.2 / 1086.2 frames/s against 1087.0 / 1087.4 with this order in alternating runs on
+    // one box, per-layer fixed cost the same (profiles/conv_f32_epilogue_layers_steps.txt) -- the two other workgroups of the CU cover it.
     fetch(0);
     store(0, 0);
+    if (tid < BM / 4) *(sd_f4*)(sBias + 4 * tid) = bq;
     if (ksteps > 1) fetch(NSET - 1);
     if (DEEP && ksteps > 2) fetch(0);
     __syncthreads();
@@ -225,84 +236,115 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
         float* T = smemf + wv * 32 * TLD;                     // wave-private: no workgroup barrier inside the epilogue
         const int piece = lane % (TWD / 4), prow = lane / (TWD / 4);
         const int cob = co0 + TWD * wm + 4 * piece;           // first of this lane's four output channels
-        sd_f4 bias4 = sd_f4{0.f, 0.f, 0.f, 0.f};
-        if (cob < A.cout) bias4 = *(const sd_f4*)(A.bias + cob);                       // bias rows are padded to the filter tile
+        const sd_f4 bias4 = *(const sd_f4*)(sBias + TWD * wm + 4 * piece);             // staged by the prologue: no wait on vector memory
         __syncthreads();                                      // every wave's last fragment reads are done: the staging buffers are free
+        // The shortcut reads of BOTH half tiles are requested up front and waited for once; no load from global memory sits between two of the
+        // tile's stores (stores count in vmcnt: a load behind a store waits for that store to be acknowledged).  `inside` as below.
+        auto tail = [&](const bool res, const bool inside) {
+            sd_f4 rr[2][32 / PPI];
+            if (res) {
 #pragma unroll
-        for (int n = 0; n < 2; n++) {
+                for (int n = 0; n < 2; n++)
 #pragma unroll
-            for (int m = 0; m < MT; m++)
-#pragma unroll
-                for (int g = 0; g < 4; g++)
-                    *(sd_f4*)(T + r32 * TLD + 32 * m + 8 * g + 4 * h) = sd_f4{acc[m][n][4 * g], acc[m][n][4 * g + 1], acc[m][n][4 * g + 2], acc[m][n][4 * g + 3]};
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const int pb = pix0 + 64 * wn + 32 * n;
-            sd_f4 rr[32 / PPI];
-#pragma unroll
-            for (int it = 0; it < 32 / PPI; it++) {            // all shortcut reads requested before the first one is used
-                const int p = pb + PPI * it + prow;
-                rr[it] = sd_f4{0.f, 0.f, 0.f, 0.f};
-                if (A.res && p < npix && cob < A.cout) rr[it] = *(const sd_f4*)(A.res + (size_t)p * A.resStride + cob);
+                    for (int it = 0; it < 32 / PPI; it++) {
+                        const int p = pix0 + 64 * wn + 32 * n + PPI * it + prow;
+                        rr[n][it] = sd_f4{0.f, 0.f, 0.f, 0.f};
+                        if (inside || (p < npix && cob < A.cout)) rr[n][it] = *(const sd_f4*)(A.res + (size_t)p * A.resStride + cob);
+                    }
+                __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0)
             }
 #pragma unroll
-            for (int it = 0; it < 32 / PPI; it++) {
-                const int pl = PPI * it + prow, p = pb + pl;
-                if (p >= npix || cob >= A.cout) continue;
-                const sd_f4 a = *(const sd_f4*)(T + pl * TLD + 4 * piece);
-                sd_f4 v;
+            for (int n = 0; n < 2; n++) {
 #pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    float x = a[e] + bias4[e];
-                    if (A.leaky) x = x > 0.f ? x : 0.1f * x;
-                    v[e] = x + rr[it][e];
-                }
-                float* dst = A.out + (size_t)p * A.outStride + cob;
-                if (cob + 3 < A.cout) *(sd_f4*)dst = v;
-                else for (int e = 0; e < 4 && cob + e < A.cout; e++) dst[e] = v[e];
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-    } else {
-        // ---- epilogue: D column = pixel (lane & 31), rows = filters (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  All shortcut reads are
-        // requested before the first one is used (one memory round trip, not one per 16-byte piece).
-        sd_f4 rr[2][MT][4];
+                for (int m = 0; m < MT; m++)
 #pragma unroll
-        for (int n = 0; n < 2; n++) {
-            const int p = pix0 + 64 * wn + 32 * n + r32;
+                    for (int g = 0; g < 4; g++)
+                        *(sd_f4*)(T + r32 * TLD + 32 * m + 8 * g + 4 * h) = sd_f4{acc[m][n][4 * g], acc[m][n][4 * g + 1], acc[m][n][4 * g + 2], acc[m][n][4 * g + 3]};
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const int pb = pix0 + 64 * wn + 32 * n;
 #pragma unroll
-            for (int m = 0; m < MT; m++)
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const int co = co0 + 32 * MT * wm + 32 * m + 8 * g + 4 * h;
-                    rr[n][m][g] = sd_f4{0.f, 0.f, 0.f, 0.f};
-                    if (A.res && p < npix && co < A.cout) rr[n][m][g] = *(const sd_f4*)(A.res + (size_t)p * A.resStride + co);
-                }
-        }
-#pragma unroll
-        for (int n = 0; n < 2; n++) {
-            const int p = pix0 + 64 * wn + 32 * n + r32;
-            if (p >= npix) continue;
-#pragma unroll
-            for (int m = 0; m < MT; m++)
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const int co = co0 + 32 * MT * wm + 32 * m + 8 * g + 4 * h;
-                    if (co >= A.cout) continue;
+                for (int it = 0; it < 32 / PPI; it++) {
+                    const int pl = PPI * it + prow, p = pb + pl;
+                    if (!inside && (p >= npix || cob >= A.cout)) continue;
+                    const sd_f4 a = *(const sd_f4*)(T + pl * TLD + 4 * piece);
                     sd_f4 v;
 #pragma unroll
                     for (int e = 0; e < 4; e++) {
-                        float x = acc[m][n][4 * g + e] + A.bias[co + e];            // bias rows are padded to the filter tile
+                        float x = a[e] + bias4[e];
                         if (A.leaky) x = x > 0.f ? x : 0.1f * x;
-                        v[e] = x + rr[n][m][g][e];
+                        v[e] = x + (res ? rr[n][it][e] : 0.f);
                     }
-                    float* dst = A.out + (size_t)p * A.outStride + co;
-                    if (co + 3 < A.cout) *(sd_f4*)dst = v;
-                    else for (int e = 0; e < 4 && co + e < A.cout; e++) dst[e] = v[e];
+                    float* dst = A.out + (size_t)p * A.outStride + cob;
+                    if (inside || cob + 3 < A.cout) *(sd_f4*)dst = v;
+                    else for (int e = 0; e < 4 && cob + e < A.cout; e++) dst[e] = v[e];
                 }
-        }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+        };
+        const bool inside = pix0 + BN <= npix && co0 + BM <= A.cout;
+        if (A.res) { if (inside) tail(true, true); else tail(true, false); }
+        else { if (inside) tail(false, true); else tail(false, false); }
+    } else {
+        // ---- epilogue: D column = pixel (lane & 31), rows = filters (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).  All shortcut reads are
+        // requested before the first one is used (one memory round trip, not one per 16-byte piece).
+        // Then ONE wait on vector memory (none without a shortcut) and the wave's 16 stores back to back: stores count in vmcnt like loads, so
+        // anything read from global memory between two stores -- the bias was, per piece -- waits for the store before it to be acknowledged:
+        // 16 dependent round trips per wave and tile.  The bias comes from LDS (sBias, staged by the prologue).  `inside` (uniform per
+        // workgroup): the tile lies wholly inside the pixels and the filters and needs no predicate per piece; edge tiles and the 255-filter heads
+        // take the predicated form.  Both flags are literals at the call sites.
+        // What it is aimed at: per layer, rate = A s / (s + c) with s the layer's K steps and A = 145 TFLOP/s -- every workgroup spends c = 5 - 8
+        // K steps outside its K loop, whatever the layer (tools/conv_f32_fixed_cost.py).  Measured at batch 128, parent -> this epilogue, one box:
+        // c 5.1 -> 4.4 (1 x 1 256 -> 128), 7.7 -> 6.4 (1 x 1 512 -> 256), 7.0 -> 6.2 (3 x 3 cin 128), 9.5 -> 8.6 (3 x 3 cin 256); the 1 x 1 layers - 3 %,
+        // the 69 layers of this tile 107.8 -> 106.8 ms; headline 1063.1 -> 1076.2 frames/s (+ 1.2 %, four alternating runs each, parent spread 0.2 %:
+        // profiles/conv_f32_epilogue_bench.json, _layers.txt, _isa.txt).  The results are bit for bit the parent's (tests/test_gpu_conv_f32_epilogue.py).
+        // All eight bias pieces of a lane read up front instead of one per piece: 5 VGPRs spilled (168 + scratch) -- not kept.
+        auto tail = [&](const bool res, const bool inside) {
+            sd_f4 rr[2][MT][4];
+            if (res) {
+#pragma unroll
+                for (int n = 0; n < 2; n++) {
+                    const int p = pix0 + 64 * wn + 32 * n + r32;
+#pragma unroll
+                    for (int m = 0; m < MT; m++)
+#pragma unroll
+                        for (int g = 0; g < 4; g++) {
+                            const int co = co0 + 32 * MT * wm + 32 * m + 8 * g + 4 * h;
+                            rr[n][m][g] = sd_f4{0.f, 0.f, 0.f, 0.f};
+                            if (inside || (p < npix && co < A.cout)) rr[n][m][g] = *(const sd_f4*)(A.res + (size_t)p * A.resStride + co);
+                        }
+                }
+                __builtin_amdgcn_s_waitcnt(0x0F70);         // vmcnt(0): every shortcut piece is here before the first store is issued
+            }
+#pragma unroll
+            for (int n = 0; n < 2; n++) {
+                const int p = pix0 + 64 * wn + 32 * n + r32;
+                if (!inside && p >= npix) continue;
+#pragma unroll
+                for (int m = 0; m < MT; m++)
+#pragma unroll
+                    for (int g = 0; g < 4; g++) {
+                        const int cl = 32 * MT * wm + 32 * m + 8 * g + 4 * h, co = co0 + cl;
+                        if (!inside && co >= A.cout) continue;
+                        const sd_f4 b4 = *(const sd_f4*)(sBias + cl);      // per piece: eight more live pieces beside rr and acc spill
+                        sd_f4 v;
+#pragma unroll
+                        for (int e = 0; e < 4; e++) {
+                            float x = acc[m][n][4 * g + e] + b4[e];
+                            if (A.leaky) x = x > 0.f ? x : 0.1f * x;
+                            v[e] = x + (res ? rr[n][m][g][e] : 0.f);
+                        }
+                        float* dst = A.out + (size_t)p * A.outStride + co;
+                        if (inside || co + 3 < A.cout) *(sd_f4*)dst = v;
+                        else for (int e = 0; e < 4 && co + e < A.cout; e++) dst[e] = v[e];
+                    }
+            }
+        };
+        const bool inside = pix0 + BN <= npix && co0 + BM <= A.cout;
+        if (A.res) { if (inside) tail(true, true); else tail(true, false); }
+        else { if (inside) tail(false, true); else tail(false, false); }
     }
 }
-#define SD_F32_LDS(BK, WM, MT, NW) (2 * (32 * (MT) * (WM) + 64 * ((NW) / (WM))) * ((BK) + 4) * 4)
+#define SD_F32_LDS(BK, WM, MT, NW) (2 * (32 * (MT) * (WM) + 64 * ((NW) / (WM))) * ((BK) + 4) * 4 + 32 * (MT) * (WM) * 4)      // two stages + the tile's bias
 
 // blobFromImage as k_blob_from_image, NHWC f32 with 4 channels (R, G, B after swapRB, then a zero)
 __global__ void __launch_bounds__(256) k_blob_from_image_f32(const uint8_t* __restrict__ src, int sw, int sh, size_t sstride, size_t spitch,
