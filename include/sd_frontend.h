@@ -887,6 +887,95 @@ int sd_descriptor_distance(const uint8_t a[32], const uint8_t b[32]); /* host, r
 /* All-pairs Hamming distances of two descriptor sets in HBM: out[i*nb + j] (u16). */
 int sd_hamming_matrix_device(const uint8_t* d_a, int na, const uint8_t* d_b, int nb, uint16_t* d_out, void* stream);
 
+/* ---- KeyFrameDatabase (include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc:33-309) ----
+ * The database both candidate searches read, resident on the device: LoopClosing::DetectLoop (src/LoopClosing.cc:95-230) takes its
+ * candidates from DetectLoopCandidates, Tracking::Relocalization (src/Tracking.cc:2219) from DetectRelocalizationCandidates, and the
+ * matchers above take those candidates as input.  A keyframe is named by a caller-chosen kf_id in [0, max_keyframes).  The device holds
+ * an entry per id (pool offset, word count, insertion sequence number, live flag, mRelocScore, up to SD_KFDB_MAX_NEIGHBOURS neighbour
+ * ids), a pool of BowVectors (u32 word ids ascending, f64 values, laid out as sd_batch_bow_device lays them out) and the work tables of
+ * a call, all allocated by sd_kfdb_create: no call allocates.  There is no inverted file: a query is matched against every live entry
+ * (DESIGN.md Q42), and the order of the reference's lists is reproduced from the sequence numbers.
+ * Capacities: max_pool_words words in the pool, max_queries queries per call of at most max_query_words (<= SD_KFDB_MAX_QUERY_WORDS)
+ * words each.  Anything beyond them is SD_ERR_CAPACITY (or SD_ERR_INVALID for an id or a size that can never be valid) before anything
+ * is launched, never a truncation.  The pool words of an erased entry are NOT reclaimed before sd_kfdb_clear; an entry added from a batch
+ * slot reserves the batch's key-point capacity, because the length of its BowVector is known to the device only.
+ * Ordering: the calls of one database take effect on the device in the order they are made, whichever streams they name (a change of
+ * stream is bridged with an event); the host-side calls (add_host, erase, set_covisible, clear) are enqueued on the stream of the
+ * previous call and do not wait for it.  Like sd_batch, a database is not re-entrant. */
+typedef struct sd_kfdb sd_kfdb;
+#define SD_KFDB_MAX_NEIGHBOURS 10
+#define SD_KFDB_MAX_QUERY_WORDS 16384
+int sd_kfdb_create(sd_kfdb** out, int max_keyframes, int max_pool_words, int max_queries, int max_query_words);
+int sd_kfdb_destroy(sd_kfdb* db);
+int sd_kfdb_clear(sd_kfdb* db);                         /* KeyFrameDatabase::clear; sequence numbers and the pool start again */
+/* KeyFrameDatabase::add(pKF) for n slots of a batch on which sd_batch_compute_bow has run (SD_ERR_STATE otherwise): slot image_index[i]
+ * becomes entry kf_id[i].  A device-to-device copy with no host synchronisation; stream NULL = the batch's.  Adding an id that is live
+ * is SD_ERR_STATE.  Every add takes the next sequence number; an id added again after an erase is a new entry (new sequence number,
+ * mRelocScore +0, no neighbours). */
+int sd_kfdb_add_from_batch(sd_kfdb* db, sd_batch* b, int n, const int32_t* image_index, const int32_t* kf_id, void* stream);
+/* The same from host arrays: word ids strictly ascending (SD_ERR_INVALID otherwise), values taken as given (not normalised). */
+int sd_kfdb_add_host(sd_kfdb* db, int kf_id, const uint32_t* bow_word, const double* bow_value, int n_words);
+/* KeyFrameDatabase::erase(pKF) for n ids; an id that is not live is skipped, as the reference finds nothing to erase. */
+int sd_kfdb_erase(sd_kfdb* db, int n, const int32_t* kf_id);
+/* pKF->GetBestCovisibilityKeyFrames(10) of n live entries as the caller's graph has it now: neigh [n][10] ids in the reference's order,
+ * count [n] <= 10.  Call it wherever KeyFrame::UpdateBestCovisibles runs.  A neighbour that is not live when a query runs is skipped
+ * by that query (the reference's graph holds no erased keyframe). */
+int sd_kfdb_set_covisible(sd_kfdb* db, int n, const int32_t* kf_id, const int32_t* neigh, const int32_t* count);
+/* One entry back (synchronises): words / values (cap_words entries each, nullable), n_words, sequence number, live flag, mRelocScore,
+ * neigh [10] (-1 beyond n_neigh).  An id that was never added reads as all zero. */
+int sd_kfdb_download_entry(sd_kfdb* db, int kf_id, uint32_t* bow_word, double* bow_value, int cap_words, int* n_words, uint32_t* seq, int* live,
+                           float* reloc_score, int32_t* neigh, int* n_neigh);
+
+/* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (:76-197) and DetectRelocalizationCandidates(F) (:199-309) for n_queries
+ * queries in one launch sequence.  Query q is the BowVector at [query_offset[q], query_offset[q+1]) of d_query_word / d_query_value
+ * (query_offset is a HOST array of n_queries + 1 entries, the two d_ arrays device memory; word ids ascending).  The loop form takes per
+ * query min_score[q] (host) and pKF->GetConnectedKeyFrames() as a host CSR of kf ids (excl_offset [n_queries + 1] starting at 0, excl_id;
+ * excl_offset NULL = nothing excluded; an id that is not live is ignored, one outside [0, max_keyframes) is SD_ERR_INVALID).
+ * What the functions compute, with the reference's types: the entries sharing a word with the query (and not excluded), in the order of
+ * (smallest shared word id, sequence number), which is the order of lKFsSharingWords; minCommonWords = (int)(maxCommonWords * 0.8f); an
+ * entry is scored iff its count is > minCommonWords, with si = (float)(-S / 2.0), S the f64 sum, from +0.0 and in ascending word order, of
+ * (fabs(vi - wi) - fabs(vi)) - fabs(wi) over the common words (vi the query's value); the loop form keeps si >= min_score, counts a
+ * neighbour iff it is in the list with a count > minCommonWords, and starts bestAccScore at min_score; the reloc form keeps every scored
+ * entry, counts a neighbour iff it is in the list and starts at 0; a better neighbour replaces pBestKF on > only; minScoreToRetain = 0.75f *
+ * bestAccScore, retention on > only; a repeated pBestKF is returned once, at its first position.
+ * mRelocScore: the reloc form reads the member of neighbours it did not score in this query.  It is +0 when an entry is
+ * added, every reloc query writes it for each entry it scores, and the queries of one call behave as if run one after the other in index
+ * order.  The loop form neither reads nor writes it; apart from this member a query's answer does not depend on what shares its call.
+ * Values must be finite.  Both calls enqueue on `stream` (NULL = the stream of the database's previous call) and return without a host
+ * synchronisation; the results stay in the database until its next query call. */
+int sd_kfdb_detect_loop(sd_kfdb* db, int n_queries, const int32_t* query_offset, const uint32_t* d_query_word, const double* d_query_value,
+                        const float* min_score, const int32_t* excl_offset, const int32_t* excl_id, void* stream);
+int sd_kfdb_detect_reloc(sd_kfdb* db, int n_queries, const int32_t* query_offset, const uint32_t* d_query_word, const double* d_query_value,
+                         void* stream);
+/* The same with query q = the BowVector of batch slot image_index[q] (sd_batch_compute_bow must have run on it: SD_ERR_STATE otherwise;
+ * the batch's key-point capacity must not exceed max_query_words: SD_ERR_CAPACITY).  stream NULL = the batch's. */
+int sd_kfdb_detect_loop_batch(sd_kfdb* db, sd_batch* b, int n_queries, const int32_t* image_index, const float* min_score,
+                              const int32_t* excl_offset, const int32_t* excl_id, void* stream);
+int sd_kfdb_detect_reloc_batch(sd_kfdb* db, sd_batch* b, int n_queries, const int32_t* image_index, void* stream);
+/* The same from a host CSR: uploads, runs, synchronises. */
+int sd_kfdb_detect_loop_host(sd_kfdb* db, int n_queries, const int32_t* query_offset, const uint32_t* query_word, const double* query_value,
+                             const float* min_score, const int32_t* excl_offset, const int32_t* excl_id);
+int sd_kfdb_detect_reloc_host(sd_kfdb* db, int n_queries, const int32_t* query_offset, const uint32_t* query_word, const double* query_value);
+/* What a query leaves.  n_sharing = lKFsSharingWords.size(); nscores as the reference counts it; n_acc = lAccScoreAndMatch.size();
+ * best_acc_score / min_score_to_retain are the start value and 0.75f times it when nothing was kept. */
+typedef struct sd_kfdb_query_info {
+    int32_t n_sharing, max_common_words, min_common_words, nscores, n_acc, n_candidates;
+    float best_acc_score, min_score_to_retain;
+} sd_kfdb_query_info;                             /* 32 bytes */
+typedef struct sd_kfdb_member { int32_t kf_id, common_words, scored; float si; } sd_kfdb_member;    /* 16 bytes; si = +0 when not scored */
+typedef struct sd_kfdb_acc { float acc_score; int32_t best_kf; } sd_kfdb_acc;                       /* 8 bytes */
+/* Synchronises once and returns query `query` of the last detect call: cand = the candidate kf ids in the reference's order
+ * (info->n_candidates of them), sharing = lKFsSharingWords in list order, acc = lAccScoreAndMatch in list order.  Every pointer is
+ * nullable; SD_ERR_CAPACITY when a buffer that was given is too small (info is filled first, so a caller can size and repeat). */
+int sd_kfdb_download_candidates(sd_kfdb* db, int query, int32_t* cand, int cap_cand, sd_kfdb_query_info* info, sd_kfdb_member* sharing,
+                                int cap_sharing, sd_kfdb_acc* acc, int cap_acc);
+/* (float)mpVoc->score(query, entry) for listed entries -- the scores from which LoopClosing::DetectLoop (:125-139) takes its minScore.
+ * Queries as for sd_kfdb_detect_loop; query q lists kf ids [list_offset[q], list_offset[q+1]) of list_id (host arrays, list_offset[0] =
+ * 0) and d_score (device, one f32 per listed id, in list order) receives the scores.  A listed id that is not live gets -1 (no L1 score
+ * of finite vectors is below -0): the caller scores those few itself.  Asynchronous on `stream`. */
+int sd_kfdb_score(sd_kfdb* db, int n_queries, const int32_t* query_offset, const uint32_t* d_query_word, const double* d_query_value,
+                  const int32_t* list_offset, const int32_t* list_id, float* d_score, void* stream);
+
 /* ---- profiling support for bench.py ----
  * When enabled, every kernel of the batch pipeline is bracketed by hipEvents on the stream it is
  * launched on; sd_batch_kernel_times returns the accumulated milliseconds and launch counts. */

@@ -151,6 +151,22 @@ def lib():
         L.sd_batch_search_by_sim3.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp, vp]
         L.sd_batch_download_sim3_matches.argtypes = [vp, i, vp, vp, vp, i, C.POINTER(i)]
         L.sd_distinctive_descriptors_device.argtypes = [i, vp, vp, vp, vp, vp]
+        L.sd_kfdb_create.argtypes = [C.POINTER(vp), i, i, i, i]
+        L.sd_kfdb_destroy.argtypes = [vp]
+        L.sd_kfdb_clear.argtypes = [vp]
+        L.sd_kfdb_add_from_batch.argtypes = [vp, vp, i, vp, vp, vp]
+        L.sd_kfdb_add_host.argtypes = [vp, i, vp, vp, i]
+        L.sd_kfdb_erase.argtypes = [vp, i, vp]
+        L.sd_kfdb_set_covisible.argtypes = [vp, i, vp, vp, vp]
+        L.sd_kfdb_download_entry.argtypes = [vp, i, vp, vp, i, C.POINTER(i), C.POINTER(C.c_uint32), C.POINTER(i), C.POINTER(f), vp, C.POINTER(i)]
+        L.sd_kfdb_detect_loop.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp]
+        L.sd_kfdb_detect_reloc.argtypes = [vp, i, vp, vp, vp, vp]
+        L.sd_kfdb_detect_loop_batch.argtypes = [vp, vp, i, vp, vp, vp, vp, vp]
+        L.sd_kfdb_detect_reloc_batch.argtypes = [vp, vp, i, vp, vp]
+        L.sd_kfdb_detect_loop_host.argtypes = [vp, i, vp, vp, vp, vp, vp, vp]
+        L.sd_kfdb_detect_reloc_host.argtypes = [vp, i, vp, vp, vp]
+        L.sd_kfdb_download_candidates.argtypes = [vp, i, vp, i, vp, vp, i, vp, i]
+        L.sd_kfdb_score.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -1160,3 +1176,166 @@ def local_bundle_adjustment(problems):
     return [dict(Tcw=T[ko[q]:ko[q] + nl[q]].reshape(-1, 4, 4).copy(), xw=xo[po[q]:po[q + 1]].copy(), normal=nrm[po[q]:po[q + 1]].copy(),
                  dist=dist[po[q]:po[q + 1]].copy(), level1=l1[eo[q]:eo[q + 1]].copy(), erase=er[eo[q]:eo[q + 1]].copy(), stats=st[q])
             for q in range(n)]
+
+
+# ---- KeyFrameDatabase on the device (include/sd_frontend.h: sd_kfdb_*) ----
+KFDB_INFO_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common_words", "<i4"), ("min_common_words", "<i4"), ("nscores", "<i4"), ("n_acc", "<i4"),
+                            ("n_candidates", "<i4"), ("best_acc_score", "<f4"), ("min_score_to_retain", "<f4")])     # sd_kfdb_query_info
+KFDB_MEMBER_DTYPE = np.dtype([("kf_id", "<i4"), ("common_words", "<i4"), ("scored", "<i4"), ("si", "<f4")])       # sd_kfdb_member
+KFDB_ACC_DTYPE = np.dtype([("acc_score", "<f4"), ("best_kf", "<i4")])                                              # sd_kfdb_acc
+KFDB_MAX_NEIGHBOURS, KFDB_MAX_QUERY_WORDS = 10, 16384
+
+
+def pack_bow_queries(queries):
+    """[(word, value)] or [dict(word, value)] -> the CSR (offset (n + 1,) i32, word u32, value f64) the sd_kfdb_* queries take."""
+    qs = [(q["word"], q["value"]) if isinstance(q, dict) else q for q in queries]
+    w = [np.ascontiguousarray(a, np.uint32).reshape(-1) for a, _ in qs]
+    v = [np.ascontiguousarray(b, np.float64).reshape(-1) for _, b in qs]
+    for a, b in zip(w, v):
+        assert len(a) == len(b)
+    off = np.concatenate([[0], np.cumsum([len(a) for a in w])]).astype(np.int32)
+    return off, (np.concatenate(w) if w else np.zeros(0, np.uint32)), (np.concatenate(v) if v else np.zeros(0, np.float64))
+
+
+def _pack_ids(lists, n):
+    """n lists of kf ids -> (offset, ids) i32, or (None, None) for None."""
+    if lists is None:
+        return None, None
+    assert len(lists) == n
+    ls = [np.ascontiguousarray(a, np.int32).reshape(-1) for a in lists]
+    off = np.concatenate([[0], np.cumsum([len(a) for a in ls])]).astype(np.int32)
+    return off, (np.concatenate(ls).astype(np.int32) if ls else np.zeros(0, np.int32))
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM2::KeyFrameDatabase on the device (sd_kfdb_*): add / erase / clear, the covisibility neighbours the two queries read,
+    DetectLoopCandidates, DetectRelocalizationCandidates and the score helper.  Keyframes are named by ids in [0, max_keyframes)."""
+
+    def __init__(self, max_keyframes, max_pool_words, max_queries=1, max_query_words=KFDB_MAX_QUERY_WORDS):
+        self.h = C.c_void_p()
+        check(lib().sd_kfdb_create(C.byref(self.h), max_keyframes, max_pool_words, max_queries, max_query_words))
+        self.max_keyframes, self.max_pool_words, self.max_queries, self.max_query_words = max_keyframes, max_pool_words, max_queries, max_query_words
+
+    def close(self):
+        if self.h:
+            lib().sd_kfdb_destroy(self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        check(lib().sd_kfdb_clear(self.h))
+
+    def add(self, batch, image_index, kf_id, stream=None):
+        """KeyFrameDatabase::add for batch slots with a BowVector (Batch.compute_bow): slot image_index[i] becomes entry kf_id[i]."""
+        ii = np.ascontiguousarray(image_index, np.int32).reshape(-1); kk = np.ascontiguousarray(kf_id, np.int32).reshape(-1)
+        assert len(ii) == len(kk)
+        check(lib().sd_kfdb_add_from_batch(self.h, batch.h, len(ii), _p(ii), _p(kk), C.c_void_p(stream or 0)))
+
+    def add_host(self, kf_id, word, value):
+        w = np.ascontiguousarray(word, np.uint32).reshape(-1); v = np.ascontiguousarray(value, np.float64).reshape(-1)
+        assert len(w) == len(v)
+        check(lib().sd_kfdb_add_host(self.h, int(kf_id), _p(w), _p(v), len(w)))
+
+    def erase(self, kf_id):
+        kk = np.ascontiguousarray(kf_id, np.int32).reshape(-1)
+        check(lib().sd_kfdb_erase(self.h, len(kk), _p(kk)))
+
+    def set_covisible(self, kf_id, neighbours):
+        """neighbours[i] = GetBestCovisibilityKeyFrames(10) of kf_id[i] as a list of at most 10 ids, best first."""
+        kk = np.ascontiguousarray(kf_id, np.int32).reshape(-1)
+        assert len(kk) == len(neighbours)
+        ng = np.zeros((max(len(kk), 1), KFDB_MAX_NEIGHBOURS), np.int32); cnt = np.zeros(max(len(kk), 1), np.int32)
+        for r, nb in enumerate(neighbours):
+            nb = np.asarray(nb, np.int32).reshape(-1)
+            if len(nb) > KFDB_MAX_NEIGHBOURS:
+                raise SdError(SD_ERR_INVALID, "more than 10 neighbours")
+            ng[r, :len(nb)] = nb; cnt[r] = len(nb)
+        check(lib().sd_kfdb_set_covisible(self.h, len(kk), _p(kk), _p(ng), _p(cnt)))
+
+    def entry(self, kf_id):
+        """-> dict(word, value, seq, live, reloc_score, neighbours) of one entry (synchronises)."""
+        n, live, nn = C.c_int(), C.c_int(), C.c_int()
+        seq = C.c_uint32(); rs = C.c_float()
+        ng = np.zeros(KFDB_MAX_NEIGHBOURS, np.int32)
+        check(lib().sd_kfdb_download_entry(self.h, int(kf_id), None, None, 0, C.byref(n), C.byref(seq), C.byref(live), C.byref(rs), _p(ng), C.byref(nn)))
+        w = np.zeros(max(n.value, 1), np.uint32); v = np.zeros(max(n.value, 1), np.float64)
+        check(lib().sd_kfdb_download_entry(self.h, int(kf_id), _p(w), _p(v), len(w), None, None, None, None, None, None))
+        return dict(word=w[:n.value].copy(), value=v[:n.value].copy(), seq=int(seq.value), live=bool(live.value),
+                    reloc_score=np.float32(rs.value), neighbours=ng[:nn.value].copy())
+
+    def _results(self, n):
+        L = lib()
+        out = []
+        for q in range(n):
+            info = np.zeros(1, KFDB_INFO_DTYPE)
+            check(L.sd_kfdb_download_candidates(self.h, q, None, 0, _p(info), None, 0, None, 0))
+            I = info[0]
+            cand = np.zeros(max(int(I["n_candidates"]), 1), np.int32); sh = np.zeros(max(int(I["n_sharing"]), 1), KFDB_MEMBER_DTYPE)
+            acc = np.zeros(max(int(I["n_acc"]), 1), KFDB_ACC_DTYPE)
+            check(L.sd_kfdb_download_candidates(self.h, q, _p(cand), len(cand), None, _p(sh), len(sh), _p(acc), len(acc)))
+            out.append(dict(candidates=cand[:I["n_candidates"]].copy(), info=I.copy(), sharing=sh[:I["n_sharing"]].copy(), acc=acc[:I["n_acc"]].copy()))
+        return out
+
+    def _detect(self, reloc, queries, min_score, excluded, batch, device, stream):
+        L = lib()
+        if batch is not None:
+            ii = np.ascontiguousarray(queries, np.int32).reshape(-1)
+            n = len(ii)
+        else:
+            off, w, v = pack_bow_queries(queries)
+            n = len(off) - 1
+        if not reloc:
+            ms = np.ascontiguousarray(np.broadcast_to(np.asarray(min_score, np.float32), (n,)) if n else np.zeros(0, np.float32), np.float32)
+            ms = ms if len(ms) else np.zeros(1, np.float32)
+            eo, ei = _pack_ids(excluded, n)
+            eo_p, ei_p = (_p(eo), _p(ei if len(ei) else np.zeros(1, np.int32))) if eo is not None else (None, None)
+        s = C.c_void_p(stream or 0)
+        if batch is not None:
+            check(L.sd_kfdb_detect_reloc_batch(self.h, batch.h, n, _p(ii), s) if reloc else
+                  L.sd_kfdb_detect_loop_batch(self.h, batch.h, n, _p(ii), _p(ms), eo_p, ei_p, s))
+        elif device:
+            import torch
+            d_w = torch.from_numpy(w.view(np.int32).copy() if len(w) else np.zeros(1, np.int32)).cuda()
+            d_v = torch.from_numpy(v.copy() if len(v) else np.zeros(1, np.float64)).cuda()
+            torch.cuda.synchronize()
+            check(L.sd_kfdb_detect_reloc(self.h, n, _p(off), C.c_void_p(d_w.data_ptr()), C.c_void_p(d_v.data_ptr()), s) if reloc else
+                  L.sd_kfdb_detect_loop(self.h, n, _p(off), C.c_void_p(d_w.data_ptr()), C.c_void_p(d_v.data_ptr()), _p(ms), eo_p, ei_p, s))
+            res = self._results(n)           # synchronises before d_w / d_v go
+            return res
+        else:
+            wq = w if len(w) else np.zeros(1, np.uint32); vq = v if len(v) else np.zeros(1, np.float64)
+            check(L.sd_kfdb_detect_reloc_host(self.h, n, _p(off), _p(wq), _p(vq)) if reloc else
+                  L.sd_kfdb_detect_loop_host(self.h, n, _p(off), _p(wq), _p(vq), _p(ms), eo_p, ei_p))
+        return self._results(n)
+
+    def detect_loop(self, queries, min_score, excluded=None, batch=None, device=False, stream=None):
+        """DetectLoopCandidates for a list of queries: BowVectors ((word, value) pairs or dicts), or slots of `batch`.  min_score: a float
+        or one per query; excluded: per query the ids of GetConnectedKeyFrames() (None = none).  device=True goes through the device-CSR
+        entry point with torch-owned arrays.  Returns one dict per query: candidates (kf ids, the reference's order), info
+        (KFDB_INFO_DTYPE), sharing (KFDB_MEMBER_DTYPE, list order), acc (KFDB_ACC_DTYPE, list order)."""
+        return self._detect(False, queries, min_score, excluded, batch, device, stream)
+
+    def detect_reloc(self, queries, batch=None, device=False, stream=None):
+        """DetectRelocalizationCandidates for a list of queries; results as for detect_loop."""
+        return self._detect(True, queries, None, None, batch, device, stream)
+
+    def score(self, queries, lists, stream=None):
+        """(float)mpVoc->score(query, entry) for the listed ids of every query -> list of f32 arrays (-1 where the id is not live)."""
+        import torch
+        off, w, v = pack_bow_queries(queries)
+        n = len(off) - 1
+        lo, li = _pack_ids(lists, n)
+        d_w = torch.from_numpy(w.view(np.int32).copy() if len(w) else np.zeros(1, np.int32)).cuda()
+        d_v = torch.from_numpy(v.copy() if len(v) else np.zeros(1, np.float64)).cuda()
+        d_s = torch.zeros(max(len(li), 1), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        check(lib().sd_kfdb_score(self.h, n, _p(off), C.c_void_p(d_w.data_ptr()), C.c_void_p(d_v.data_ptr()), _p(lo),
+                                  _p(li if len(li) else np.zeros(1, np.int32)), C.c_void_p(d_s.data_ptr()), C.c_void_p(stream or 0)))
+        torch.cuda.synchronize()             # the whole device: the call ran on the database's stream
+        sc = d_s.cpu().numpy()
+        return [sc[lo[q]:lo[q + 1]].copy() for q in range(n)]
