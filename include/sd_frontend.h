@@ -976,6 +976,121 @@ int sd_kfdb_download_candidates(sd_kfdb* db, int query, int32_t* cand, int cap_c
 int sd_kfdb_score(sd_kfdb* db, int n_queries, const int32_t* query_offset, const uint32_t* d_query_word, const double* d_query_value,
                   const int32_t* list_offset, const int32_t* list_id, float* d_score, void* stream);
 
+/* ---- the covisibility graph on the device (KeyFrame::UpdateConnections, AddConnection, UpdateBestCovisibles, EraseConnection:
+ * src/KeyFrame.cc:123-208, 289-379, 553-567) ----
+ * sd_covis mirrors the part of the map the covisibility bookkeeping reads.  Per keyframe: a live flag, its features (mvpMapPoints as point
+ * ids, -1 = none; mvKeysUn[i].octave; mvuRight[i] >= 0; mvDepth[i]), its parent, mbFirstConnection, a protected flag (mnId == 0, given at
+ * add time because kf_id is the caller's), its row mConnectedKeyFrameWeights and its ordered list mvpOrderedConnectedKeyFrames /
+ * mvOrderedWeights.  Per map point: a bad flag.  The caller chooses kf_id in [0, max_keyframes) -- the ids it uses in sd_kfdb, so that the
+ * two compose -- and mp_id in [0, max_points).
+ * The observation relation is DERIVED from the keyframe tables and not stored: the observations of point p are exactly the (kf, i) of live
+ * keyframes with mvpMapPoints[i] == p.  A state in which the two sides of that reference disagree (inside MapPoint::Replace or SetBadFlag)
+ * cannot be represented: the caller uploads after its tail has finished.  An index by map point is rebuilt on the device when a table
+ * changed since the last query; the order inside one point's list is unspecified and no result depends on it.
+ * Where the reference orders by KeyFrame* (map<KeyFrame*, ..> iteration, the second key of sort(vPairs)), pointer order is kf_id order:
+ * the ordered list is by descending (weight, kf_id), pKFmax is the lowest id among equal maxima.
+ * Everything is allocated by sd_covis_create: no call allocates device memory (except sd_covis_local_map_host, for its staging).  The rows are dense, 12 bytes per pair of keyframe ids, hence
+ * max_keyframes <= SD_COVIS_MAX_KEYFRAMES.  max_features bounds the features of all keyframes added since the last clear (an erased
+ * keyframe's are NOT reclaimed before sd_covis_clear; a keyframe added from a batch slot takes the slot's capacity), max_jobs the
+ * keyframes or frames listed in one query, max_local_points the local points of one frame.  Anything beyond a capacity is SD_ERR_CAPACITY, an id or size that can never be valid SD_ERR_INVALID,
+ * before anything is launched; nothing is ever truncated.  Calls take effect in the order made; a change of stream is bridged with an
+ * event; the object is not re-entrant.  Only the download_* and *_host calls (and sd_covis_add_host, which ends with its uploads done)
+ * synchronises with the host. */
+#define SD_COVIS_MAX_KEYFRAMES 8192
+typedef struct sd_covis sd_covis;
+int sd_covis_create(sd_covis** out, int max_keyframes, int max_features, int max_points, int max_jobs, int max_local_points);
+int sd_covis_destroy(sd_covis* cv);
+int sd_covis_clear(sd_covis* cv);
+/* n slots of a batch become keyframes, device to device: octave, uRight >= 0 and depth of slot image_index[i] (what the last stereo or
+ * RGB-D call left there) are copied; all matches start at -1, there are no connections, no parent, mbFirstConnection is set.
+ * is_protected (nullable = none) marks mnId == 0.  A live kf_id, or one listed twice: SD_ERR_STATE.  stream NULL = the batch's. */
+int sd_covis_add_from_batch(sd_covis* cv, sd_batch* b, int n, const int32_t* image_index, const int32_t* kf_id, const uint8_t* is_protected,
+                            void* stream);
+/* The same from host arrays of n_features entries each. */
+int sd_covis_add_host(sd_covis* cv, int kf_id, int n_features, const uint8_t* octave, const float* uright, const float* depth,
+                      int is_protected);
+/* mvpMapPoints[idx[i]] of keyframe kf_id[i] = mp_id[i], -1 erases; applied in list order.  Stands for AddMapPoint + AddObservation,
+ * EraseMapPointMatch + EraseObservation and the net effect of Replace.  A keyframe that is not live: SD_ERR_STATE.  If after the call two
+ * features of one keyframe would name the same point: SD_ERR_INVALID and nothing changes.  For a keyframe added from a batch slot idx is
+ * checked against the slot's capacity; an idx at or beyond the slot's key-point count is ignored on the device. */
+int sd_covis_set_matches(sd_covis* cv, int n, const int32_t* kf_id, const int32_t* idx, const int32_t* mp_id);
+/* The same from device arrays of n items (what a device matcher wrote), asynchronous on `stream` (NULL = the object's last), with no host
+ * copy.  The caller guarantees what the host-array path checks: every item names a live keyframe, a feature of it and a point id in
+ * [-1, max_points), no (keyframe, feature) is listed twice (the order of the items is unspecified), and afterwards no keyframe names a
+ * point twice.  The device checks instead of trusting: an item out of range is left out, and two features of one keyframe naming one
+ * point are found when the index by map point is next rebuilt; either makes the next sd_covis_download_* return SD_ERR_INVALID (an
+ * out-of-range item is reported once; a doubly named point until the tables are corrected).  From the first such call until
+ * sd_covis_clear the host no longer knows the match tables: sd_covis_set_matches still checks its ids, but the doubly-named-point refusal
+ * is the device's too, and the index covers all of [0, max_points). */
+int sd_covis_set_matches_device(sd_covis* cv, int n, const int32_t* d_kf_id, const int32_t* d_idx, const int32_t* d_mp_id, void* stream);
+int sd_covis_set_point_bad(sd_covis* cv, int n, const int32_t* mp_id, const uint8_t* bad);         /* MapPoint::isBad() */
+/* mpParent (-1 = none): what the caller's spanning-tree repair (KeyFrame::SetBadFlag, :479-537, ChangeParent) decided. */
+int sd_covis_set_parent(sd_covis* cv, int n, const int32_t* kf_id, const int32_t* parent_id);
+/* The graph part of KeyFrame::SetBadFlag, in list order: EraseConnection(this) on every keyframe of its row (each such keyframe's ordered
+ * list is rebuilt from its whole row, as UpdateBestCovisibles does), its matches, row and list cleared, no longer live.  A protected or
+ * not-live id is skipped. */
+int sd_covis_erase_keyframe(sd_covis* cv, int n, const int32_t* kf_id);
+/* KeyFrame::UpdateConnections for n <= max_jobs live keyframes (SD_ERR_STATE otherwise); they behave as if run in list order.  KFcounter:
+ * over the keyframe's non-null, non-bad points every observer but itself.  Empty counter: nothing changes.  Keyframes with count >= 15
+ * are kept, or if none the single maximum (picked on > in ascending id).  Each kept keyframe X gets AddConnection(this, w): no effect when
+ * X holds this keyframe with that weight, else X's entry is written and X's list rebuilt from X's whole row.  This keyframe's row becomes
+ * KFcounter (every non-zero count), its list the kept pairs; on a first connection of an unprotected keyframe parent = front of the list.
+ * Asynchronous on `stream` (NULL = the object's last). */
+int sd_covis_update_connections(sd_covis* cv, int n, const int32_t* kf_id, void* stream);
+typedef struct sd_covis_keyframe_info {
+    int32_t live, n_features, is_protected, parent, first_connection;
+    int32_t n_ordered, n_row;
+    int32_t n_best;          /* GetBestCovisibilityKeyFrames(best_n) is the first n_best of the ordered list */
+    int32_t n_by_weight;     /* GetCovisiblesByWeight(min_weight) is the first n_by_weight: the prefix up to upper_bound(weights, w, a > b), and, as in
+                                the reference, EMPTY when every weight is >= w */
+} sd_covis_keyframe_info;   /* 36 bytes */
+/* Synchronises.  ordered_id / ordered_weight: GetVectorCovisibleKeyFrames() and mvOrderedWeights; row_id / row_weight:
+ * mConnectedKeyFrameWeights in ascending id (GetConnectedKeyFrames, GetWeight).  Arrays nullable; info is filled first, SD_ERR_CAPACITY
+ * when a given buffer is too small. */
+int sd_covis_download_connections(sd_covis* cv, int kf_id, int best_n, int min_weight, int32_t* ordered_id, int32_t* ordered_weight,
+                                  int cap_ordered, sd_covis_keyframe_info* info, int32_t* row_id, int32_t* row_weight, int cap_row);
+/* LocalMapping::KeyFrameCulling (src/LocalMapping.cc:633-697) over cand_kf_id = GetVectorCovisibleKeyFrames() of the current keyframe (n <=
+ * max_jobs live keyframes, none twice), in list order.  A protected candidate is skipped.  A feature is skipped when its point is null or
+ * bad, or, unless `monocular`, when depth > th_depth || depth < 0 (f32; a NaN depth counts).  Every other feature increments nMPs; with
+ * Observations() (2 per stereo observer, 1 otherwise) > 3 and at least 3 other observers of octave <= this octave + 1 it is redundant.
+ * flag = (double)nRedundant > 0.9 * (double)nMPs.  The loop is sequential, as the reference's: a flagged candidate whose not_erase (nullable
+ * = all 0) is 0 counts as removed for every later candidate -- its observations count nowhere, and a point that lost an observer this
+ * way and is left with a weighted count <= 2 is bad (MapPoint::EraseObservation -> SetBadFlag).  A flagged candidate with not_erase 1
+ * changes nothing (mbToBeErased).  The call changes no state: the caller commits what it deletes with sd_covis_erase_keyframe and
+ * sd_covis_set_point_bad.  Asynchronous on `stream`. */
+int sd_covis_keyframe_culling(sd_covis* cv, int n, const int32_t* cand_kf_id, const uint8_t* not_erase, int monocular, float th_depth,
+                              void* stream);
+typedef struct sd_covis_cull_result { int32_t flag, n_mps, n_redundant; } sd_covis_cull_result;      /* 12 bytes */
+/* The last culling call's record per candidate (synchronises); out nullable to ask for *n alone. */
+int sd_covis_download_culling(sd_covis* cv, sd_covis_cull_result* out, int cap, int* n);
+/* Tracking::UpdateLocalKeyFrames then UpdateLocalPoints (src/Tracking.cc:2076-2210) for n_queries <= max_jobs frames.  Query q is the
+ * frame's mvpMapPoints as point ids (-1 = null): entries [point_offset[q], point_offset[q+1]) of the device array d_mp_id (point_offset is a
+ * host array).  Votes come from the non-bad points; the list starts with the voted keyframes in ascending id, reference_kf = pKFmax
+ * (picked on >).  Then the reference's loop over those members, literally: stop when the list holds more than 80; per member append the
+ * first not yet included live one of its ten best covisibles, then the first such child (ascending id), then the parent if not included
+ * -- and the parent's break ends the WHOLE loop, as in the source (:2192-2200).  Local points: first occurrence over (local keyframes in
+ * list order, feature index), null and bad points excluded.  d_entry_bad (nullable, device, one byte per entry of d_mp_id) receives 1
+ * where the frame named a bad point (the reference nulls those).  An empty vote counter gives reference_kf -1 and empty lists: the
+ * reference returns early and keeps what it had.  Asynchronous on `stream`. */
+int sd_covis_local_map(sd_covis* cv, int n_queries, const int32_t* point_offset, const int32_t* d_mp_id, uint8_t* d_entry_bad, void* stream);
+/* The same from host arrays: uploads, runs, synchronises, downloads entry_bad (nullable).  The one call that allocates device memory: a
+ * staging buffer for the ids and flags, freed before it returns. */
+int sd_covis_local_map_host(sd_covis* cv, int n_queries, const int32_t* point_offset, const int32_t* mp_id, uint8_t* entry_bad);
+typedef struct sd_covis_local_info {
+    int32_t n_keyframes, n_voted, reference_kf, n_points;
+    int32_t overflow;        /* more local points than max_local_points: n_points is the true count, the download is SD_ERR_CAPACITY */
+    int32_t n_bad_entries;
+} sd_covis_local_info;      /* 24 bytes */
+/* One query of the last local-map call (synchronises): info first, then the lists (nullable).  SD_ERR_CAPACITY when the query overflowed
+ * max_local_points -- never a short list -- or a given buffer is too small. */
+int sd_covis_download_local_map(sd_covis* cv, int query, sd_covis_local_info* info, int32_t* local_kf, int cap_kf, int32_t* local_point,
+                                int cap_points);
+/* sd_kfdb_set_covisible for n keyframes live in both objects (SD_ERR_STATE otherwise), device to device: the first ten of each ordered
+ * list.  The graph must hold no keyframe id at or beyond the database's max_keyframes (SD_ERR_INVALID: a neighbour could not be named).
+ * Last writer wins between this call and sd_kfdb_set_covisible.  Ordered after the earlier calls of both objects on `stream` (NULL = the
+ * graph's last). */
+int sd_kfdb_set_covisible_from_covis(sd_kfdb* db, sd_covis* cv, int n, const int32_t* kf_id, void* stream);
+
 /* ---- profiling support for bench.py ----
  * When enabled, every kernel of the batch pipeline is bracketed by hipEvents on the stream it is
  * launched on; sd_batch_kernel_times returns the accumulated milliseconds and launch counts. */

@@ -26,6 +26,7 @@
 #include "k_sim3.h"
 #include "k_loop.h"
 #include "k_kfdb.h"
+#include "k_covis.h"
 #include "sd_scw.h"
 #include "sd_common.h"
 #include "sd_vocab.h"
@@ -3286,5 +3287,6 @@ int sd_batch_backproject_dense(sd_batch* b, int n_frames, const int32_t* slots, 
 
 #include "sd_tracker.inc"
 #include "sd_kfdb.inc"
+#include "sd_covis.inc"
 
 } // extern "C"

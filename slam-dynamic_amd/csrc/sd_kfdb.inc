@@ -151,7 +151,8 @@ int sd_kfdb_erase(sd_kfdb* db, int n, const int32_t* kf_id)
         SdKfdbEntry& E = db->h[kf_id[i]];
         if (!E.live) continue;                               // erase of a keyframe that is not in the lists does nothing (KeyFrameDatabase.cc:58-65)
         E.live = 0;
-        HIPCHK(hipMemcpyAsync(db->d_entry + kf_id[i], &E, SD_KFDB_HOST_BYTES, hipMemcpyHostToDevice, db->lastStream));
+        // off, seq, live only: the neighbour fields of the device entry may have been written by sd_kfdb_set_covisible_from_covis, which the mirror does not see
+        HIPCHK(hipMemcpyAsync(db->d_entry + kf_id[i], &E, offsetof(SdKfdbEntry, nNeigh), hipMemcpyHostToDevice, db->lastStream));
     }
     return SD_OK;
 }

@@ -167,6 +167,24 @@ def lib():
         L.sd_kfdb_detect_reloc_host.argtypes = [vp, i, vp, vp, vp]
         L.sd_kfdb_download_candidates.argtypes = [vp, i, vp, i, vp, vp, i, vp, i]
         L.sd_kfdb_score.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp]
+        L.sd_covis_create.argtypes = [C.POINTER(vp), i, i, i, i, i]
+        L.sd_covis_destroy.argtypes = [vp]
+        L.sd_covis_clear.argtypes = [vp]
+        L.sd_covis_add_from_batch.argtypes = [vp, vp, i, vp, vp, vp, vp]
+        L.sd_covis_add_host.argtypes = [vp, i, i, vp, vp, vp, i]
+        L.sd_covis_set_matches.argtypes = [vp, i, vp, vp, vp]
+        L.sd_covis_set_matches_device.argtypes = [vp, i, vp, vp, vp, vp]
+        L.sd_covis_set_point_bad.argtypes = [vp, i, vp, vp]
+        L.sd_covis_set_parent.argtypes = [vp, i, vp, vp]
+        L.sd_covis_erase_keyframe.argtypes = [vp, i, vp]
+        L.sd_covis_update_connections.argtypes = [vp, i, vp, vp]
+        L.sd_covis_download_connections.argtypes = [vp, i, i, i, vp, vp, i, vp, vp, vp, i]
+        L.sd_covis_keyframe_culling.argtypes = [vp, i, vp, vp, i, f, vp]
+        L.sd_covis_download_culling.argtypes = [vp, vp, i, C.POINTER(i)]
+        L.sd_covis_local_map.argtypes = [vp, i, vp, vp, vp, vp]
+        L.sd_covis_local_map_host.argtypes = [vp, i, vp, vp, vp]
+        L.sd_covis_download_local_map.argtypes = [vp, i, vp, vp, i, vp, i]
+        L.sd_kfdb_set_covisible_from_covis.argtypes = [vp, vp, i, vp, vp]
         _lib = L
     return _lib
 
@@ -1257,6 +1275,11 @@ class KeyFrameDatabase:
             ng[r, :len(nb)] = nb; cnt[r] = len(nb)
         check(lib().sd_kfdb_set_covisible(self.h, len(kk), _p(kk), _p(ng), _p(cnt)))
 
+    def set_covisible_from(self, covis, kf_id, stream=None):
+        """set_covisible with the first ten of each keyframe's ordered list in a CovisibilityGraph, device to device."""
+        kk = np.ascontiguousarray(kf_id, np.int32).reshape(-1)
+        check(lib().sd_kfdb_set_covisible_from_covis(self.h, covis.h, len(kk), _p(kk if len(kk) else np.zeros(1, np.int32)), C.c_void_p(stream or 0)))
+
     def entry(self, kf_id):
         """-> dict(word, value, seq, live, reloc_score, neighbours) of one entry (synchronises)."""
         n, live, nn = C.c_int(), C.c_int(), C.c_int()
@@ -1339,3 +1362,148 @@ class KeyFrameDatabase:
         torch.cuda.synchronize()             # the whole device: the call ran on the database's stream
         sc = d_s.cpu().numpy()
         return [sc[lo[q]:lo[q + 1]].copy() for q in range(n)]
+
+
+# ---- the covisibility graph on the device (include/sd_frontend.h: sd_covis_*) ----
+COVIS_KF_INFO_DTYPE = np.dtype([("live", "<i4"), ("n_features", "<i4"), ("is_protected", "<i4"), ("parent", "<i4"), ("first_connection", "<i4"),
+                                ("n_ordered", "<i4"), ("n_row", "<i4"), ("n_best", "<i4"), ("n_by_weight", "<i4")])          # sd_covis_keyframe_info
+COVIS_CULL_DTYPE = np.dtype([("flag", "<i4"), ("n_mps", "<i4"), ("n_redundant", "<i4")])                                       # sd_covis_cull_result
+COVIS_LOCAL_DTYPE = np.dtype([("n_keyframes", "<i4"), ("n_voted", "<i4"), ("reference_kf", "<i4"), ("n_points", "<i4"), ("overflow", "<i4"),
+                              ("n_bad_entries", "<i4")])                                                                       # sd_covis_local_info
+COVIS_MAX_KEYFRAMES, COVIS_LDS_KEYFRAMES = 8192, 4096
+
+
+def _i32(a):
+    a = np.ascontiguousarray(a, np.int32).reshape(-1)
+    return a, (a if len(a) else np.zeros(1, np.int32))
+
+
+class CovisibilityGraph:
+    """The map's covisibility bookkeeping on the device (sd_covis_*): keyframes with their matches, map points' bad flags,
+    KeyFrame::UpdateConnections, LocalMapping::KeyFrameCulling and Tracking::UpdateLocalKeyFrames / UpdateLocalPoints.  Keyframes are named
+    by ids in [0, max_keyframes) -- those of a KeyFrameDatabase -- and map points by ids in [0, max_points)."""
+
+    def __init__(self, max_keyframes, max_features, max_points, max_jobs=1, max_local_points=1 << 16):
+        self.h = C.c_void_p()
+        check(lib().sd_covis_create(C.byref(self.h), max_keyframes, max_features, max_points, max_jobs, max_local_points))
+        self.max_keyframes, self.max_features, self.max_points, self.max_jobs, self.max_local_points = max_keyframes, max_features, max_points, max_jobs, max_local_points
+
+    def close(self):
+        if self.h:
+            lib().sd_covis_destroy(self.h)
+        self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        check(lib().sd_covis_clear(self.h))
+
+    def add(self, batch, image_index, kf_id, protected=None, stream=None):
+        """Batch slots become keyframes (octave, uRight >= 0 and depth copied on the device); no matches, no connections."""
+        ii, iip = _i32(image_index); kk, kkp = _i32(kf_id)
+        assert len(ii) == len(kk)
+        pr = None if protected is None else np.ascontiguousarray(protected, np.uint8).reshape(-1)
+        assert pr is None or len(pr) == len(kk)
+        check(lib().sd_covis_add_from_batch(self.h, batch.h, len(ii), _p(iip), _p(kkp), None if pr is None or not len(pr) else _p(pr), C.c_void_p(stream or 0)))
+
+    def add_host(self, kf_id, octave, uright, depth, protected=False):
+        o = np.ascontiguousarray(octave, np.uint8).reshape(-1); u = np.ascontiguousarray(uright, np.float32).reshape(-1)
+        d = np.ascontiguousarray(depth, np.float32).reshape(-1)
+        assert len(o) == len(u) == len(d)
+        z8, zf = np.zeros(1, np.uint8), np.zeros(1, np.float32)
+        check(lib().sd_covis_add_host(self.h, int(kf_id), len(o), _p(o if len(o) else z8), _p(u if len(u) else zf), _p(d if len(d) else zf), int(bool(protected))))
+
+    def set_matches(self, kf_id, idx, mp_id):
+        """mvpMapPoints[idx[i]] of keyframe kf_id[i] = mp_id[i] (-1 erases), in list order."""
+        kk, kkp = _i32(kf_id); ii, iip = _i32(idx); mm, mmp = _i32(mp_id)
+        assert len(kk) == len(ii) == len(mm)
+        check(lib().sd_covis_set_matches(self.h, len(kk), _p(kkp), _p(iip), _p(mmp)))
+
+    def set_matches_device(self, kf_id, idx, mp_id, stream=None):
+        """The same through the device-array entry point, with torch-owned arrays (every feature listed once: the order is unspecified)."""
+        import torch
+        kk, kkp = _i32(kf_id); ii, iip = _i32(idx); mm, mmp = _i32(mp_id)
+        assert len(kk) == len(ii) == len(mm)
+        d = [torch.from_numpy(a.copy()).cuda() for a in (kkp, iip, mmp)]
+        torch.cuda.synchronize()
+        check(lib().sd_covis_set_matches_device(self.h, len(kk), C.c_void_p(d[0].data_ptr()), C.c_void_p(d[1].data_ptr()), C.c_void_p(d[2].data_ptr()),
+                                                C.c_void_p(stream or 0)))
+        torch.cuda.synchronize()             # the whole device, before the arrays go
+
+    def set_point_bad(self, mp_id, bad=True):
+        mm, mmp = _i32(mp_id)
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(bad, np.uint8), mm.shape), np.uint8)
+        check(lib().sd_covis_set_point_bad(self.h, len(mm), _p(mmp), _p(b if len(b) else np.zeros(1, np.uint8))))
+
+    def set_parent(self, kf_id, parent_id):
+        kk, kkp = _i32(kf_id); pp, ppp = _i32(parent_id)
+        assert len(kk) == len(pp)
+        check(lib().sd_covis_set_parent(self.h, len(kk), _p(kkp), _p(ppp)))
+
+    def erase(self, kf_id):
+        kk, kkp = _i32(kf_id)
+        check(lib().sd_covis_erase_keyframe(self.h, len(kk), _p(kkp)))
+
+    def update_connections(self, kf_id, stream=None):
+        """KeyFrame::UpdateConnections for the listed keyframes, as if run in list order."""
+        kk, kkp = _i32(kf_id)
+        check(lib().sd_covis_update_connections(self.h, len(kk), _p(kkp), C.c_void_p(stream or 0)))
+
+    def connections(self, kf_id, best_n=10, min_weight=0):
+        """-> dict(ordered_id, ordered_weight, row_id, row_weight, best (GetBestCovisibilityKeyFrames(best_n)), by_weight
+        (GetCovisiblesByWeight(min_weight)), parent, live, first_connection, is_protected) of one keyframe (synchronises)."""
+        info = np.zeros(1, COVIS_KF_INFO_DTYPE)
+        check(lib().sd_covis_download_connections(self.h, int(kf_id), int(best_n), int(min_weight), None, None, 0, _p(info), None, None, 0))
+        I = info[0]
+        no, nr = int(I["n_ordered"]), int(I["n_row"])
+        oi = np.zeros(max(no, 1), np.int32); ow = np.zeros(max(no, 1), np.int32); ri = np.zeros(max(nr, 1), np.int32); rw = np.zeros(max(nr, 1), np.int32)
+        check(lib().sd_covis_download_connections(self.h, int(kf_id), int(best_n), int(min_weight), _p(oi), _p(ow), len(oi), _p(info), _p(ri), _p(rw), len(ri)))
+        return dict(ordered_id=oi[:no].copy(), ordered_weight=ow[:no].copy(), row_id=ri[:nr].copy(), row_weight=rw[:nr].copy(),
+                    best=oi[:int(I["n_best"])].copy(), by_weight=oi[:int(I["n_by_weight"])].copy(), parent=int(I["parent"]), live=bool(I["live"]),
+                    first_connection=bool(I["first_connection"]), is_protected=bool(I["is_protected"]), n_features=int(I["n_features"]))
+
+    def keyframe_culling(self, cand_kf_id, not_erase=None, monocular=False, th_depth=np.inf, stream=None):
+        """LocalMapping::KeyFrameCulling over the candidates in list order -> COVIS_CULL_DTYPE array (flag, n_mps, n_redundant)."""
+        kk, kkp = _i32(cand_kf_id)
+        ne = None if not_erase is None else np.ascontiguousarray(not_erase, np.uint8).reshape(-1)
+        assert ne is None or len(ne) == len(kk)
+        check(lib().sd_covis_keyframe_culling(self.h, len(kk), _p(kkp), None if ne is None or not len(ne) else _p(ne), int(bool(monocular)),
+                                              C.c_float(float(np.float32(th_depth))), C.c_void_p(stream or 0)))
+        out = np.zeros(max(len(kk), 1), COVIS_CULL_DTYPE)
+        n = C.c_int()
+        check(lib().sd_covis_download_culling(self.h, _p(out), len(out), C.byref(n)))
+        return out[:n.value].copy()
+
+    def local_map(self, frames, device=False, stream=None):
+        """UpdateLocalKeyFrames + UpdateLocalPoints for a list of frames, each its mvpMapPoints as point ids (-1 = null).  device=True goes
+        through the device-array entry point with torch-owned arrays.  -> one dict per frame: local_kf, reference_kf, local_points, info
+        (COVIS_LOCAL_DTYPE), entry_bad (u8 per entry of the frame)."""
+        fr = [np.ascontiguousarray(f, np.int32).reshape(-1) for f in frames]
+        off = np.concatenate([[0], np.cumsum([len(f) for f in fr])]).astype(np.int32)
+        ids = np.concatenate(fr).astype(np.int32) if fr and off[-1] else np.zeros(1, np.int32)
+        bad = np.zeros(max(int(off[-1]), 1), np.uint8)
+        if device:
+            import torch
+            d_id = torch.from_numpy(ids.copy()).cuda(); d_bad = torch.zeros(len(bad), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            check(lib().sd_covis_local_map(self.h, len(fr), _p(off), C.c_void_p(d_id.data_ptr()), C.c_void_p(d_bad.data_ptr()), C.c_void_p(stream or 0)))
+        else:
+            check(lib().sd_covis_local_map_host(self.h, len(fr), _p(off), _p(ids), _p(bad)))
+        out = []
+        for q in range(len(fr)):
+            info = np.zeros(1, COVIS_LOCAL_DTYPE)
+            check(lib().sd_covis_download_local_map(self.h, q, _p(info), None, 0, None, 0))      # synchronises before d_id / d_bad go
+            I = info[0]
+            lk = np.zeros(max(int(I["n_keyframes"]), 1), np.int32); lp = np.zeros(max(int(I["n_points"]), 1), np.int32)
+            check(lib().sd_covis_download_local_map(self.h, q, None, _p(lk), len(lk), _p(lp), len(lp)))
+            out.append(dict(local_kf=lk[:I["n_keyframes"]].copy(), reference_kf=int(I["reference_kf"]), local_points=lp[:I["n_points"]].copy(), info=I.copy()))
+        if device:
+            torch.cuda.synchronize()
+            bad = d_bad.cpu().numpy()
+        for q in range(len(fr)):
+            out[q]["entry_bad"] = bad[off[q]:off[q + 1]].copy()
+        return out
