@@ -508,6 +508,96 @@ int sd_batch_search_by_projection_sim3(sd_batch* b, int n_jobs, const int32_t* k
  * when a buffer that was given is too small.  n_entries = the job's entry count, nmatches = its return value. */
 int sd_batch_download_projection_sim3(sd_batch* b, int job, int32_t* assigned, int cap, int32_t* best, int cap_entries, int* n_entries,
                                       int* nmatches);
+/* ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set<MapPoint*>& sAlreadyFound, th, ORBdist)
+ * (src/ORBmatcher.cc:1629-1756), the matcher of Tracking::Relocalization (src/Tracking.cc:2323, :2343), for n_jobs calls at once, with
+ * mbCheckOrientation set as Relocalization sets it.  Job j = frame slot frame_index[j], keyframe slot kf_index[j] (sd_batch_assign_grid
+ * must have run on both, SD_ERR_STATE otherwise; jobs may share slots), CurrentFrame.mTcw = Tcw_host[j] (row-major 4x4), th[j] and
+ * orb_dist[j].  Per-job device rows, each [n_jobs][cap] with cap = kp_capacity:
+ *   d_kf_point     pKF->GetMapPointMatches() as indices into d_points / d_point_desc (sd_map_point records and 32-byte descriptors as for
+ *                  sd_batch_fuse), -1 for NULL; isBad() is flag bit 0 cleared;
+ *   d_frame_point  CurrentFrame.mvpMapPoints on entry as point indices, -1 for NULL (each job has its own, also on a shared frame slot);
+ *   d_found        (nullable, u8) per KEYFRAME feature: its point is in sAlreadyFound.  The set is expressed over point ids by the caller:
+ *                  every keyframe feature that carries an id of the set is flagged.  Two features carrying one id are two visits of the
+ *                  loop, as in the reference; each follows its own flag.
+ * Reproduced as the reference states them: no `z > 0` test (a point behind the camera that projects inside the image is searched),
+ * invzc = 1.0 / z in double rounded to float, u < mnMinX || u > mnMaxX (both ends inside, likewise v), both distance bounds inside,
+ * Frame::GetFeaturesInArea(u, v, th * mvScaleFactors[level], level - 1, level + 1), the sequential greedy (a frame feature that holds a
+ * point, from the entry row or from an earlier keyframe feature of this call, is no target), dist < bestDist, bestDist <= ORBdist, and
+ * the rotation histogram whose losers become NULL after the loop.
+ * Outputs (library-owned device memory, valid until the next call), rows [n_jobs][cap]: d_frame_point_out = mvpMapPoints after the call,
+ * d_from_kf = the keyframe feature that supplied a new entry, -1 elsewhere; d_nmatches[j] = the return value.  Per keyframe feature the
+ * exit it took (SD_RELOC_*) and (bestIdx2, bestDist) at its turn come with sd_batch_download_reloc_matches.
+ * Caps: n_jobs <= SD_RELOC_MAX_JOBS, features per slot = the batch's kp_capacity (<= 65535); 0 < th, 0 <= ORBdist <= 255 (a larger one
+ * would index with bestIdx2 == -1 in the reference): SD_ERR_INVALID before anything is launched.
+ * Per keyframe feature the 64 smallest (distance, visiting order) keys of its window are kept.  A feature that finds all 64 taken while
+ * its window held more is not answered: the next sd_batch_sync (and with it every download) returns SD_ERR_UNSUPPORTED with flag 128.
+ * A d_kf_point / d_frame_point value outside [-1, n_points) is read as -1 and turns the downloads of the call into SD_ERR_INVALID.
+ * No host synchronisation inside the call, except when a call has more jobs than any before it: the library-owned tables then grow,
+ * and the stream is synchronised once before the old ones are freed (as in sd_batch_fuse). */
+#define SD_RELOC_MAX_JOBS 4096
+#define SD_RELOC_NULL 1          /* the keyframe feature has no point (or lies beyond the keyframe's count) */
+#define SD_RELOC_BAD 2           /* isBad() */
+#define SD_RELOC_FOUND 3         /* in sAlreadyFound */
+#define SD_RELOC_OUT_U 4         /* u < mnMinX || u > mnMaxX */
+#define SD_RELOC_OUT_V 5
+#define SD_RELOC_DIST_MIN 6      /* dist3D < 0.8f * min_distance */
+#define SD_RELOC_DIST_MAX 7      /* dist3D > 1.2f * max_distance */
+#define SD_RELOC_WINDOW_EMPTY 8  /* vIndices2.empty() */
+#define SD_RELOC_NO_FREE 9       /* every member held a point (or lay at distance 256): bestIdx2 == -1 */
+#define SD_RELOC_ABOVE_DIST 10   /* bestDist > ORBdist */
+#define SD_RELOC_MATCHED 11
+#define SD_RELOC_CULLED 12       /* matched, then removed by the rotation histogram */
+int sd_batch_search_by_projection_reloc(sd_batch* b, int n_jobs, const int32_t* frame_index, const int32_t* kf_index, const float* Tcw_host,
+                                        const float* th, const int32_t* orb_dist, const int32_t* d_kf_point, const int32_t* d_frame_point,
+                                        const uint8_t* d_found, const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points,
+                                        const sd_camera* cam, int32_t** d_frame_point_out, int32_t** d_from_kf, int32_t** d_nmatches,
+                                        void* stream);
+/* Job `job` of the last sd_batch_search_by_projection_reloc.  frame_point, from_kf, exits (each [cap]) and best ([cap][2]) are nullable
+ * and need room for cap >= kp_capacity entries (SD_ERR_CAPACITY otherwise); nmatches = the return value. */
+int sd_batch_download_reloc_matches(sd_batch* b, int job, int32_t* frame_point, int32_t* from_kf, int32_t* exits, int32_t* best, int cap,
+                                    int* nmatches);
+/* The cascade of Tracking::Relocalization after PnP, from `if(!Tcw.empty())` to `if(nGood>=50)` (src/Tracking.cc:2292-2358), for n_jobs
+ * (frame, candidate keyframe) pairs as one launch sequence without a host synchronisation between its steps.  Job j is what the reference
+ * holds at line 2292: frame slot frame_index[j], keyframe slot kf_index[j] (sd_batch_assign_grid on both), Tcw_host[j] = the pose of
+ * PnPsolver::iterate, row j of d_frame_point = mvpMapPoints after lines 2300-2309 (the BoW match where vbInliers, else -1) and row j of
+ * d_kf_point = vpCandidateKFs[i]->GetMapPointMatches(), both [n_jobs][cap] indices into d_points as for sd_batch_search_by_projection_reloc.
+ * sFound is derived on the device, over point ids: the non-NULL entries of d_frame_point, and at line 2333 every non-NULL entry of the
+ * assignment, outliers of the second optimisation included.  Steps, each predicated per job on the device:
+ *   1  PoseOptimization (k_pose_optimize on edges built from the assignment in key point order: mvKeysUn, mvuRight, mvInvLevelSigma2 of
+ *      the octave, the point's position); nGood < 10 is the `continue`; else outliers become NULL
+ *   2  nGood < 50: SearchByProjection(.., sFound, 10, 100)
+ *   3  nadditional + nGood >= 50: PoseOptimization; NO outlier is set to NULL after this one (the reference does not)
+ *   4  30 < nGood < 50: sFound rebuilt, SearchByProjection(.., sFound, 3, 64)
+ *   5  nGood + nadditional >= 50: PoseOptimization, outliers become NULL
+ * matched = nGood >= 50 of the last optimisation that ran.  The caller applies the reference's `break`: the first job of a frame, in
+ * candidate order, with matched set is the answer; jobs are independent because lines 2300-2309 rewrite every entry of mvpMapPoints for
+ * each candidate.  PnPsolver, mnLastRelocFrameId and that `break` stay on the host.
+ * stage_reached = the number of the last step that ran; n_good / n_additional are -1 for a step that did not run; Tcw_stage[k] = the pose
+ * after optimisation k (the pose before it where it did not run), Tcw = Tcw_stage[2].
+ * Caps, refusals and the answer-or-refuse rule of the searches are those of sd_batch_search_by_projection_reloc; the call reuses that
+ * function's library-owned tables, so its last results are gone.  No host synchronisation inside the call except when the tables grow. */
+typedef struct sd_reloc_result {
+    int32_t stage_reached, matched;
+    int32_t n_good[3], n_additional[2];
+    float Tcw_stage[3][16];
+    float Tcw[16];
+} sd_reloc_result;
+int sd_batch_relocalize_refine(sd_batch* b, int n_jobs, const int32_t* frame_index, const int32_t* kf_index, const float* Tcw_host,
+                               const int32_t* d_kf_point, const int32_t* d_frame_point, const sd_map_point* d_points, const uint8_t* d_point_desc,
+                               int n_points, const sd_camera* cam, sd_reloc_result** d_results, void* stream);
+/* Job `job` of the last sd_batch_relocalize_refine: the result record, and per frame key point the final mvpMapPoints (point index or -1)
+ * and mvbOutlier (written only where a key point had an edge, as the reference does: a key point whose outlier was set to NULL keeps its
+ * flag).  Each pointer is nullable; the rows need cap >= kp_capacity entries. */
+int sd_batch_download_reloc(sd_batch* b, int job, sd_reloc_result* result, int32_t* frame_point, uint8_t* outlier, int cap);
+/* What optimisation `stage` (0 .. 2) of the job saw and decided: its edges in order, mvbOutlier per edge, the pose it started from.
+ * n_edges = 0 for a stage that did not run. */
+int sd_batch_download_reloc_optimisation(sd_batch* b, int job, int stage, sd_pose_edge* edges, uint8_t* edge_outlier, int cap_edges,
+                                         int* n_edges, float* Tcw_in);
+/* Search `which` (0: th 10 / ORBdist 100, 1: th 3 / ORBdist 64) of the job: mvpMapPoints before and after it and the rows of
+ * sd_batch_download_reloc_matches.  A search that did not run passes mvpMapPoints through, with exits 0 and nmatches 0.  Its pose is
+ * Tcw_stage[which] of the result, its sFound the non-NULL entries of d_frame_point (0) or of frame_point_in (1). */
+int sd_batch_download_reloc_search(sd_batch* b, int job, int which, int32_t* frame_point_in, int32_t* frame_point_out, int32_t* from_kf,
+                                   int32_t* exits, int32_t* best, int cap, int* nmatches);
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307) for n_points points in one launch (the "Update points" loop of
  * SearchInNeighbors, Replace, CreateNewMapPoints).  Point p owns observations [d_obs_offset[p], d_obs_offset[p+1]) of d_obs_desc (32 B
  * each, 16-byte aligned) in the order the reference fills vDescriptors: the caller's std::map order, bad keyframes left out.

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <cstddef>
 #include <cmath>
+#include <climits>
 #include <string>
 #include <vector>
 #include <map>
@@ -25,6 +26,7 @@
 #include "k_ba.h"
 #include "k_sim3.h"
 #include "k_loop.h"
+#include "k_reloc.h"
 #include "k_kfdb.h"
 #include "k_covis.h"
 #include "sd_scw.h"
@@ -52,11 +54,11 @@ struct sd_extractor {
     SdParams prm;
 };
 
-enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_TRI_M, K_TRI_T, K_TRI_R, K_FUSE_S, K_FUSE_R, K_SIM3_M, K_SIM3_S, K_SIM3_A, K_LOOP_BOW, K_LOOP_F, K_LOOP_P, K_LOOP_A, K_COUNT };
+enum KernelId { K_PYR0, K_PYR, K_FAST, K_QTREE, K_ORIENT, K_BLUR, K_DESC, K_STEREO, K_STEREO_F, K_RGBD, K_GRID, K_UNPROJ, K_PROJ_A, K_PROJ_B, K_BOXSEP, K_SEPARATE, K_UPDATE, K_LOCAL_A, K_LOCAL_B, K_BOW_T, K_BOW_F, K_BOW_S, K_MOTION_P, K_MOTION_H, K_MOTION_S, K_TRI_M, K_TRI_T, K_TRI_R, K_FUSE_S, K_FUSE_R, K_SIM3_M, K_SIM3_S, K_SIM3_A, K_LOOP_BOW, K_LOOP_F, K_LOOP_P, K_LOOP_A, K_RELOC_S, K_RELOC_A, K_RELOC_E, K_RELOC_O, K_RELOC_X, K_COUNT };
 static const char* kKernelNames[K_COUNT] = {"k_pyr_level0", "k_pyr_level", "k_fast_cells", "k_quadtree", "k_orient",
                                             "k_blur", "k_describe", "k_stereo_match", "k_stereo_filter", "k_rgbd",
                                             "k_grid_cells", "k_unproject", "k_proj_candidates", "k_proj_resolve",
-                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select", "k_tri_match", "k_tri_triangulate", "k_tri_resolve", "k_fuse_search", "k_fuse_resolve", "k_sim3_mark", "k_sim3_search", "k_sim3_agree", "k_search_by_bow_kf", "k_loop_search<0>", "k_loop_search<1>", "k_loop_assign"};
+                                            "k_box_separate", "k_separate", "k_update_frame", "k_local_candidates", "k_local_resolve", "k_bow_transform", "k_bow_finalize", "k_search_by_bow", "k_motion_prepare", "k_motion_hyp", "k_motion_select", "k_tri_match", "k_tri_triangulate", "k_tri_resolve", "k_fuse_search", "k_fuse_resolve", "k_sim3_mark", "k_sim3_search", "k_sim3_agree", "k_search_by_bow_kf", "k_loop_search<0>", "k_loop_search<1>", "k_loop_assign", "k_reloc_search", "k_reloc_assign", "k_reloc_edges", "k_pose_optimize (reloc)", "k_reloc_begin/after/mark/finish"};
 
 #define SD_PT_TW 256
 #define SD_PT_TH 16
@@ -147,6 +149,18 @@ struct sd_batch {
     std::vector<float> loopT; std::vector<int32_t> loopOff;
     SdDevBuf<int> d_loopJobs; SdDevBuf<float> d_loopT; SdDevBuf<int> d_loopNm; SdDevBuf<int> d_loopAssigned; SdDevBuf<int> d_loopErr;
     SdDevBuf<unsigned> d_loopList; SdDevBuf<int> d_loopListN; SdDevBuf<int2> d_loopBest; int loopJobCap = 0, loopEntryCap = 0, loopJobs = 0;
+    // sd_batch_search_by_projection_reloc (k_reloc.h), grown with the largest call seen: job tables (slots, poses, th, ORBdist; the slot
+    // pairs staged on the host), the kept keys per keyframe feature and the result rows [jobs][cap]
+    std::vector<int2> relocSlots; int relocJobCap = 0, relocJobs = 0;
+    SdDevBuf<int2> d_relocSlots; SdDevBuf<float> d_relocT; SdDevBuf<float> d_relocTh; SdDevBuf<int> d_relocOrb; SdDevBuf<int> d_relocNm;
+    SdDevBuf<unsigned> d_relocList; SdDevBuf<int> d_relocListN; SdDevBuf<int> d_relocExit; SdDevBuf<int2> d_relocBest;
+    SdDevBuf<int> d_relocFrame; SdDevBuf<int> d_relocFrom; SdDevBuf<int> d_relocErr;
+    // sd_batch_relocalize_refine: the assignment after each step P [5][jobs][cap], the two searches' rows [2][jobs][cap], the three
+    // optimisations' edges [3][jobs][cap] with their ranges, flags and return values, the poses [4][jobs][16], mvbOutlier [jobs][cap],
+    // the sFound marks [jobs][n_points], the per-job th / ORBdist / camera of the steps (staged on the host), the results
+    SdDevBuf<int> d_rrP, d_rrFrom, d_rrExit, d_rrNm, d_rrGood, d_rrFirst, d_rrLast, d_rrOrb; SdDevBuf<int2> d_rrBest; SdDevBuf<sd_pose_edge> d_rrEdges;
+    SdDevBuf<uint8_t> d_rrEdgeOut, d_rrOutlier, d_rrMark; SdDevBuf<float> d_rrT, d_rrTh; SdDevBuf<sd_camera> d_rrCam; SdDevBuf<sd_reloc_result> d_rrRes;
+    std::vector<float> rrTh; std::vector<int> rrOrb; std::vector<sd_camera> rrCam; int rrJobCap = 0, rrJobs = 0; size_t rrMarkCap = 0;
     std::vector<sd_camera> pairCam, hPoseCam; std::vector<int32_t> hPoseMap;
     int nPairs = 0;
     int dlPairs = 0;          // pairs sd_batch_download_matches may read (the tracker also keeps pairs at [n_lanes, 2 * n_lanes))
@@ -3288,5 +3302,6 @@ int sd_batch_backproject_dense(sd_batch* b, int n_frames, const int32_t* slots, 
 #include "sd_tracker.inc"
 #include "sd_kfdb.inc"
 #include "sd_covis.inc"
+#include "sd_reloc.inc"
 
 } // extern "C"

@@ -17,6 +17,12 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 
 SD_OK = 0
 SD_ERR_INVALID, SD_ERR_NO_DEVICE, SD_ERR_HIP, SD_ERR_CAPACITY, SD_ERR_UNSUPPORTED, SD_ERR_STATE = -1, -2, -3, -4, -5, -6
+# sd_batch_search_by_projection_reloc: the jobs one call takes, and the exit of a keyframe feature (download_reloc_matches)
+SD_RELOC_MAX_JOBS = 4096
+(SD_RELOC_NULL, SD_RELOC_BAD, SD_RELOC_FOUND, SD_RELOC_OUT_U, SD_RELOC_OUT_V, SD_RELOC_DIST_MIN, SD_RELOC_DIST_MAX, SD_RELOC_WINDOW_EMPTY,
+ SD_RELOC_NO_FREE, SD_RELOC_ABOVE_DIST, SD_RELOC_MATCHED, SD_RELOC_CULLED) = range(1, 13)
+RELOC_RESULT_DTYPE = np.dtype([("stage_reached", "<i4"), ("matched", "<i4"), ("n_good", "<i4", (3,)), ("n_additional", "<i4", (2,)),
+                               ("Tcw_stage", "<f4", (3, 4, 4)), ("Tcw", "<f4", (4, 4))])      # sd_reloc_result
 
 
 class SdError(RuntimeError):
@@ -148,6 +154,12 @@ def lib():
         L.sd_batch_search_by_bow_kf.argtypes = [vp, i, vp, vp, vp, vp, f, i, vp]
         L.sd_batch_search_by_projection_sim3.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, i, vp, vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
         L.sd_batch_download_projection_sim3.argtypes = [vp, i, vp, i, vp, i, C.POINTER(i), C.POINTER(i)]
+        L.sd_batch_search_by_projection_reloc.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp]
+        L.sd_batch_download_reloc_matches.argtypes = [vp, i, vp, vp, vp, vp, i, C.POINTER(i)]
+        L.sd_batch_relocalize_refine.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, vp, C.POINTER(vp), vp]
+        L.sd_batch_download_reloc.argtypes = [vp, i, vp, vp, vp, i]
+        L.sd_batch_download_reloc_optimisation.argtypes = [vp, i, i, vp, vp, i, C.POINTER(i), vp]
+        L.sd_batch_download_reloc_search.argtypes = [vp, i, i, vp, vp, vp, vp, vp, i, C.POINTER(i)]
         L.sd_batch_search_by_sim3.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp, vp]
         L.sd_batch_download_sim3_matches.argtypes = [vp, i, vp, vp, vp, i, C.POINTER(i)]
         L.sd_distinctive_descriptors_device.argtypes = [i, vp, vp, vp, vp, vp]
@@ -570,6 +582,69 @@ class Batch:
         assigned = np.zeros(self.cap, np.int32); best = np.zeros((max(n, 1), 2), np.int32); ne, nm = C.c_int(), C.c_int()
         check(lib().sd_batch_download_projection_sim3(self.h, job, _p(assigned), self.cap, _p(best), n, C.byref(ne), C.byref(nm)))
         return assigned, best[:ne.value].copy(), nm.value
+
+    # -- Tracking::Relocalization: SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)
+    def search_by_projection_reloc(self, frame_index, kf_index, Tcw, th, orb_dist, d_kf_point, d_frame_point, d_points, d_point_desc, cam,
+                                   d_found=None, stream=None, *, n_points):
+        """Job j = SearchByProjection(frame slot frame_index[j] with mTcw = Tcw[j], keyframe slot kf_index[j], sAlreadyFound, th[j],
+        orb_dist[j]) (assign_grid must have run on both slots).  d_kf_point / d_frame_point: [n_jobs][cap] i32 device rows (the keyframe's
+        points and the frame's mvpMapPoints on entry as indices into d_points, -1 for NULL); d_found: [n_jobs][cap] u8 per keyframe
+        feature or None (include/sd_frontend.h).  th / orb_dist: a scalar or one value per job.
+        -> (d_frame_point_out, d_from_kf, d_nmatches) device pointers; results through download_reloc_matches."""
+        c = camera_array(cam)
+        fi = np.ascontiguousarray(frame_index, np.int32).reshape(-1); ki = np.ascontiguousarray(kf_index, np.int32).reshape(-1)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 16)
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(th, np.float32), fi.shape)); o = np.ascontiguousarray(np.broadcast_to(np.asarray(orb_dist, np.int32), fi.shape))
+        if len(ki) != len(fi) or len(T) != len(fi):
+            raise ValueError("search_by_projection_reloc: one frame slot, one keyframe slot and one pose per job")
+        d_fp, d_from, d_nm = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().sd_batch_search_by_projection_reloc(self.h, len(fi), _p(fi), _p(ki), _p(T), _p(t), _p(o), C.c_void_p(d_kf_point or 0),
+                                                        C.c_void_p(d_frame_point or 0), C.c_void_p(d_found or 0), C.c_void_p(d_points or 0),
+                                                        C.c_void_p(d_point_desc or 0), int(n_points), _p(c), C.byref(d_fp), C.byref(d_from),
+                                                        C.byref(d_nm), C.c_void_p(stream or 0)))
+        return d_fp.value, d_from.value, d_nm.value
+
+    def download_reloc_matches(self, job):
+        """Job `job` of the last search_by_projection_reloc -> (frame_point (cap,) i32, from_kf (cap,) i32, exits (cap,) i32 (SD_RELOC_*),
+        best (cap, 2) i32, nmatches)."""
+        fp = np.zeros(self.cap, np.int32); fk = np.zeros(self.cap, np.int32); ex = np.zeros(self.cap, np.int32); best = np.zeros((self.cap, 2), np.int32)
+        nm = C.c_int()
+        check(lib().sd_batch_download_reloc_matches(self.h, job, _p(fp), _p(fk), _p(ex), _p(best), self.cap, C.byref(nm)))
+        return fp, fk, ex, best, nm.value
+
+    def relocalize_refine(self, frame_index, kf_index, Tcw, d_kf_point, d_frame_point, d_points, d_point_desc, cam, stream=None, *, n_points):
+        """Job j = lines 2292-2358 of Tracking::Relocalization for frame slot frame_index[j] and candidate keyframe slot kf_index[j]: Tcw[j]
+        from PnPsolver::iterate, row j of d_frame_point = mvpMapPoints after lines 2300-2309, row j of d_kf_point = the candidate's points
+        (both [n_jobs][cap] i32 device rows).  One launch sequence, no host synchronisation.  -> device pointer of the sd_reloc_result
+        records; results through download_reloc."""
+        c = camera_array(cam)
+        fi = np.ascontiguousarray(frame_index, np.int32).reshape(-1); ki = np.ascontiguousarray(kf_index, np.int32).reshape(-1)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(-1, 16)
+        if len(ki) != len(fi) or len(T) != len(fi):
+            raise ValueError("relocalize_refine: one frame slot, one keyframe slot and one pose per job")
+        d_res = C.c_void_p()
+        check(lib().sd_batch_relocalize_refine(self.h, len(fi), _p(fi), _p(ki), _p(T), C.c_void_p(d_kf_point or 0), C.c_void_p(d_frame_point or 0),
+                                               C.c_void_p(d_points or 0), C.c_void_p(d_point_desc or 0), int(n_points), _p(c), C.byref(d_res),
+                                               C.c_void_p(stream or 0)))
+        return d_res.value
+
+    def download_reloc(self, job):
+        """Job `job` of the last relocalize_refine -> (result (RELOC_RESULT_DTYPE scalar), frame_point (cap,) i32, outlier (cap,) u8)."""
+        res = np.zeros(1, RELOC_RESULT_DTYPE); fp = np.zeros(self.cap, np.int32); out = np.zeros(self.cap, np.uint8)
+        check(lib().sd_batch_download_reloc(self.h, job, _p(res), _p(fp), _p(out), self.cap))
+        return res[0], fp, out
+
+    def download_reloc_optimisation(self, job, stage):
+        """What optimisation `stage` (0 .. 2) of the job saw -> (edges (POSE_EDGE_DTYPE), outlier per edge (u8), Tcw_in (4, 4))."""
+        edges = np.zeros(self.cap, POSE_EDGE_DTYPE); out = np.zeros(self.cap, np.uint8); n = C.c_int(); T = np.zeros(16, np.float32)
+        check(lib().sd_batch_download_reloc_optimisation(self.h, job, stage, _p(edges), _p(out), self.cap, C.byref(n), _p(T)))
+        return edges[:n.value].copy(), out[:n.value].copy(), T.reshape(4, 4)
+
+    def download_reloc_search(self, job, which):
+        """Search `which` (0, 1) of the job -> (frame_point_in, frame_point_out, from_kf, exits (each (cap,) i32), best (cap, 2), nmatches)."""
+        rows = [np.zeros(self.cap, np.int32) for _ in range(4)]; best = np.zeros((self.cap, 2), np.int32); nm = C.c_int()
+        check(lib().sd_batch_download_reloc_search(self.h, job, which, _p(rows[0]), _p(rows[1]), _p(rows[2]), _p(rows[3]), _p(best), self.cap, C.byref(nm)))
+        return rows[0], rows[1], rows[2], rows[3], best, nm.value
 
     # -- ORBmatcher::SearchBySim3 (LoopClosing::ComputeSim3)
     def search_by_sim3(self, kf1_index, kf2_index, Tcw1, Tcw2, s12, R12, t12, cam, d_points, d_point_desc, d_kf1_point, d_kf2_point,
