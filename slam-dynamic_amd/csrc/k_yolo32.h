@@ -22,10 +22,34 @@ struct SdConvArgsF {
     int N, H, W, cin, cinStride;
     int Ho, Wo, cout, outStride, resStride;
     int ksize, stride, pad, leaky;
-    int pair;                // first layer (BK == 8 only): the input has 4 channels per pixel and K step s holds taps 2 s and 2 s + 1 (tap 9 = zeros):
-                             // 5 steps of 8 instead of 9 steps of 8 with five zero channels each; weights [coutPad][5][2][4]
+    int pair;                // first layer: the input has 4 channels per pixel and K step s holds taps 2 s and 2 s + 1 (tap 9 = zeros):
+                             // 5 steps of 8 instead of 9 steps of 8 with five zero channels each; weights [coutPad][5][2][4].  k_conv_f32<8, ...> IS
+                             // this form and is launched for the first layer alone (yolo_plan_launch): the kernel does not test the flag
     int tilesX, tilesY, groupY;      // pixel tiles, filter tiles (groupY divides tilesY): the launch is 1-D, SD_F32_GRID(tilesX, tilesY) workgroups
+    // k_conv_f32's set-up, computed where the struct is filled (yolo_f32_setup, sd_yolo_plan.h): the kernel divides by multiply-high
+    // (sd_udiv below) and moves its gather pointers from tap to tap by adding one of two byte distances
+    unsigned mHoWo, sHoWo, mWo, sWo;              // n / (Ho Wo), n / Wo
+    unsigned mPerGroup, sPerGroup, mGroupY, sGroupY;      // n / (ceil8(tilesX) / 8 * groupY), n / groupY
+    int tapCol, tapRow;              // bytes from a tap's first channel to the next tap's: one column on, (kw = ksize - 1 ->) first column of the next row
 };
+
+// n / d for n < 2^31 with the pair (m, s) sd_magic_div(d) made on the host (sd_yolo_plan.h)
+__device__ __forceinline__ unsigned sd_udiv(unsigned n, unsigned m, unsigned s) { return (__umulhi(n, m) + n) >> s; }
+
+// The element-wise tail of the epilogue on one 16-byte piece: x = acc + bias, leaky ReLU, + shortcut, in that order, on PAIRS of floats
+// (v_pk_add_f32 / v_pk_mul_f32: half the instructions of the add, the multiply and the shortcut add).  The leaky ReLU is max(x, slope x) with
+// slope 0.1 -- for every finite x, +-0 included, the value of x > 0 ? x : 0.1 x -- and slope 1 on a linear layer (x 1 and max(x, x) leave x
+// as it is): no compare, no select, no branch on `leaky`.  -ffp-contract=off: no FMA forms.  An `inside` epilogue spends 160 VALU instructions on
+// its 64 outputs per lane instead of 320.  Measured alone (the set-up below in both builds, alternating runs on one box): headline 1109.3 ->
+// 1110.9 frames/s, + 0.13 %, the same sign in every pair of runs but no larger than the parent's own spread; results bit for bit the same.
+typedef float sd_f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ sd_f4 sd_f32_tail(const sd_f4 a, const sd_f4 b, const float slope, const sd_f4 r, const bool res)
+{
+    sd_f2 x0 = a.xy + b.xy, x1 = a.zw + b.zw;
+    x0 = __builtin_elementwise_max(x0, x0 * slope); x1 = __builtin_elementwise_max(x1, x1 * slope);
+    if (res) { x0 += r.xy; x1 += r.zw; }
+    return sd_f4{x0.x, x0.y, x1.x, x1.y};
+}
 
 // Tile shapes: WM waves along the filters x (NW / WM) waves along the pixels, a wave owns MT x 2 MFMA tiles (32 MT filters x 64
 // pixels), K steps of BK channels.  Four instantiations exist, all launched by the one layer walk of sd_yolo_api.hip as yolo_plan_launch
@@ -53,6 +77,14 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     extern __shared__ __align__(16) float smemf[];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, r32 = lane & 31, h = lane >> 5;
     const int wm = wv % WM, wn = wv / WM;               // wave tile: filters [32 MT wm, +32 MT), pixels [64 wn, +64)
+    // Every argument the set-up needs is read here, ahead of any branch: the compiler fetches them with a few wide scalar loads and one wait.
+    const float* const in = A.in; const float* const wgt = A.wgt; const float* const zero = A.zero;
+    const int H = A.H, W = A.W, cin = A.cin, cinStride = A.cinStride, Ho = A.Ho, Wo = A.Wo, ksize = A.ksize, stride = A.stride, pad = A.pad;
+    const int tilesX = A.tilesX, groupY = A.groupY;
+    const int N = A.N, HoWo = Ho * Wo, npix = N * HoWo;
+    const unsigned mHoWo = A.mHoWo, sHoWo = A.sHoWo, mWo = A.mWo, sWo = A.sWo;
+    const ptrdiff_t tapCol = A.tapCol, tapRow = A.tapRow;
+    const float slope = A.leaky ? 0.1f : 1.f;
     // XCD-aware order (workgroup L runs on XCD L % 8, each XCD has its own 4 MB L2): XCD x owns a CONTIGUOUS range of pixel tiles (the
     // rows that neighbouring pixel tiles share for the 3 x 3 taps meet in one L2) and walks it once per GROUP of groupY filter tiles,
     // the filter tiles of a group back to back on each pixel tile.  groupY is chosen on the host so that a group's weights stay
@@ -60,31 +92,17 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     // trading them for weight misses (all 8 filter tiles of a 512 -> 1024 3 x 3 layer are 19 MB of weights).  Measured per 128-image batch
     // (FETCH_SIZE, doubled): 246 GB read in plain (pixel tile, filter tile) grid order, 139 GB with this order at the same 124.1 ms;
     // all filter tiles back to back regardless of their weights: 103 GB but 126.4 ms.
-    const int perXcd = (A.tilesX + 7) >> 3;
-    const int slot = blockIdx.x >> 3, perGroup = perXcd * A.groupY;
-    const int grp = slot / perGroup, r = slot - grp * perGroup;
-    const int tx = (blockIdx.x & 7) * perXcd + r / A.groupY, ty = grp * A.groupY + r % A.groupY;
-    if (tx >= A.tilesX) return;
+    const int perXcd = (tilesX + 7) >> 3;
+    const unsigned slot = blockIdx.x >> 3, perGroup = perXcd * groupY;
+    const unsigned grp = sd_udiv(slot, A.mPerGroup, A.sPerGroup), r = slot - grp * perGroup, rq = sd_udiv(r, A.mGroupY, A.sGroupY);
+    const int tx = (blockIdx.x & 7) * perXcd + rq, ty = grp * groupY + (r - rq * groupY);
+    if (tx >= tilesX) return;
     const int pix0 = tx * BN, co0 = ty * BM;
-    const int npix = A.N * A.Ho * A.Wo;
-    int pyi[XC], pxi[XC];
-    size_t pbase[XC];
-    bool pok[XC];
-#pragma unroll
-    for (int i = 0; i < XC; i++) {
-        const int chunk = tid + NT * i;
-        const int p = pix0 + chunk / CPR;
-        pok[i] = chunk < BN * CPR && p < npix;
-        const int pp = pok[i] ? p : 0;
-        const int n = pp / (A.Ho * A.Wo), r = pp - n * (A.Ho * A.Wo);
-        const int yo = r / A.Wo, xo = r - yo * A.Wo;
-        pyi[i] = yo * A.stride - A.pad; pxi[i] = xo * A.stride - A.pad;
-        pbase[i] = (size_t)n * A.H * A.W;
-    }
-    const int taps = A.ksize * A.ksize;
-    const bool pair = BK == 8 && A.pair;
-    const int ksteps = pair ? (taps + 1) / 2 : taps * (A.cin / BK);
-    const int wrow = pair ? 8 * ksteps : taps * A.cin;   // floats per filter
+    const int taps = ksize * ksize;                     // 1 or 9 (yolo_plan_net admits no other size): the tap masks below hold ksize <= 3
+    constexpr bool pair = BK == 8;                      // the 8-channel step exists for the first layer alone (yolo_plan_launch), in its tap-pair form (SdConvArgsF::pair)
+    __builtin_assume(pair || cin >= 2 * BK);            // stored input channels are a multiple of 32 (yolo_plan_net): the first request never ends a tap
+    const int ksteps = pair ? (taps + 1) / 2 : taps * (cin / BK);
+    const int wrow = pair ? 8 * ksteps : taps * cin;    // floats per filter
     sd_f16v acc[MT][2];
 #pragma unroll
     for (int m = 0; m < MT; m++)
@@ -92,53 +110,116 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
         for (int n = 0; n < 2; n++)
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[m][n][r] = 0.f;
-    // Staging addresses are kept as running pointers: inside a filter tap a step only adds BK floats to each of them; the (y, x)
-    // arithmetic and the bounds test of the im2col gather run once per TAP (every cin / BK steps), and a padded tap reads a zero
-    // page through the same unconditional load.  (The per-step form of this arithmetic, ~150 VALU instructions with 64-bit
-    // multiplies and branches, cost the MFMA pipe a quarter of its time: tools/micro/conv_loop_cost.hip.)
+    // Staging addresses are kept as running pointers: inside a filter tap a step only adds BK floats to each of them.  The im2col gather's
+    // (y, x) arithmetic and bounds tests run ONCE, here: per activation chunk a thread keeps xtrue, the address its piece would have if every
+    // tap lay inside the image (64-bit: the first layers' tensors exceed 2^31 elements at batch 256; outside the image it is formed and never
+    // dereferenced), and tapmask, bit t = tap t of this pixel is inside the image (and the pixel exists).  A tap change (every cin / BK steps)
+    // adds a uniform byte distance to xtrue -- tapCol, or tapRow behind a row's last tap -- and selects xptr = bit ? xtrue : the zero page,
+    // xinc = bit ? BK : 0: one 64-bit add, one bit test and three selects per chunk, no multiply, no branch on exec, no argument reload.  (The per-step form of
+    // the gather arithmetic, ~150 VALU instructions with 64-bit multiplies and branches, cost the MFMA pipe a quarter of its time:
+    // tools/micro/conv_loop_cost.hip; the per-tap form this replaces compiled to nested exec-mask branches around two 64-bit and two 32-bit
+    // multiplies per pointer, five copies of it in the kernel.)  Static counts per wave of the 128-filter tile, before -> after: 377 -> 163 VALU
+    // instructions before the first barrier, 60 -> 8 of them integer multiplies, 16 -> 0 integer multiplies between the first and the last MFMA
+    // (profiles/conv_f32_setup_isa.txt, pinned by tests/test_conv_f32_isa_budget.py).  Measured, alternating runs on one box, in steps: the tap
+    // pointers with plain divisions in the set-up, headline 1096.1 -> 1108.0 frames/s (+ 1.1 %, parent spread 0.3 %) and 118.0 -> 116.6 ms per
+    // 128-image detector pass; the divisions by multiply-high on top, 1108.0 -> 1109.3 (+ 0.1 %: inside the spread; kept because they are what
+    // brings the set-up below half the parent's instructions); the packed epilogue on top: sd_f32_tail.  Results bit for bit the parent's
+    // (tests/test_gpu_conv_f32_epilogue.py, tests/test_gpu_conv_f32_setup.py).
+    // The pixel of chunk 0 is split into (image, row, column) by two multiply-highs (sd_udiv); chunk i + 1 lies NT / CPR pixels further on and
+    // follows from chunk i by adding the (uniform) split of that distance with carries.
     // DEEP: two register sets, a stage's tiles are requested TWO steps before they go to LDS.  The 64-filter tile <.., 1, 2, ..> stages
     // four activation chunks per thread; a second set would cost it its third wave per SIMD (186 VGPRs) and more than it gains.
     constexpr bool DEEP = !(WM == 1 && MT == 2);
     constexpr int NSET = DEEP ? 2 : 1;
+    static_assert(XC * NT == BN * CPR && NT % CPR == 0, "every thread stages XC activation chunks, all of them the same piece of their rows");
     sd_f4 xr[NSET][XC], wr[NSET][WC];
     const float* wptr[WC];
     const float* xptr[XC];
+    const char* xtrue[XC];
+    unsigned tapmask[XC];
     int winc[WC], xinc[XC];
-#pragma unroll
-    for (int i = 0; i < WC; i++) {
-        const int chunk = tid + NT * i;
-        const bool on = chunk < BM * CPR;
-        wptr[i] = on ? A.wgt + (size_t)(co0 + chunk / CPR) * wrow + 4 * (chunk % CPR) : A.zero;
-        winc[i] = on ? BK : 0;                          // (tap, channel) is one contiguous axis of a filter's weights
-    }
-    int c0 = 0, kh = 0, kw = 0, ps = 0;
-    auto retap = [&]() {                                // branch-free: the address of a padded tap is computed and discarded
+    const int q = tid % CPR;                            // this thread's 16-byte piece of a row, the same in all its chunks
+    {
+        constexpr unsigned D = NT / CPR;                // pixels between two chunks of a thread
+        const unsigned dn = sd_udiv(D, mHoWo, sHoWo), dr = D - dn * HoWo, dy = sd_udiv(dr, mWo, sWo), dx = dr - dy * Wo;
+        const unsigned p = pix0 + tid / CPR;
+        unsigned n = sd_udiv(p, mHoWo, sHoWo);
+        const unsigned pr = p - n * HoWo;
+        unsigned yo = sd_udiv(pr, mWo, sWo), xo = pr - yo * Wo;
+        const unsigned rowrep = ksize == 1 ? 1u : 1u | 1u << ksize | 1u << 2 * ksize;      // bit 0 of every filter row
+        const unsigned rowlow = (1u << ksize) - 1u;
 #pragma unroll
         for (int i = 0; i < XC; i++) {
-            const int chunk = tid + NT * i;
-            int dy = kh, dx = kw, coff = 4 * (chunk % CPR);
-            bool tapok = true;
-            if (BK == 8 && pair) {                      // piece q of the row = tap 2 ps + q, all four channels of its pixel
-                const int tap = 2 * ps + (chunk % CPR);
-                dy = tap / A.ksize; dx = tap - dy * A.ksize; coff = 0;
-                tapok = tap < taps;
+            if (i > 0) {
+                xo += dx; const bool cx = xo >= (unsigned)Wo; xo -= cx ? Wo : 0;
+                yo += dy + (cx ? 1 : 0); const bool cy = yo >= (unsigned)Ho; yo -= cy ? Ho : 0;
+                n += dn + (cy ? 1 : 0);
             }
-            const int yi = pyi[i] + dy, xi = pxi[i] + dx;
-            const bool ok = pok[i] && tapok && yi >= 0 && yi < A.H && xi >= 0 && xi < A.W;
-            const float* p = A.in + ((ptrdiff_t)pbase[i] + (ptrdiff_t)yi * A.W + xi) * A.cinStride + coff;
-            xptr[i] = ok ? p : A.zero;
+            const int yi = __mul24((int)yo, stride) - pad, xi = __mul24((int)xo, stride) - pad;      // tap (0, 0) of the pixel
+            // taps k of an axis inside the map: l <= k < h with l = max(-c, 0), h = min(extent - c, ksize), c the coordinate of tap 0.  pad <= 1, so
+            // l is 0 or 1 and h >= 1: the columns' bits are (1 << h) - 1 - l, repeated per filter row (x rowrep, bit 0 of every row), and the
+            // rows' bits [l ksize, h ksize) are (1 << h ksize) - 1 - l rowlow (rowlow: the first row's bits)
+            const int lx = max(-xi, 0), hx = min(W - xi, ksize), ly = max(-yi, 0), hy = min(H - yi, ksize);
+            const unsigned mk = __umul24((1u << hx) - 1u - lx, rowrep) & ((1u << __umul24(hy, ksize)) - (1u + __umul24(ly, rowlow)));
+            // piece q of a row: channels [4 q, +4) of the tap -- in `pair` mode tap 2 s + q of K step s, all four channels of its pixel.  A chunk beyond the
+            // last pixel lies in an image >= N
+            tapmask[i] = n < (unsigned)N ? (pair ? mk >> q : mk) : 0;
+            // 32-bit pixel index, 24-bit factors (the host refuses larger inputs); the byte offset is 64-bit
+            const int pixel = __mul24((int)__umul24(n, H) + yi, W) + xi;
+            xtrue[i] = (const char*)in + ((long long)pixel * (4 * cinStride) + (pair ? 4 * cinStride : 16) * q);
+        }
+    }
+    {
+        constexpr int DW = NT / CPR;                    // filters between two chunks of a thread
+        // the tile's first filter row in scalar registers; a thread's own row and piece within the tile: a 32-bit byte offset
+        const char* const w0 = (const char*)(wgt + (size_t)co0 * (unsigned)wrow) + (__umul24(tid / CPR, wrow) * 4u + 16u * q);
+#pragma unroll
+        for (int i = 0; i < WC; i++) {
+            const bool on = (WC * NT == BM * CPR) || tid + NT * i < BM * CPR;
+            wptr[i] = on ? (const float*)(w0 + (size_t)(4 * DW * i) * (unsigned)wrow) : zero;
+            winc[i] = on ? BK : 0;                      // (tap, channel) is one contiguous axis of a filter's weights
+        }
+    }
+    int c0 = 0, kw = 0, pdx = q;                        // pdx (`pair`): the column of this thread's tap in its filter row
+    unsigned tapbit = 1;                                // the current tap's bit in tapmask (`pair`: the bit of tap 2 s at K step s, tapmask is shifted by q)
+    auto select = [&]() {
+#pragma unroll
+        for (int i = 0; i < XC; i++) {
+            const bool ok = (tapmask[i] & tapbit) != 0;
+            xptr[i] = ok ? (const float*)xtrue[i] : zero;
             xinc[i] = ok && !pair ? BK : 0;
         }
     };
-    retap();
+    auto retap = [&]() {                                // the next tap (`pair`: the next two)
+        if (pair) {
+            // a thread's tap goes two columns on; past the row's end (once at most: ksize >= 2 wherever a second step exists) it wraps into the next row
+            pdx += 2;
+            const bool wrap = pdx >= ksize;
+            pdx -= wrap ? ksize : 0;
+            const ptrdiff_t d = wrap ? tapRow + tapCol : 2 * tapCol;
+#pragma unroll
+            for (int i = 0; i < XC; i++) xtrue[i] += d;
+            tapbit <<= 2;
+        } else {
+            kw++;
+            const bool wrap = kw == ksize;
+            if (wrap) kw = 0;
+            const ptrdiff_t d = wrap ? tapRow : tapCol;
+#pragma unroll
+            for (int i = 0; i < XC; i++) xtrue[i] += d;
+            tapbit <<= 1;
+        }
+        select();
+    };
+    select();
     auto fetch = [&](const int set) {
 #pragma unroll
         for (int i = 0; i < WC; i++) { wr[set][i] = *(const sd_f4*)wptr[i]; wptr[i] += winc[i]; }
 #pragma unroll
         for (int i = 0; i < XC; i++) { xr[set][i] = *(const sd_f4*)xptr[i]; xptr[i] += xinc[i]; }
-        if (BK == 8 && pair) { ps++; retap(); return; }
+        if (pair) { retap(); return; }
         c0 += BK;
-        if (c0 == A.cin) { c0 = 0; kw++; if (kw == A.ksize) { kw = 0; kh++; } retap(); }
+        if (c0 == cin) { c0 = 0; retap(); }
     };
     auto store = [&](int buf, const int set) {
         float* sW = smemf + buf * STAGE;
@@ -176,8 +257,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     // ds_read_b128, which counts in lgkmcnt -- a bias load from global memory there shares vmcnt with the tile's stores and made every
     // store wait for the one before it (see the epilogue).
     float* const sBias = smemf + 2 * STAGE;
-    sd_f4 bq = sd_f4{0.f, 0.f, 0.f, 0.f};
-    if (tid < BM / 4 && co0 + 4 * tid < A.cout) bq = *(const sd_f4*)(A.bias + co0 + 4 * tid);     // bias rows are padded to the filter tile
+    // every thread requests a piece (no branch, no zero fill; the first BM / 4 threads write theirs); bias rows are padded to the widest filter tile
+    // (coutPad): no test against cout
+    const sd_f4 bq = *(const sd_f4*)(A.bias + co0 + 4 * (tid % (BM / 4)));
     // The order below exposes two latencies (stage 1 is requested only behind store(0, 0)'s wait).  Requesting stages 0 AND 1 before the first
     // wait was measured and is not kept: headline 1085.2 / 1086.2 frames/s against 1087.0 / 1087.4 with this order in alternating runs on
     // one box, per-layer fixed cost the same (profiles/conv_f32_epilogue_layers_steps.txt) -- the two other workgroups of the CU cover it.
@@ -267,13 +349,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
                     const int pl = PPI * it + prow, p = pb + pl;
                     if (!inside && (p >= npix || cob >= A.cout)) continue;
                     const sd_f4 a = *(const sd_f4*)(T + pl * TLD + 4 * piece);
-                    sd_f4 v;
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        float x = a[e] + bias4[e];
-                        if (A.leaky) x = x > 0.f ? x : 0.1f * x;
-                        v[e] = x + (res ? rr[n][it][e] : 0.f);
-                    }
+                    const sd_f4 v = sd_f32_tail(a, bias4, slope, rr[n][it], res);
                     float* dst = A.out + (size_t)p * A.outStride + cob;
                     if (inside || cob + 3 < A.cout) *(sd_f4*)dst = v;
                     else for (int e = 0; e < 4 && cob + e < A.cout; e++) dst[e] = v[e];
@@ -326,13 +402,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
                         const int cl = 32 * MT * wm + 32 * m + 8 * g + 4 * h, co = co0 + cl;
                         if (!inside && co >= A.cout) continue;
                         const sd_f4 b4 = *(const sd_f4*)(sBias + cl);      // per piece: eight more live pieces beside rr and acc spill
-                        sd_f4 v;
-#pragma unroll
-                        for (int e = 0; e < 4; e++) {
-                            float x = acc[m][n][4 * g + e] + b4[e];
-                            if (A.leaky) x = x > 0.f ? x : 0.1f * x;
-                            v[e] = x + (res ? rr[n][m][g][e] : 0.f);
-                        }
+                        const sd_f4 v = sd_f32_tail(sd_f4{acc[m][n][4 * g], acc[m][n][4 * g + 1], acc[m][n][4 * g + 2], acc[m][n][4 * g + 3]}, b4, slope, rr[n][m][g], res);
                         float* dst = A.out + (size_t)p * A.outStride + co;
                         if (inside || co + 3 < A.cout) *(sd_f4*)dst = v;
                         else for (int e = 0; e < 4 && co + e < A.cout; e++) dst[e] = v[e];

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cstddef>
+#include <climits>
 #include <cmath>
 #include <string>
 #include <memory>
@@ -486,7 +487,14 @@ int sd_yolo_forward_device(sd_yolo* y, const uint8_t* d_bgr, int width, int heig
                 A.Ho = r.H; A.Wo = r.W; A.cout = l.filters; A.outStride = r.outC; A.resStride = resStride;
                 A.ksize = l.size; A.stride = l.stride; A.pad = l.size / 2; A.leaky = l.leaky;
                 A.tilesX = K.tilesX; A.tilesY = K.tilesY; A.groupY = K.groupY;
-                const uint4* wq = y->d_wgtB + r.wOffB;                 // the limb kernels' second argument
+                const SdF32Setup S = yolo_f32_setup(K.tilesX, K.groupY, r.H, r.W, W, l.size, Cs);
+                // the kernels index pixels in 32 bits (k_conv_f32's gather: 24-bit factors) and move between taps by 32-bit byte distances
+                if (S.tapRow > INT_MAX || S.tapRow < INT_MIN || (long long)n * r.H * r.W + 512 > INT_MAX || (long long)n * H * W > INT_MAX || (long long)n * H >= (1 << 23) || W >= (1 << 23))
+                    return set_err(SD_ERR_UNSUPPORTED, "convolution too large for the f32 kernels' 32-bit pixel index");
+                A.mHoWo = S.hoWo.m; A.sHoWo = S.hoWo.s; A.mWo = S.wo.m; A.sWo = S.wo.s;
+                A.mPerGroup = S.perGroup.m; A.sPerGroup = S.perGroup.s; A.mGroupY = S.groupY.m; A.sGroupY = S.groupY.s;
+                A.tapCol = (int)S.tapCol; A.tapRow = (int)S.tapRow;
+                const uint4* wq =y->d_wgtB + r.wOffB;                 // the limb kernels' second argument
                 void* args[] = {&A, &wq};
                 rc = yolo_launch(K, args, s);
             }

@@ -213,6 +213,31 @@ static inline int f32_group_y(int tilesY, int bm, int kdim)
     return g;
 }
 
+// Division by a number known on the host, for the kernels: n / d == (mulhi32(n, m) + n) >> s for every n < 2^31 (the sum then fits 32 bits),
+// with s = ceil(log2 d) and m = ceil(2^(32 + s) / d) - 2^32 (Granlund & Montgomery 1994: 2^(32 + s) <= (m + 2^32) d <= 2^(32 + s) + 2^s).
+// d = 1 and the powers of two come out as m = 0.  tests/test_conv_f32_magic_div.py walks the full ranges the detector divides.
+struct SdMagic { unsigned m, s; };
+static inline SdMagic sd_magic_div(unsigned d)
+{
+    unsigned s = 0;
+    while ((1ull << s) < d) s++;
+    return {(unsigned)((((1ull << (32 + s)) + d - 1) / d) - (1ull << 32)), s};
+}
+static inline unsigned sd_magic_quot(unsigned n, SdMagic k) { return ((unsigned)(((unsigned long long)n * k.m) >> 32) + n) >> k.s; }
+
+// What k_conv_f32's set-up takes from the host (SdConvArgsF, k_yolo32.h): the four divisors of its pixel split and workgroup order, and the byte
+// distances its gather pointers move by at a tap change -- to the next column, and from a filter row's last column to the next row's first (negative
+// on maps narrower than the filter).  `W`: the INPUT map's width.
+struct SdF32Setup { SdMagic hoWo, wo, perGroup, groupY; long long tapCol, tapRow; };
+static inline SdF32Setup yolo_f32_setup(int tilesX, int groupY, int Ho, int Wo, int W, int ksize, int cinStride)
+{
+    SdF32Setup S;
+    S.hoWo = sd_magic_div((unsigned)(Ho * Wo)); S.wo = sd_magic_div((unsigned)Wo);
+    S.perGroup = sd_magic_div((unsigned)(((tilesX + 7) / 8) * groupY)); S.groupY = sd_magic_div((unsigned)groupY);
+    S.tapCol = 4ll * cinStride; S.tapRow = 4ll * (W - ksize + 1) * cinStride;
+    return S;
+}
+
 // The launch of convolution `l` (the network's first when `first`) with shape record `r` on a batch of n images.
 static inline SdYoloLaunch yolo_plan_launch(const sd_yolo_layer& l, const SdYoloLayerPlan& r, bool first, int n)
 {
