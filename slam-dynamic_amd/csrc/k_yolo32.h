@@ -51,6 +51,41 @@ __device__ __forceinline__ sd_f4 sd_f32_tail(const sd_f4 a, const sd_f4 b, const
     return sd_f4{x0.x, x0.y, x1.x, x1.y};
 }
 
+// Where a K step's staging instructions go among its MFMAs (LLVM's sched_group_barrier: "next, N instructions of this class", in the order the
+// groups are written).  The step is one basic block of TM MFMAs behind the R0 fragment reads of its first K chunk.  Behind MFMA g:
+//   g < ceil(RD / 2)              two of the RD fragment reads of the step's later K chunks (needed from MFMA TM / 2 on);
+//   g = W0, W0 + WS, ...          one of the NS ds_write_b128 of the next stage;
+//   g = L0, L0 + LS, ...          one of the NS global_load_dwordx4 of the stage after it, with its pointer's post-increment (load i overwrites the
+//                                 registers write i read: every write stands in front of every load);
+//   every other gap               nothing: what is left (lgkmcnt / vmcnt waits, scalar instructions) falls where the scheduler likes.
+// No gap holds more than one vector-memory or two LDS instructions: tools/conv_f32_loop_gaps.py prints the emitted gaps,
+// tests/test_conv_f32_loop_schedule.py pins them.  WHERE the gaps lie matters far more than that they are apart -- measured on the 128-filter
+// tile (headline, frames/s, builds alternated with the parent on one box; TM = 32, writes / loads behind MFMA ...):
+//   2, 3, ..., 9 alternating (write, load, write, ...)           - 14.8 %      10 - 17 alternating   - 7.4 %      16 - 23 alternating   - 2.7 %
+//   6, 8, ..., 20 alternating                                    -  3.6 %      2, 5, ..., 23 alternating  + 0.2 %   6, 9, ..., 27 alternating  + 1.2 %
+//   writes 6, 9, 12, 15, loads 18, 21, 24, 27                    +  1.6 %      writes 4, 8, 12, 16, loads 20, 23, 26, 29 (this)  + 1.8 %
+//   writes 4, 7, 10, 13, loads 16 - 25   + 0.9 %;   writes 6 - 15, loads 24, 25, 26, 27   + 0.9 %;   writes 3, 7, 11, 15, loads 19, 23, 27, 31   + 0.9 %
+// (the parent's own spread in those sessions: 0.02 - 0.34 %; profiles/conv_f32_schedule_bench.json).  What the numbers say: a staging instruction
+// directly behind the post-barrier burst of fragment reads, or directly behind another one, stalls its wave at issue (instruction issue is in
+// order: the MFMAs behind it wait with it); a load two or three MFMAs behind the write whose registers it overwrites is the worst case; writes
+// early, loads late, each three or four MFMAs apart is the best found.
+template <int TM, int R0, int RD, int NS, int W0, int WS, int L0, int LS, int G = 0>
+__device__ __forceinline__ void sd_f32_place()
+{
+    static_assert(W0 >= (RD + 1) / 2 && W0 + WS * (NS - 1) < L0 && L0 + LS * (NS - 1) < TM, "the step's staging does not fit its MFMA gaps");
+    if constexpr (G == 0) __builtin_amdgcn_sched_group_barrier(0x100, R0, 0);               // the first chunk's R0 fragment reads, behind the barrier
+    if constexpr (G < TM) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                  // one MFMA
+        if constexpr (2 * G < RD) __builtin_amdgcn_sched_group_barrier(0x100, RD - 2 * G < 2 ? RD - 2 * G : 2, 0);      // DS reads
+        else if constexpr (G >= W0 && (G - W0) % WS == 0 && (G - W0) / WS < NS) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);      // one DS write
+        else if constexpr (G >= L0 && (G - L0) % LS == 0 && (G - L0) / LS < NS) {
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                              // one VMEM read
+            __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                              // a pointer update
+        }
+        sd_f32_place<TM, R0, RD, NS, W0, WS, L0, LS, G + 1>();
+    }
+}
+
 // Tile shapes: WM waves along the filters x (NW / WM) waves along the pixels, a wave owns MT x 2 MFMA tiles (32 MT filters x 64
 // pixels), K steps of BK channels.  Four instantiations exist, all launched by the one layer walk of sd_yolo_api.hip as yolo_plan_launch
 // (sd_yolo_plan.h) chooses them, in the f32-class modes for every convolution their Winograd / bf16-limb kernels do not take:
@@ -131,6 +166,11 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     // four activation chunks per thread; a second set would cost it its third wave per SIMD (186 VGPRs) and more than it gains.
     constexpr bool DEEP = !(WM == 1 && MT == 2);
     constexpr int NSET = DEEP ? 2 : 1;
+    // ALWAYS: every K step writes a stage and requests one, whether or not the tile has one left (see request() below) -- the tiles whose weight rows
+    // fill their threads.  The two 32-filter tiles store their weight rows under an exec-mask branch, which splits the step anyway, and measured
+    // slower with unconditional requests (first layer + 12.6 %, the 1 x 1 64 -> 32 layer + 2.5 %): they keep the conditional store and request, inside
+    // the step.  The end-of-tile handling in retap() is the same for all tiles; on these two no request follows it.
+    constexpr bool ALWAYS = WC * NT == BM * CPR;
     static_assert(XC * NT == BN * CPR && NT % CPR == 0, "every thread stages XC activation chunks, all of them the same piece of their rows");
     sd_f4 xr[NSET][XC], wr[NSET][WC];
     const float* wptr[WC];
@@ -180,6 +220,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
             winc[i] = on ? BK : 0;                      // (tap, channel) is one contiguous axis of a filter's weights
         }
     }
+    int nreq = 0;                                       // stages requested so far
     int c0 = 0, kw = 0, pdx = q;                        // pdx (`pair`): the column of this thread's tap in its filter row
     unsigned tapbit = 1;                                // the current tap's bit in tapmask (`pair`: the bit of tap 2 s at K step s, tapmask is shifted by q)
     auto select = [&]() {
@@ -210,13 +251,39 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
             tapbit <<= 1;
         }
         select();
+        const bool dead = nreq >= ksteps;               // the tile has no stage left to request: see request() below
+#pragma unroll
+        for (int i = 0; i < WC; i++) { wptr[i] = dead ? zero : wptr[i]; winc[i] = dead ? 0 : winc[i]; }
     };
     select();
-    auto fetch = [&](const int set) {
+    // A stage's request is split in two.  request(): its loads and the pointers' post-increments, straight-line -- on the ALWAYS tiles issued by
+    // EVERY K step and 1 + NSET times by the prologue, whether or not the tile has a stage left to ask for.  advance(): the tap walk behind it, with
+    // its one branch, placed where it splits no MFMA sequence: behind a step's last MFMA, in front of its barrier.
+    // Why unconditional: with `if (stage left) fetch` inside the step the compiler had to assume, at every ds_write, that the younger register
+    // set's loads might not have been issued, and waited with vmcnt(3..0) -- for loads requested ONE step earlier; DEEP's two-step distance was in the
+    // registers but not in the waits.  With every request always issued the waits are counted (vmcnt(7) on the 128-filter tile), and the step
+    // between its first and its last MFMA is one basic block whose instructions can be placed (sd_f32_place).
+    // What a request behind the tile's last stage reads: the zero page A.zero, into a register set that goes to an LDS buffer no MFMA reads
+    // again.  The tile's last real request ends its last tap, so the retap() behind it is where the tile ends (`dead`, wave-uniform: nreq >=
+    // ksteps; it stays set for the 1 + NSET requests that follow, one per remaining step).  No load is formed from an address the parent did
+    // not read, per pointer kind:
+    //   weights       wptr walks [tap][channel] of its filter row contiguously, post-incremented; behind the last real request it points one step
+    //                 past the row (behind the tensor for the last row): the dead retap() replaces it by A.zero with increment 0 before the next load;
+    //   activations   the dead retap() moves tapbit to bit `taps` (pair: bit 10 and up) of the tap masks, which is clear in every mask (mk has
+    //                 bits [0, ksize^2) only): select() gives A.zero with increment 0, exactly as for a padded tap; later retaps shift it further up
+    //                 (three times at most, far below bit 32);
+    //   padded taps   select() as before: A.zero with increment 0 while the tap's mask bit is clear; xtrue is formed and never dereferenced
+    //                 (also behind the tile's end, where it keeps walking);
+    //   chunks beyond npix   tapmask == 0: A.zero at every tap, from the first request on.
+    // retap() only moves VALU registers: no path of the loop issues a load another does not, which is what keeps the waits counted.
+    auto request = [&](const int set) {
 #pragma unroll
         for (int i = 0; i < WC; i++) { wr[set][i] = *(const sd_f4*)wptr[i]; wptr[i] += winc[i]; }
 #pragma unroll
         for (int i = 0; i < XC; i++) { xr[set][i] = *(const sd_f4*)xptr[i]; xptr[i] += xinc[i]; }
+    };
+    auto advance = [&]() {
+        nreq++;
         if (pair) { retap(); return; }
         c0 += BK;
         if (c0 == cin) { c0 = 0; retap(); }
@@ -252,7 +319,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     const int myslot = NW == 8 ? (NCH >= 4 ? 2 * (wv >> 2) : (NCH == 2 ? (wv >> 2) : 0)) : 0;
     // DEEP: stage s lives in register set s & 1 from its request (two steps ahead: ~12 000 cycles with three waves per SIMD, against an
     // L2 / HBM latency of several thousand under load -- with ONE step of distance the ds_writes waited on their loads for 11 % of
-    // the kernel time) until it is written to LDS buffer s & 1 during step s - 1.
+    // the kernel time) until it is written to LDS buffer s & 1 during step s - 1.  (Until the requests became unconditional that distance was
+    // in the registers only: the waits in front of the ds_writes were vmcnt(3..0), which also waits for the loads issued one step earlier.)
     // The tile's BM bias floats are staged in LDS behind the two stages (requested first, written with stage 0): the epilogue reads them with
     // ds_read_b128, which counts in lgkmcnt -- a bias load from global memory there shares vmcnt with the tile's stores and made every
     // store wait for the one before it (see the epilogue).
@@ -263,17 +331,20 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     // The order below exposes two latencies (stage 1 is requested only behind store(0, 0)'s wait).  Requesting stages 0 AND 1 before the first
     // wait was measured and is not kept: headline 1085.2 / 1086.2 frames/s against 1087.0 / 1087.4 with this order in alternating runs on
     // one box, per-layer fixed cost the same (profiles/conv_f32_epilogue_layers_steps.txt) -- the two other workgroups of the CU cover it.
-    fetch(0);
+    // Every tile has at least two K steps (32 stored channels = two 16-channel steps; the first layer's nine taps = five): stage 1 always exists,
+    // stage 2 is the zero page on a two-step tile (advance() behind stage 1 was the tile's last real request).
+    request(0); advance();
     store(0, 0);
     if (tid < BM / 4) *(sd_f4*)(sBias + 4 * tid) = bq;
-    if (ksteps > 1) fetch(NSET - 1);
-    if (DEEP && ksteps > 2) fetch(0);
+    request(NSET - 1); advance();
+    if (DEEP && (ALWAYS || ksteps > 2)) { request(0); advance(); }
     __syncthreads();
     // Measured around this loop at batch 128 (ms per detector batch; the ablation builds -- no barrier / no staging / no fragment reads -- gave wrong results, existed for timing only and are no longer in this source):
     // as is 121.0-122.5; without the barrier -1 % (122.9 against 124.1, measured before the two-step prefetch); without any staging (no
     // loads, no LDS writes, no address updates) 109.3; staging without the
     // global loads 120.1 -- i.e. what the staging costs is not the memory latency.  Requests issued unconditionally (so that the
-    // compiler can wait with vmcnt(7..4) instead of vmcnt(3..0)) 122.2; a staging map whose ds_write_b128 passes hit 16 distinct bank
+    // compiler can wait with vmcnt(7..4) instead of vmcnt(3..0)) 122.2 (neutral then; with the whole step straight-line and the compiler's own
+    // order it is - 3.2 % on the headline, PLACED it is + 1.1 ... + 1.8 %: sd_f32_place above); a staging map whose ds_write_b128 passes hit 16 distinct bank
     // quads (SQ_LDS_BANK_CONFLICT 0 instead of 33 % of the LDS-active cycles, but the LDS is busy only 10-16 % of the time) 123.7; the
     // barrier moved in front of the step's last chunk with the next step's first fragments requested right behind it (the post-barrier
     // LDS round trip under 16 MFMAs) 121.4.  The same tile staged entirely by LDS-DMA (global_load_lds_dwordx4 into unpadded, XOR-
@@ -290,11 +361,20 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
         for (int kc = 0; kc < NCH; kc++) {
             if (kc + 1 < NCH) frags(cur, kc + 1, (kc + 1) & 1);
             mfmas(kc & 1);
-            if (kc == myslot) {                         // stage ks + 1 into the other buffer, stage ks + 3 requested into the set that frees
-                if (ks + 1 < ksteps) store(cur ^ 1, DEEP ? par ^ 1 : 0);
-                if (ks + 1 + NSET < ksteps) fetch(DEEP ? par ^ 1 : 0);
+            if (kc == myslot) {                         // stage ks + 1 into the other buffer, stage ks + 1 + NSET requested into the set that frees
+                if constexpr (ALWAYS) {
+                    store(cur ^ 1, DEEP ? par ^ 1 : 0); // the tile's last step writes a zero-page set into the buffer nobody reads again
+                    request(DEEP ? par ^ 1 : 0);
+                } else {
+                    if (ks + 1 < ksteps) store(cur ^ 1, DEEP ? par ^ 1 : 0);
+                    if (ks + 1 + NSET < ksteps) { request(DEEP ? par ^ 1 : 0); advance(); }
+                }
             }
         }
+        // The 128-filter tile's staging is placed among its MFMAs (sd_f32_place: the measurements are there).  The 64-filter tile keeps the
+        // compiler's order: it has one register set (a load placed late would not be back for its write early in the next step).
+        if constexpr (BK == 16 && WM == 2 && MT == 2) sd_f32_place<NCH * 8 * MT, MT + 2, (NCH - 1) * (MT + 2), WC + XC, 4, 4, 20, 3>();
+        if constexpr (ALWAYS) advance();
         // The barrier stays BEHIND the step's last MFMA: hoisted above them (legal, they touch no memory) the two waves of a SIMD
         // would reach it a staging block apart and the earlier one would sit there with its remaining MFMAs unissued.
         __builtin_amdgcn_sched_barrier(0);
