@@ -932,6 +932,9 @@ int sd_yolo_forward_device(sd_yolo* y, const uint8_t* d_bgr, int width, int heig
 /* Test access: layer output (f16, NHWC, dense) of one image; region-layer rows [total_rows][5 + classes] of image 0
  * (only after a forward with n == 1). */
 int sd_yolo_download_layer(sd_yolo* y, int layer, int image, uint16_t* f16_nhwc_out); /* float* in SD_YOLO_F32 mode */
+/* Test access: the same with the channels the layer STORES beyond its own -- *stored_channels = its channel count rounded up to 32 (256 for a
+ * 255-channel head; the padding must stay zero), [H][W][*stored_channels]; `out` may be null to ask for the count alone. */
+int sd_yolo_download_layer_stored(sd_yolo* y, int layer, int image, uint16_t* out, int* stored_channels);
 int sd_yolo_download_region(sd_yolo* y, float* rows, int* total_rows);
 /* Host-image forms for a per-frame caller (`yolo->Segmentation_(imLeft)`, stereo_kitti.cc:107): upload + forward of one
  * 8-bit BGR image, and yolov3Segment::Segmentation's mask in host memory (image 0 of the last forward). */

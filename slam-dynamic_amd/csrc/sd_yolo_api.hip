@@ -106,6 +106,10 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
     SdYoloNetPlan P;
     const SdYoloPlanError pe = yolo_plan_net(layers, n_layers, net_w, net_h, classes, precision, P);
     if (pe.code != SD_OK) return set_err(pe.code, pe.text);
+    const bool f32mode = precision != SD_YOLO_F16;
+    SdYoloStorage S;                                      // fused shortcuts, in-place routes -- and the refusal of every list the forward could not run
+    const SdYoloPlanError se = yolo_plan_storage(layers, n_layers, P, f32mode, S);
+    if (se.code != SD_OK) return set_err(se.code, se.text);
     (SdYoloTotals&)*y = P;
     y->L.assign(layers, layers + n_layers);
     y->R.assign(P.R.begin(), P.R.end());
@@ -146,26 +150,15 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
             r.out = r.own;
             if (ok && r.outC != r.C) ok = hipMemset(r.out, 0, nB * r.H * r.W * r.outC * eb) == hipSuccess;
         } else if (l.type == SD_YOLO_SHORTCUT) {
-            // fused into the preceding convolution's epilogue when that output has no other consumer
-            bool fuse = i > 0 && y->L[i - 1].type == SD_YOLO_CONV && yolo_resolve(i, l.from[0]) != i - 1;
-            for (int j = 0; fuse && j < n_layers; j++) {
-                if (j == i) continue;
-                const sd_yolo_layer& o = y->L[j];
-                if (o.type == SD_YOLO_SHORTCUT || o.type == SD_YOLO_ROUTE)
-                    for (int k = 0; k < o.nfrom; k++) if (yolo_resolve(j, o.from[k]) == i - 1) fuse = false;
-            }
-            if (fuse) { r.out = y->R[i - 1].out; r.alias = true; }
-            else { alloc(r.own, nB * r.H * r.W * r.outC * eb + 64); r.out = r.own; }
+            // fused into the preceding convolution's epilogue (yolo_plan_storage refuses the lists where that output has another consumer)
+            r.out = y->R[i - 1].out; r.alias = true;
         } else if (l.type == SD_YOLO_ROUTE && l.nfrom == 1) {
             r.out = y->R[yolo_resolve(i, l.from[0])].out; r.alias = true; r.outC = y->R[yolo_resolve(i, l.from[0])].outC;
         } else if (l.type == SD_YOLO_ROUTE) {
             alloc(r.own, nB * r.H * r.W * r.outC * eb + 64);
             r.out = r.own;
         } else if (l.type == SD_YOLO_UPSAMPLE) {
-            // materialised only inside the following 2-input route (k_upsample_concat); stand-alone upsample unsupported
-            if (!(i + 1 < n_layers && y->L[i + 1].type == SD_YOLO_ROUTE && y->L[i + 1].nfrom == 2 && yolo_resolve(i + 1, y->L[i + 1].from[0]) == i)) {
-                return set_err(SD_ERR_UNSUPPORTED, "[upsample] must feed a 2-input [route] as its first input");
-            }
+            // materialised only inside the following 2-input route (yolo_plan_storage has checked that one follows)
         } else if (l.type == SD_YOLO_YOLO) {
             r.out = y->R[i - 1].out; r.alias = true; r.outC = y->R[i - 1].outC;
         }
@@ -174,19 +167,13 @@ int sd_yolo_create_prec(sd_yolo** out, const sd_yolo_layer* layers, int n_layers
     // written IN PLACE -- its producer's output pointer becomes the route buffer at the channel offset, its stride the route's channel count -- so the
     // route copies only the up-sampled half (k_upsample_into_f32).  Possible when the producer is a convolution (with or without a fused shortcut)
     // and its tensor is dense; every consumer reads it through (pointer, channel stride) anyway.
-    for (int i = 0; ok && y->f32 && i < n_layers; i++) {
+    for (int i = 0; ok && i < n_layers; i++) {
+        if (!S.inPlace[i]) continue;                       // yolo_plan_storage: the producer is a convolution (with or without a fused shortcut), its tensor dense, this route its only one
         const sd_yolo_layer& l = y->L[i];
-        if (l.type != SD_YOLO_ROUTE || l.nfrom != 2) continue;
         const int fa = yolo_resolve(i, l.from[0]), fb = yolo_resolve(i, l.from[1]);
         const int src = yolo_resolve(fa, -1);
         sd_yolo::Rt& rb = y->R[fb];
-        const int conv = y->L[fb].type == SD_YOLO_CONV ? fb : (y->L[fb].type == SD_YOLO_SHORTCUT && rb.alias ? fb - 1 : -1);
-        if (conv < 0 || y->L[fa].type != SD_YOLO_UPSAMPLE || rb.outC != rb.C || y->R[conv].outC != y->R[conv].C || (y->R[src].C % 4) || (rb.C % 4)) continue;
-        bool soleRoute = true;                             // one route only may own the tensor's storage
-        for (int j = 0; j < n_layers; j++)
-            if (j != i && y->L[j].type == SD_YOLO_ROUTE)
-                for (int k = 0; k < y->L[j].nfrom; k++) if (yolo_resolve(j, y->L[j].from[k]) == fb) soleRoute = false;
-        if (!soleRoute) continue;
+        const int conv = y->L[fb].type == SD_YOLO_CONV ? fb : fb - 1;
         float* at = y->R[i].as<float>() + y->R[src].C;
         y->R[conv].out = at; y->R[conv].outC = y->R[i].C;
         rb.out = at; rb.outC = y->R[i].C;
@@ -500,7 +487,7 @@ int sd_yolo_forward_device(sd_yolo* y, const uint8_t* d_bgr, int width, int heig
             }
             if (rc != SD_OK) return rc;
         } else if (l.type == SD_YOLO_SHORTCUT) {
-            if (!r.alias) return set_err(SD_ERR_UNSUPPORTED, "unfused [shortcut] is not implemented");
+            if (!r.alias) return set_err(SD_ERR_UNSUPPORTED, "unfused [shortcut] is not implemented");      // a guard: sd_yolo_create_prec refuses such a list
         } else if (l.type == SD_YOLO_ROUTE && l.nfrom == 2) {
             const int fa = yolo_resolve((int)i, l.from[0]), fb = yolo_resolve((int)i, l.from[1]);
             const int src = yolo_resolve(fa, -1);          // the layer the [upsample] reads
@@ -557,6 +544,23 @@ int sd_yolo_download_layer(sd_yolo* y, int layer, int image, uint16_t* out)
     } else {
         HIPCHK(hipMemcpy2D(out, (size_t)r.C * eb, src, (size_t)r.outC * eb, (size_t)r.C * eb, pix, hipMemcpyDeviceToHost));
     }
+    return SD_OK;
+}
+
+int sd_yolo_download_layer_stored(sd_yolo* y, int layer, int image, uint16_t* out, int* stored_channels)
+{
+    if (!y || !stored_channels || layer < 0 || layer >= (int)y->L.size()) return SD_ERR_INVALID;
+    const sd_yolo::Rt& r = y->R[layer];
+    // a tensor written in place into a route's buffer is dense (its stride is the route's): nothing of its own lies beyond its channels
+    const int S = std::min(r.outC, (r.C + 31) / 32 * 32);
+    *stored_channels = S;
+    if (!out) return SD_OK;
+    if (image < 0 || image >= y->lastN) return SD_ERR_INVALID;
+    if (!r.out) return set_err(SD_ERR_INVALID, "layer has no materialised output");
+    HIPCHK(hipDeviceSynchronize());
+    const size_t pix = (size_t)r.H * r.W, eb = y->f32 ? 4 : 2;
+    const unsigned char* src = r.as<const unsigned char>() + (size_t)image * pix * r.outC * eb;
+    HIPCHK(hipMemcpy2D(out, (size_t)S * eb, src, (size_t)r.outC * eb, (size_t)S * eb, pix, hipMemcpyDeviceToHost));
     return SD_OK;
 }
 

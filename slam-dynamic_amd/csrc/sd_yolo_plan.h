@@ -1,5 +1,6 @@
 // Host-side plan of the detector, with no HIP in it (what sd_plan.h is for the extractor): the built-in YOLOv3 layer list, the shape pass
-// of a network (yolo_plan_net: per-layer sizes, weight offsets, the kernel class of every convolution, FLOP totals) and THE choice of the kernel,
+// of a network (yolo_plan_net: per-layer sizes, weight offsets, the kernel class of every convolution, FLOP totals), where the outputs of its
+// [shortcut] and [route] layers live and which lists are refused (yolo_plan_storage) and THE choice of the kernel,
 // tiles and grid that run a convolution at a batch size (yolo_plan_launch).  sd_yolo_api.hip launches what these records say and decides nothing
 // itself; tests/test_yolo_plan.py compiles this header alone and pins the records.  The measurements behind the choices: DESIGN.md 4.1.
 #pragma once
@@ -153,6 +154,78 @@ static inline SdYoloPlanError yolo_plan_net(const sd_yolo_layer* L, int n_layers
         } else return {SD_ERR_INVALID, "unknown layer type"};
         H = r.H; W = r.W; C = r.C;
         if ((l.type == SD_YOLO_CONV) && (r.C % 4) && r.C != 3 * (5 + classes)) return {SD_ERR_UNSUPPORTED, "filters must be a multiple of 4"};
+    }
+    return {SD_OK, nullptr};
+}
+
+// Where the outputs of the layers that compute nothing live, decided at creation: which [shortcut]s are fused into the epilogue of the convolution
+// before them, and which 2-input [route]s get their second input written IN PLACE by its producer (f32-class modes: only the up-sampled half is
+// then copied, k_upsample_into_f32) instead of being copied whole (k_upsample_concat).  Every list the forward pass could not run is refused here,
+// before anything is allocated or launched: sd_yolo_create_prec creates no detector for it.
+struct SdYoloStorage { std::vector<char> fused, inPlace; };      // per layer: fused [shortcut]; 2-input [route] whose second input is written in place
+static inline SdYoloPlanError yolo_plan_storage(const sd_yolo_layer* L, int n_layers, const SdYoloNetPlan& P, bool f32, SdYoloStorage& S)
+{
+    S.fused.assign(n_layers, 0); S.inPlace.assign(n_layers, 0);
+    std::vector<char> strided(n_layers, 0);      // tensors written in place into a route's buffer: their channel stride is the route's
+    auto read_by_route = [&](int layer, int except) {
+        for (int j = 0; j < n_layers; j++)
+            if (j != except && L[j].type == SD_YOLO_ROUTE)
+                for (int k = 0; k < L[j].nfrom; k++) if (yolo_resolve(j, L[j].from[k]) == layer) return true;
+        return false;
+    };
+    for (int i = 0; i < n_layers; i++) {
+        const sd_yolo_layer& l = L[i];
+        if (l.type == SD_YOLO_SHORTCUT) {
+            // fused when the preceding convolution's output has no other consumer (the layer after a [shortcut] reads the sum, never the addend)
+            bool fuse = i > 0 && L[i - 1].type == SD_YOLO_CONV && yolo_resolve(i, l.from[0]) != i - 1;
+            for (int j = 0; fuse && j < n_layers; j++) {
+                if (j == i) continue;
+                if (L[j].type == SD_YOLO_SHORTCUT || L[j].type == SD_YOLO_ROUTE)
+                    for (int k = 0; k < L[j].nfrom; k++) if (yolo_resolve(j, L[j].from[k]) == i - 1) fuse = false;
+            }
+            if (!fuse) return {SD_ERR_UNSUPPORTED, "unfused [shortcut] is not implemented: it must follow a convolution whose output nothing else reads"};
+            const int f = yolo_resolve(i, l.from[0]);
+            if (L[f].type == SD_YOLO_UPSAMPLE) return {SD_ERR_UNSUPPORTED, "[shortcut] from an [upsample]: it is materialised only inside a [route]"};
+            S.fused[i] = 1;
+        } else if (l.type == SD_YOLO_UPSAMPLE) {
+            // materialised only inside the following 2-input route; stand-alone upsample unsupported
+            if (!(i >= 1 && i + 1 < n_layers && L[i + 1].type == SD_YOLO_ROUTE && L[i + 1].nfrom == 2 && yolo_resolve(i + 1, L[i + 1].from[0]) == i))
+                return {SD_ERR_UNSUPPORTED, "[upsample] must feed a 2-input [route] as its first input"};
+            if (L[i - 1].type == SD_YOLO_UPSAMPLE) return {SD_ERR_UNSUPPORTED, "[upsample] of an [upsample]"};
+            if (read_by_route(i, i + 1)) return {SD_ERR_UNSUPPORTED, "[upsample] must feed a 2-input [route] as its first input"};
+        } else if (l.type == SD_YOLO_ROUTE) {
+            if (l.nfrom != 1 && l.nfrom != 2) return {SD_ERR_INVALID, "bad route"};
+            const int fa = yolo_resolve(i, l.from[0]);
+            if (l.nfrom == 1) {
+                if (L[fa].type == SD_YOLO_UPSAMPLE) return {SD_ERR_UNSUPPORTED, "[upsample] must feed a 2-input [route] as its first input"};
+                continue;
+            }
+            const int fb = yolo_resolve(i, l.from[1]);
+            if (L[fa].type != SD_YOLO_UPSAMPLE || fa != i - 1 || L[fb].type == SD_YOLO_UPSAMPLE)
+                return {SD_ERR_UNSUPPORTED, "a 2-input [route] must take the [upsample] before it as its first input"};
+        }
+    }
+    // in place (f32-class modes): the producer is a convolution (with or without a fused shortcut), its tensor is dense, and one route only may
+    // own the tensor's storage
+    for (int i = 0; f32 && i < n_layers; i++) {
+        const sd_yolo_layer& l = L[i];
+        if (l.type != SD_YOLO_ROUTE || l.nfrom != 2) continue;
+        const int fb = yolo_resolve(i, l.from[1]), src = yolo_resolve(i, l.from[0]) - 1;      // src: the layer the [upsample] reads
+        const SdYoloLayerPlan& ra = P.R[src]; const SdYoloLayerPlan& rb = P.R[fb];
+        const int conv = L[fb].type == SD_YOLO_CONV ? fb : (L[fb].type == SD_YOLO_SHORTCUT && S.fused[fb] ? fb - 1 : -1);
+        if (conv >= 0 && rb.outC == rb.C && P.R[conv].outC == P.R[conv].C && (ra.C % 4) == 0 && (rb.C % 4) == 0 && !read_by_route(fb, i)) {
+            S.inPlace[i] = 1; strided[conv] = strided[fb] = 1;
+        }
+    }
+    // every other 2-input route is copied whole: k_upsample_concat moves 16-byte pieces of dense tensors
+    for (int i = 0; i < n_layers; i++) {
+        const sd_yolo_layer& l = L[i];
+        if (l.type != SD_YOLO_ROUTE || l.nfrom != 2 || S.inPlace[i]) continue;
+        const int fb = yolo_resolve(i, l.from[1]), src = yolo_resolve(i, l.from[0]) - 1;
+        const SdYoloLayerPlan& ra = P.R[src]; const SdYoloLayerPlan& rb = P.R[fb];
+        const int piece = f32 ? 4 : 8;
+        if (ra.outC != ra.C || rb.outC != rb.C || strided[src] || strided[fb] || (ra.C % piece) || (rb.C % piece))
+            return {SD_ERR_UNSUPPORTED, f32 ? "route inputs must be dense, channels % 4 == 0" : "route inputs must be dense, channels % 8 == 0"};
     }
     return {SD_OK, nullptr};
 }

@@ -210,6 +210,17 @@ class Detector:
         fe.check(fe.lib().sd_yolo_download_layer(self.h, layer, image, fe._p(out)))
         return out
 
+    def layer_stored(self, layer, image=0):
+        """layer_output with the channels the layer stores beyond its own (a 255-channel head: 256, the last one padding)."""
+        L = fe.lib()
+        L.sd_yolo_download_layer_stored.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+        s = C.c_int()
+        fe.check(L.sd_yolo_download_layer_stored(self.h, layer, image, None, C.byref(s)))
+        h, w, _ = self.layer_shape(layer)
+        out = np.zeros((h, w, s.value), np.float32 if self.precision in ("f32", "f32w", "f32x3") else np.float16)
+        fe.check(L.sd_yolo_download_layer_stored(self.h, layer, image, fe._p(out), C.byref(s)))
+        return out
+
     def region_rows(self):
         n = C.c_int()
         rows = np.zeros((4 * 18900, 85), np.float32)
