@@ -332,6 +332,89 @@ int sd_sim3_ransac_device(int n_problems, const int32_t* corr_offset, const sd_s
 /* The same from host arrays: uploads, runs, synchronises. */
 int sd_sim3_ransac_host(int n_problems, const int32_t* corr_offset, const sd_sim3_corr* corr, const sd_sim3_problem* problems,
                         double probability, int min_inliers, int max_iterations, sd_sim3_result* results, uint8_t* inliers);
+/* ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241), as LoopClosing::ComputeSim3 calls it after SearchBySim3 (:326) ----
+ * Up to SD_SIM3_MAX_PROBLEMS independent problems in one launch: one free Sim3 vertex, two projection edges per correspondence
+ * (x1 = S12 X2 and x2 = S12^-1 X1), Huber with delta = (float)sqrt(th2), g2o's Levenberg-Marquardt with NUMERIC Jacobians (delta =
+ * 1e-9), optimize(5), the chi2 classification, optimize(5 or 10) and the final count, all in one kernel (DESIGN Q45).
+ * A correspondence is one that passed the `continue`s of :1101-1136 (the caller applies them, as for sd_sim3_ransac_*), in i order:
+ * xw1 / xw2 = GetWorldPos() of pMP1 / pMP2, obs1 / obs2 = mvKeysUn[i].pt / mvKeysUn[i2].pt, inv_sigma2_1 / _2 =
+ * mvInvLevelSigma2[octave] of the two key points, tag = i (carried, never read).  Camera coordinates are R * xw + t of Tcw1 / Tcw2 in
+ * f32, the statement sd_sim3_ransac_* uses.  R12 (row-major 3x3) / t12 / s12: the prior g2oS12 = Sim3(R, t, s). */
+typedef struct sd_sim3_opt_corr {
+    float xw1[3], xw2[3];
+    float obs1[2], obs2[2];
+    float inv_sigma2_1, inv_sigma2_2;
+    int32_t tag;
+} sd_sim3_opt_corr;                               /* 52 bytes */
+typedef struct sd_sim3_opt_problem {
+    float Tcw1[16], Tcw2[16];
+    float fx1, fy1, cx1, cy1;                     /* pKF1->mK */
+    float fx2, fy2, cx2, cy2;                     /* pKF2->mK */
+    float R12[9], t12[3], s12;
+    float th2;
+    int32_t fix_scale;                            /* bFixScale */
+} sd_sim3_opt_problem;                            /* 220 bytes */
+/* ret = the return value (nIn, or 0 from `if (nCorrespondences - nBad < 10) return 0`); n_bad = nBad of the first check;
+ * more_iterations = nMoreIterations; per optimize() call r: iterations[r] = LM iterations run, trials[r] = solves (the sum of
+ * qmax), stop[r] = SD_SIM3_OPT_STOP_*.  written = 1 when g2oS12 was assigned (:1238): q (x y z w) / t / s are then the estimate, else
+ * the prior as Sim3(R12, t12, s12) holds it -- the `return 0` path leaves g2oS12 alone but keeps the matches it set to NULL.
+ * T12 = [s R | t] row-major 4x4 in f32 (Converter::toCvSE3(s * R, t)). */
+#define SD_SIM3_OPT_STOP_OK 0                     /* every iteration returned OK */
+#define SD_SIM3_OPT_STOP_TRIALS 1                 /* Terminate: ten trials after a failure */
+#define SD_SIM3_OPT_STOP_RHO_ZERO 2               /* Terminate: rho == 0 */
+#define SD_SIM3_OPT_STOP_NO_GAIN 3                /* Terminate: _nBad >= 3 */
+typedef struct sd_sim3_opt_result {
+    int32_t ret, n_correspondences, n_bad, more_iterations;
+    int32_t iterations[2], trials[2], stop[2], written, reserved;
+    double q[4], t[3], s;
+    float T12[16];
+} sd_sim3_opt_result;                             /* 176 bytes */
+/* Problem p owns correspondences [corr_offset[p], corr_offset[p+1]) of d_corr; corr_offset [n_problems + 1] and problems
+ * [n_problems] are HOST arrays, d_ arrays device memory.  Out: d_results [n_problems]; d_state [correspondences] u8, indexed like
+ * d_corr: 0 = inlier at the end, 1 = removed by the first check (vpMatches1[i] = NULL, edges removed), 2 = set to NULL by the
+ * last check.  More than SD_SIM3_MAX_PROBLEMS problems, more than SD_SIM3_MAX_CORRESPONDENCES in a problem, th2 not > 0, a
+ * non-finite R12 / t12 / s12, offsets that do not start at 0 or decrease: SD_ERR_INVALID before anything is launched, never a
+ * truncation.  Stateless with respect to sd_batch; asynchronous on `stream` with no host synchronisation, the problem table going
+ * through a ring of 8 library-owned device tables per device as for sd_sim3_ransac_device.  A problem's bytes do not depend on what
+ * shares its launch or on its position in it. */
+int sd_sim3_optimize_device(int n_problems, const int32_t* corr_offset, const sd_sim3_opt_corr* d_corr,
+                            const sd_sim3_opt_problem* problems, sd_sim3_opt_result* d_results, uint8_t* d_state, void* stream);
+/* The same from host arrays: uploads, runs, synchronises. */
+int sd_sim3_optimize_host(int n_problems, const int32_t* corr_offset, const sd_sim3_opt_corr* corr, const sd_sim3_opt_problem* problems,
+                          sd_sim3_opt_result* results, uint8_t* state);
+/* ---- LoopClosing::ComputeSim3 after the RANSAC (src/LoopClosing.cc:312-340) as ONE launch sequence for n_jobs (keyframe, candidate)
+ * jobs of a batch, without a host round trip (DESIGN Q45): per job, from the RANSAC's answer d_ransac[job] (device, as
+ * sd_sim3_ransac_device leaves it; a job with found == 0 does not run),
+ *   1. vpMapPointMatches[i1] = vbInliers ? the BoW match : NULL -- from d_bow12 [n_jobs][cap] (the KF-KF SearchByBoW result in
+ *      d_matched12's encoding: idx2 = GetIndexInKeyFrame(pKF2), -2 when the point is not in KF2, -1 NULL) and the RANSAC's d_corr (tag =
+ *      i1) / d_inliers, rows [corr_offset[job], corr_offset[job + 1]) (corr_offset is a HOST array),
+ *   2. SearchBySim3 at `th` (the reference passes 7.5) with R12 / t12 / s12 of d_ransac[job]; the pairs it adds are merged
+ *      (vpMatches12[i1] = vpMapPoints2[idx2]),
+ *   3. the correspondences of OptimizeSim3, built in i1 order: GetMapPointMatches()[i1] and the match's point both non-NULL and not
+ *      bad, i2 = the match's index in KF2 inside [0, N2) (-2 is skipped, Optimizer.cc:1114), mvKeysUn, octave -> mvInvLevelSigma2, xw,
+ *   4. OptimizeSim3 with th2 (the reference passes 10) and fix_scale, both cameras = `cam` as in sd_batch_search_by_sim3,
+ *   5. matched = ret >= 20,  6. Scw = gScm * gSmw in f64, gSmw = Sim3(Quaterniond(R2w), t2w, 1), and its f32 4x4 [s R | t].
+ * Every other argument follows sd_batch_search_by_sim3 (slots with sd_batch_assign_grid done, Tcw1 / Tcw2 host [n_jobs][16], the point
+ * table, d_kf1_point / d_kf2_point [n_jobs][cap]), including its answer-or-refuse rule: a point index outside [-1, n_points) turns every
+ * download of the call into SD_ERR_INVALID.  The `break` over candidates and the round-robin bookkeeping stay with the caller. */
+typedef struct sd_sim3_refine_result {
+    int32_t ran, matched, n_built, reserved;      /* ran: d_ransac[job].found; n_built: correspondences handed to the optimiser */
+    double Scw_q[4], Scw_t[3], Scw_s;             /* mg2oScw (rotation x y z w); meaningful when matched */
+    float Scw[16];                                /* mScw = Converter::toCvMat(mg2oScw) */
+    sd_sim3_opt_result opt;                       /* step 4: ret, n_bad, ..., gScm */
+} sd_sim3_refine_result;                          /* 320 bytes */
+int sd_batch_compute_sim3_refine(sd_batch* b, int n_jobs, const int32_t* kf1_index, const int32_t* kf2_index, const float* Tcw1_host,
+                                 const float* Tcw2_host, const sd_sim3_result* d_ransac, const int32_t* corr_offset, const sd_sim3_corr* d_corr,
+                                 const uint8_t* d_inliers, const int32_t* d_bow12, const sd_camera* cam, float th, float th2, int fix_scale,
+                                 const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points, const int32_t* d_kf1_point,
+                                 const int32_t* d_kf2_point, void* stream);
+/* Job `job` of the last call (synchronises).  result (nullable); final12 [cap] (nullable): the final vpMapPointMatches per KF1 feature in
+ * d_matched12's encoding (idx2, -2, or -1 for NULL: never matched, or set to NULL by either check of the optimiser). */
+int sd_batch_download_sim3_refine(sd_batch* b, int job, sd_sim3_refine_result* result, int32_t* final12, int cap);
+/* One stage at a time, so that a test can feed each stage's input to a reference: merged12 [cap] = step 1's row (SearchBySim3's
+ * vpMatches12); the search's own output through sd_batch_download_sim3_matches(job); corr [cap] / state [cap] (nullable) = step 3's
+ * correspondences and the optimiser's state bytes, *n_built of them. */
+int sd_batch_download_sim3_refine_stages(sd_batch* b, int job, int32_t* merged12, sd_sim3_opt_corr* corr, uint8_t* state, int cap, int* n_built);
 /* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (src/ORBmatcher.cc:1259-1483; LoopClosing.cc:362 passes th =
  * 7.5) for n_pairs independent (KF1 slot, KF2 slot) pairs of one batch; sd_batch_assign_grid must have run on both slots of every
  * pair (SD_ERR_STATE otherwise).  Host, per pair: kf1_index / kf2_index (slots), Tcw1 / Tcw2 (GetPose(), row-major 4x4), s12, R12

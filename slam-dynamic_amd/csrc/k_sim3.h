@@ -347,6 +347,7 @@ __global__ void __launch_bounds__(256) k_sim3_inliers(SdSim3Args A)
 // ---------------------------------------------------------------- ORBmatcher::SearchBySim3 (src/ORBmatcher.cc:1259-1483)
 // Per pair (KF1 slot, KF2 slot) and direction: what the kernels read.  T1 / T2 = the key frames' poses; T21 = [sR21 | t21] and
 // T12 = [sR12 | t12] are formed on the host as Q39 freezes them.
+// pad[0] != 0: the pair is skipped by all three kernels (a job of the refine chain that does not run); the host path writes 0.
 struct SdSim3Pair { float T1[16], T2[16], T21[16], T12[16]; int slot1, slot2, pad[2]; };      // 272 bytes
 
 struct SdSim3SearchArgs {
@@ -370,6 +371,7 @@ __global__ void __launch_bounds__(256) k_sim3_mark(SdSim3SearchArgs A)
 {
     const int pair = blockIdx.y;
     const SdSim3Pair& P = A.pairs[pair];
+    if (P.pad[0]) return;
     const int N1 = A.count[P.slot1], N2 = A.count[P.slot2];
     const size_t row = (size_t)pair * A.cap;
     for (int i1 = blockIdx.x * 256 + threadIdx.x; i1 < N1; i1 += gridDim.x * 256) {
@@ -389,6 +391,7 @@ __global__ void __launch_bounds__(256) k_sim3_search(SdSim3SearchArgs A, SdLevel
     const int pair = blockIdx.y >> 1, dir = blockIdx.y & 1;
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const SdSim3Pair& P = A.pairs[pair];
+    if (P.pad[0]) return;
     const int src = dir == 0 ? P.slot1 : P.slot2, dst = dir == 0 ? P.slot2 : P.slot1;
     const int N = A.count[src];
     const int i = blockIdx.x * 4 + wv;
@@ -458,6 +461,7 @@ __global__ void __launch_bounds__(256) k_sim3_agree(SdSim3SearchArgs A)
     __shared__ int s_n[4];
     const int pair = blockIdx.x, tid = threadIdx.x;
     const SdSim3Pair& P = A.pairs[pair];
+    if (P.pad[0]) { if (tid == 0) A.nFound[pair] = 0; return; }
     const int N1 = A.count[P.slot1], N2 = A.count[P.slot2];
     const size_t row = (size_t)pair * A.cap;
     int n = 0;

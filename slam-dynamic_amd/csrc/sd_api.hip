@@ -25,6 +25,8 @@
 #include "k_fuse.h"
 #include "k_ba.h"
 #include "k_sim3.h"
+#include "k_sim3_opt.h"
+#include "k_sim3_refine.h"
 #include "k_loop.h"
 #include "k_reloc.h"
 #include "k_kfdb.h"
@@ -143,6 +145,10 @@ struct sd_batch {
     // sd_batch_search_by_sim3: pair table and per-pair rows [pairs][cap], grown with the largest call seen
     SdDevBuf<SdSim3Pair> d_s3Pairs; SdDevBuf<int> d_s3Match1, d_s3Match2, d_s3Match12, d_s3Found, d_s3Err; SdDevBuf<uint8_t> d_s3Already;
     int s3PairCap = 0, s3Pairs = 0; std::vector<SdSim3Pair> s3Host;
+    // sd_batch_compute_sim3_refine (k_sim3_refine.h): job table, merged matches, built correspondences, optimiser tables, final matches
+    SdDevBuf<SdRefineJob> d_rfJobs; SdDevBuf<int> d_rfMerged, d_rfFinal; SdDevBuf<sd_sim3_opt_corr> d_rfCorr; SdDevBuf<SdSim3OptProb> d_rfProb;
+    SdDevBuf<sd_sim3_opt_result> d_rfOpt; SdDevBuf<uint8_t> d_rfState; SdDevBuf<sd_sim3_refine_result> d_rfOut;
+    int rfJobCap = 0, rfJobs = 0; std::vector<SdRefineJob> rfHost;
     // the Scw matchers of loop closing (k_loop.h), grown with the largest call seen: the decomposed poses of sd_batch_fuse_sim3 and
     // sd_batch_search_by_projection_sim3 (host staging that outlives the upload), and for the projection its job tables, the kept keys
     // per candidate, the per-entry results and the per-job rows [jobs][cap]
@@ -2708,6 +2714,9 @@ static int ensure_sim3(sd_batch* b, int n_pairs, hipStream_t s, hipStream_t prev
     return SD_OK;
 }
 
+static int sim3_search_launch(sd_batch* b, int n_pairs, const sd_camera* cam, float th, const sd_map_point* d_points, const uint8_t* d_point_desc,
+                              int n_points, const int32_t* d_kf1_point, const int32_t* d_kf2_point, const int32_t* d_matched12, hipStream_t s);
+
 int sd_batch_search_by_sim3(sd_batch* b, int n_pairs, const int32_t* kf1_index, const int32_t* kf2_index, const float* Tcw1_host,
                             const float* Tcw2_host, const float* s12, const float* R12, const float* t12, const sd_camera* cam, float th,
                             const sd_map_point* d_points, const uint8_t* d_point_desc, int n_points, const int32_t* d_kf1_point,
@@ -2755,8 +2764,19 @@ int sd_batch_search_by_sim3(sd_batch* b, int n_pairs, const int32_t* kf1_index, 
         P.T12[15] = 1.f; P.T21[15] = 1.f;
         P.slot1 = kf1_index[p]; P.slot2 = kf2_index[p]; P.pad[0] = P.pad[1] = 0;
     }
-    const size_t rows = (size_t)n_pairs * cap;
     HIPCHK(hipMemcpyAsync(b->d_s3Pairs, b->s3Host.data(), (size_t)n_pairs * sizeof(SdSim3Pair), hipMemcpyHostToDevice, s));
+    rc = sim3_search_launch(b, n_pairs, cam, th, d_points, d_point_desc, n_points, d_kf1_point, d_kf2_point, d_matched12, s);
+    if (rc != SD_OK) return rc;
+    b->s3Pairs = n_pairs;
+    return SD_OK;
+}
+
+// the three kernels of SearchBySim3 over the pair table b->d_s3Pairs (filled by the caller, on the host or on the device)
+static int sim3_search_launch(sd_batch* b, int n_pairs, const sd_camera* cam, float th, const sd_map_point* d_points, const uint8_t* d_point_desc,
+                              int n_points, const int32_t* d_kf1_point, const int32_t* d_kf2_point, const int32_t* d_matched12, hipStream_t s)
+{
+    const int cap = b->plan.kpCap;
+    const size_t rows = (size_t)n_pairs * cap;
     HIPCHK(hipMemsetAsync(b->d_s3Already, 0, rows, s));
     HIPCHK(hipMemsetAsync(b->d_s3Match1, 0xFF, rows * 4, s)); HIPCHK(hipMemsetAsync(b->d_s3Match2, 0xFF, rows * 4, s));
     HIPCHK(hipMemsetAsync(b->d_s3Match12, 0xFF, rows * 4, s));
@@ -2780,7 +2800,6 @@ int sd_batch_search_by_sim3(sd_batch* b, int n_pairs, const int32_t* kf1_index, 
         hipLaunchKernelGGL(k_sim3_agree, dim3(n_pairs), dim3(256), 0, s, A);
         LAUNCH_CHECK("k_sim3_agree");
     }
-    b->s3Pairs = n_pairs;
     return SD_OK;
 }
 
@@ -3303,5 +3322,7 @@ int sd_batch_backproject_dense(sd_batch* b, int n_frames, const int32_t* slots, 
 #include "sd_kfdb.inc"
 #include "sd_covis.inc"
 #include "sd_reloc.inc"
+#include "sd_sim3_opt.inc"
+#include "sd_sim3_refine.inc"
 
 } // extern "C"

@@ -141,6 +141,11 @@ def lib():
         L.sd_local_ba_profile.argtypes = [i, vp]
         L.sd_sim3_ransac_device.argtypes = [i, vp, vp, vp, C.c_double, i, i, vp, vp, vp, vp]
         L.sd_sim3_ransac_host.argtypes = [i, vp, vp, vp, C.c_double, i, i, vp, vp]
+        L.sd_sim3_optimize_device.argtypes = [i, vp, vp, vp, vp, vp, vp]
+        L.sd_batch_compute_sim3_refine.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, i, vp, vp, i, vp, vp, vp]
+        L.sd_batch_download_sim3_refine.argtypes = [vp, i, vp, vp, i]
+        L.sd_batch_download_sim3_refine_stages.argtypes = [vp, i, vp, vp, vp, i, vp]
+        L.sd_sim3_optimize_host.argtypes = [i, vp, vp, vp, vp, vp]
         L.sd_batch_pose_optimize.argtypes = [vp, i, vp, vp, vp]
         L.sd_batch_download_pose.argtypes = [vp, i, vp, vp, i, C.POINTER(i), C.POINTER(i)]
         L.sd_tracker_set_pose_optimization.argtypes = [vp, i]
@@ -669,6 +674,39 @@ class Batch:
         m12 = np.zeros(self.cap, np.int32); m1 = np.zeros(self.cap, np.int32); m2 = np.zeros(self.cap, np.int32); nf = C.c_int()
         check(lib().sd_batch_download_sim3_matches(self.h, pair, _p(m12), _p(m1), _p(m2), self.cap, C.byref(nf)))
         return m12, m1, m2, nf.value
+
+    def compute_sim3_refine(self, kf1_index, kf2_index, Tcw1, Tcw2, d_ransac, corr_offset, d_corr, d_inliers, d_bow12, cam, d_points,
+                            d_point_desc, d_kf1_point, d_kf2_point, th=7.5, th2=10.0, fix_scale=False, stream=None, *, n_points):
+        """LoopClosing::ComputeSim3 after the RANSAC for job j = (slot kf1_index[j], slot kf2_index[j]) as one launch sequence: the
+        inlier BoW matches, SearchBySim3, the correspondences, OptimizeSim3, matched = ret >= 20 and Scw (include/sd_frontend.h:
+        sd_batch_compute_sim3_refine).  d_ransac / d_corr / d_inliers: the device arrays of sd_sim3_ransac_device; corr_offset (n + 1,) host;
+        d_bow12 / d_kf1_point / d_kf2_point: [n_jobs][cap] int32 device tables.  Results: download_sim3_refine, download_sim3_refine_stages,
+        download_sim3_matches."""
+        c = camera_array(cam)
+        k1 = np.ascontiguousarray(kf1_index, np.int32).reshape(-1); k2 = np.ascontiguousarray(kf2_index, np.int32).reshape(-1)
+        n = len(k1)
+        T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(-1, 16); T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(-1, 16)
+        off = np.ascontiguousarray(corr_offset, np.int32).reshape(-1)
+        if not (len(k2) == len(T1) == len(T2) == len(off) - 1 == n):
+            raise ValueError("compute_sim3_refine: one slot pair, two poses and one offset range per job")
+        check(lib().sd_batch_compute_sim3_refine(self.h, n, _p(k1), _p(k2), _p(T1), _p(T2), C.c_void_p(d_ransac or 0), _p(off), C.c_void_p(d_corr or 0),
+                                                 C.c_void_p(d_inliers or 0), C.c_void_p(d_bow12 or 0), _p(c), C.c_float(th), C.c_float(th2), int(bool(fix_scale)),
+                                                 C.c_void_p(d_points or 0), C.c_void_p(d_point_desc or 0), int(n_points), C.c_void_p(d_kf1_point or 0),
+                                                 C.c_void_p(d_kf2_point or 0), C.c_void_p(stream or 0)))
+
+    def download_sim3_refine(self, job):
+        """Job `job` of the last compute_sim3_refine -> (result (SIM3_REFINE_RESULT_DTYPE scalar), final12 (cap,): the final
+        vpMapPointMatches per KF1 feature as idx2 / -2 / -1)."""
+        res = np.zeros(1, SIM3_REFINE_RESULT_DTYPE); f12 = np.zeros(self.cap, np.int32)
+        check(lib().sd_batch_download_sim3_refine(self.h, job, _p(res), _p(f12), self.cap))
+        return res[0], f12
+
+    def download_sim3_refine_stages(self, job):
+        """-> (merged12 (cap,): what SearchBySim3 was given, corr (n_built,) SIM3_OPT_CORR_DTYPE, state (n_built,) u8); the search's own
+        output comes from download_sim3_matches(job)."""
+        m = np.zeros(self.cap, np.int32); corr = np.zeros(self.cap, SIM3_OPT_CORR_DTYPE); st = np.zeros(self.cap, np.uint8); n = C.c_int()
+        check(lib().sd_batch_download_sim3_refine_stages(self.h, job, _p(m), _p(corr), _p(st), self.cap, C.byref(n)))
+        return m, corr[:n.value].copy(), st[:n.value].copy()
 
     # -- Tracking::TrackHomo model fit (H / F from the projection matcher's point pairs)
     def estimate_motion(self, stream=None):
@@ -1214,6 +1252,47 @@ def sim3_ransac(corr_offset, corr, problems, probability=0.99, min_inliers=20, m
                                       C.c_void_p(d_r.data_ptr()), C.c_void_p(d_i.data_ptr()), None, C.c_void_p(stream)))
     torch.cuda.synchronize()
     return d_r.cpu().numpy().view(SIM3_RESULT_DTYPE)[:n].copy(), d_i.cpu().numpy()[:len(c)].copy()
+
+
+# ---- Optimizer::OptimizeSim3 on the device (include/sd_frontend.h: sd_sim3_optimize_*) ----
+SIM3_OPT_CORR_DTYPE = np.dtype([("xw1", "<f4", (3,)), ("xw2", "<f4", (3,)), ("obs1", "<f4", (2,)), ("obs2", "<f4", (2,)), ("inv_sigma2_1", "<f4"),
+                                ("inv_sigma2_2", "<f4"), ("tag", "<i4")])                               # sd_sim3_opt_corr
+SIM3_OPT_PROBLEM_DTYPE = np.dtype([("Tcw1", "<f4", (16,)), ("Tcw2", "<f4", (16,)), ("K1", "<f4", (4,)), ("K2", "<f4", (4,)), ("R12", "<f4", (9,)),
+                                   ("t12", "<f4", (3,)), ("s12", "<f4"), ("th2", "<f4"), ("fix_scale", "<i4")])   # sd_sim3_opt_problem; K = fx fy cx cy
+SIM3_OPT_RESULT_DTYPE = np.dtype([("ret", "<i4"), ("n_correspondences", "<i4"), ("n_bad", "<i4"), ("more_iterations", "<i4"),
+                                  ("iterations", "<i4", (2,)), ("trials", "<i4", (2,)), ("stop", "<i4", (2,)), ("written", "<i4"),
+                                  ("reserved", "<i4"), ("q", "<f8", (4,)), ("t", "<f8", (3,)), ("s", "<f8"), ("T12", "<f4", (16,))])   # sd_sim3_opt_result
+assert SIM3_OPT_CORR_DTYPE.itemsize == 52 and SIM3_OPT_PROBLEM_DTYPE.itemsize == 220 and SIM3_OPT_RESULT_DTYPE.itemsize == 176
+SIM3_REFINE_RESULT_DTYPE = np.dtype([("ran", "<i4"), ("matched", "<i4"), ("n_built", "<i4"), ("reserved", "<i4"), ("Scw_q", "<f8", (4,)),
+                                     ("Scw_t", "<f8", (3,)), ("Scw_s", "<f8"), ("Scw", "<f4", (16,)), ("opt", SIM3_OPT_RESULT_DTYPE)])   # sd_sim3_refine_result
+assert SIM3_REFINE_RESULT_DTYPE.itemsize == 320
+SIM3_OPT_STOP_OK, SIM3_OPT_STOP_TRIALS, SIM3_OPT_STOP_RHO_ZERO, SIM3_OPT_STOP_NO_GAIN = 0, 1, 2, 3
+
+
+def sim3_optimize(corr_offset, corr, problems, device=False):
+    """n independent Optimizer::OptimizeSim3 problems in one launch (sd_sim3_optimize_host; device=True goes through
+    sd_sim3_optimize_device with torch-owned device arrays and one explicit synchronisation).  corr_offset (n + 1,) int32, corr (E,)
+    SIM3_OPT_CORR_DTYPE, problems (n,) SIM3_OPT_PROBLEM_DTYPE.  Returns (results (n,) SIM3_OPT_RESULT_DTYPE, state (E,) u8 in the
+    order of corr: 0 inlier, 1 removed by the first check, 2 set to NULL by the last)."""
+    off = np.ascontiguousarray(corr_offset, np.int32).reshape(-1)
+    n = len(off) - 1
+    c = np.ascontiguousarray(corr, SIM3_OPT_CORR_DTYPE).reshape(-1)
+    pr = np.ascontiguousarray(problems, SIM3_OPT_PROBLEM_DTYPE).reshape(-1)
+    assert len(pr) == n
+    res = np.zeros(max(n, 1), SIM3_OPT_RESULT_DTYPE); st = np.zeros(max(len(c), 1), np.uint8)
+    if not device:
+        check(lib().sd_sim3_optimize_host(n, _p(off), _p(c), _p(pr), _p(res), _p(st)))
+        return res[:n], st[:len(c)]
+    import torch
+    lib()
+    d_c = torch.from_numpy(c.view(np.uint8).reshape(-1).copy() if len(c) else np.zeros(1, np.uint8)).cuda()
+    d_r = torch.zeros(max(n, 1) * SIM3_OPT_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    d_s = torch.zeros(max(len(c), 1), dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    check(lib().sd_sim3_optimize_device(n, _p(off), C.c_void_p(d_c.data_ptr()), _p(pr), C.c_void_p(d_r.data_ptr()), C.c_void_p(d_s.data_ptr()),
+                                        C.c_void_p(stream)))
+    torch.cuda.synchronize()
+    return d_r.cpu().numpy().view(SIM3_OPT_RESULT_DTYPE)[:n].copy(), d_s.cpu().numpy()[:len(c)].copy()
 
 
 # ---- Optimizer::LocalBundleAdjustment on the device (include/sd_frontend.h: sd_local_ba_*) ----
