@@ -55,8 +55,8 @@ __device__ __forceinline__ sd_f4 sd_f32_tail(const sd_f4 a, const sd_f4 b, const
 // groups are written).  The step is one basic block of TM MFMAs behind the R0 fragment reads of its first K chunk.  Behind MFMA g:
 //   g < ceil(RD / 2)              two of the RD fragment reads of the step's later K chunks (needed from MFMA TM / 2 on);
 //   g = W0, W0 + WS, ...          one of the NS ds_write_b128 of the next stage;
-//   g = L0, L0 + LS, ...          one of the NS global_load_dwordx4 of the stage after it, with its pointer's post-increment (load i overwrites the
-//                                 registers write i read: every write stands in front of every load);
+//   g = L0, L0 + LS, ...          one of the NS buffer_load_dwordx4 of the stage after it, alone: its address walks in scalar registers (load i
+//                                 overwrites the registers write i read: every write stands in front of every load);
 //   every other gap               nothing: what is left (lgkmcnt / vmcnt waits, scalar instructions) falls where the scheduler likes.
 // No gap holds more than one vector-memory or two LDS instructions: tools/conv_f32_loop_gaps.py prints the emitted gaps,
 // tests/test_conv_f32_loop_schedule.py pins them.  WHERE the gaps lie matters far more than that they are apart -- measured on the 128-filter
@@ -78,10 +78,7 @@ __device__ __forceinline__ void sd_f32_place()
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                  // one MFMA
         if constexpr (2 * G < RD) __builtin_amdgcn_sched_group_barrier(0x100, RD - 2 * G < 2 ? RD - 2 * G : 2, 0);      // DS reads
         else if constexpr (G >= W0 && (G - W0) % WS == 0 && (G - W0) / WS < NS) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);      // one DS write
-        else if constexpr (G >= L0 && (G - L0) % LS == 0 && (G - L0) / LS < NS) {
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                              // one VMEM read
-            __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);                              // a pointer update
-        }
+        else if constexpr (G >= L0 && (G - L0) % LS == 0 && (G - L0) / LS < NS) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);      // one VMEM read, alone
         sd_f32_place<TM, R0, RD, NS, W0, WS, L0, LS, G + 1>();
     }
 }
@@ -145,7 +142,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
         for (int n = 0; n < 2; n++)
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[m][n][r] = 0.f;
-    // Staging addresses are kept as running pointers: inside a filter tap a step only adds BK floats to each of them.  The im2col gather's
+    // (The two 32-filter tiles; the 128- and 64-filter tiles took this form one step further: "The scalar walk" below.  The one-time (y, x)
+    // arithmetic and the tap masks are common to all four.)  Staging addresses are kept as running pointers: inside a filter tap a step only adds BK floats to each of them.  The im2col gather's
     // (y, x) arithmetic and bounds tests run ONCE, here: per activation chunk a thread keeps xtrue, the address its piece would have if every
     // tap lay inside the image (64-bit: the first layers' tensors exceed 2^31 elements at batch 256; outside the image it is formed and never
     // dereferenced), and tapmask, bit t = tap t of this pixel is inside the image (and the pixel exists).  A tap change (every cin / BK steps)
@@ -163,7 +161,10 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     // The pixel of chunk 0 is split into (image, row, column) by two multiply-highs (sd_udiv); chunk i + 1 lies NT / CPR pixels further on and
     // follows from chunk i by adding the (uniform) split of that distance with carries.
     // DEEP: two register sets, a stage's tiles are requested TWO steps before they go to LDS.  The 64-filter tile <.., 1, 2, ..> stages
-    // four activation chunks per thread; a second set would cost it its third wave per SIMD (186 VGPRs) and more than it gains.
+    // four activation chunks per thread; with running pointers a second set would have cost it its third wave per SIMD (186 VGPRs).  With the
+    // scalar walk it fits (166 VGPRs at __launch_bounds__(256, 3)); measured with its step placed like the 128-filter tile's (writes behind
+    // MFMAs 4, 7, ..., 16, loads behind 19, 22, ..., 31), bit-identical: headline 1150.8 -> 1150.3 frames/s, nothing -- not kept
+    // (profiles/conv_f32_walk_bench.json).
     constexpr bool DEEP = !(WM == 1 && MT == 2);
     constexpr int NSET = DEEP ? 2 : 1;
     // ALWAYS: every K step writes a stage and requests one, whether or not the tile has one left (see request() below) -- the tiles whose weight rows
@@ -172,12 +173,38 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     // the step.  The end-of-tile handling in retap() is the same for all tiles; on these two no request follows it.
     constexpr bool ALWAYS = WC * NT == BM * CPR;
     static_assert(XC * NT == BN * CPR && NT % CPR == 0, "every thread stages XC activation chunks, all of them the same piece of their rows");
+    // The scalar walk (ALWAYS tiles).  Everything a staging address does during a tile is wave-uniform -- a step adds BK floats to every live
+    // pointer, a tap change the same tapCol / tapRow to every lane -- so these two tiles do not keep pointers at all.  They stage with buffer
+    // loads, address = descriptor base + voffset (VGPR) + soffset (SGPR):
+    //   two descriptors per workgroup, built from kernel arguments and blockIdx-derived values only (uniform to the compiler: no waterfall loop,
+    //   no v_readfirstlane), stride 0.  Weights: base = the tile's first filter row, records = its BM rows.  Activations: base = the tile's
+    //   ANCHOR, tap (0, 0), channel 0 of pixel pix0, formed in 64 bits (it lies in front of the tensor by the padding at an image's corner;
+    //   no live lane reads there), records = SD_F32_WALK_RECORDS = 2^31 bytes;
+    //   per lane, fixed for the tile: woff[i] = (filter row) wrow 4 + 16 q; xoff[i] = (chunk's tap-(0, 0) pixel - anchor pixel) 4 cinStride + 16 q, in
+    //   [0, 2^31) for every live chunk (the host refuses a layer where it could not be: yolo_f32_walk_fits, sd_yolo_plan.h); tapmask[i] as before;
+    //   the walk: wsoff and xsoff, one SGPR each.  request() adds 4 BK bytes to both with scalar adds; a tap change adds tapCol - 4 cin (tapRow -
+    //   4 cin behind a row's last tap) to xsoff -- xsoff is then the byte distance from tap (0, 0) to the current (tap, channel), never negative --
+    //   and, per activation chunk, ONE bit test and ONE select: xv[i] = bit ? xoff[i] : SD_F32_WALK_SENTINEL.  The sentinel lies outside the
+    //   records whatever the scalar offset adds: the range check answers a padded tap (and a chunk beyond the last pixel) with zeros and touches
+    //   no memory -- the zero page is not read;
+    //   the tile's end (`dead` in retap(), as before): both record counts become 0 by scalar selects, so the 1 + NSET requests behind the last
+    //   stage read nothing whatever their offsets are.  Requests stay unconditional, waits counted, the step one basic block.
+    // The loads, their order and the LDS map are the parent's: results bit for bit the same (tests/test_gpu_conv_f32_scalar_walk.py); the address
+    // arithmetic is walked on the host for every tile, chunk, tap and step of the detector's layers (tests/cpp/conv_f32_offsets_check.cpp).
+    // Static counts, VALU per loop step with its tap-change block, before -> after: 24 -> 6 on the 128-filter tile, 39 -> 12 on the 64-filter tile;
+    // none between a step's first and last MFMA (tests/test_conv_f32_scalar_walk.py).  What was measured: DESIGN.md 4.1, "The scalar walk".
+    // The two 32-filter tiles keep the pointers below, the zero page and their conditional request.
     sd_f4 xr[NSET][XC], wr[NSET][WC];
     const float* wptr[WC];
     const float* xptr[XC];
     const char* xtrue[XC];
     unsigned tapmask[XC];
     int winc[WC], xinc[XC];
+    // ALWAYS tiles: see "The scalar walk" below.  Per lane: woff / xoff (fixed for the tile) and xv, the activations' voffset of the current tap
+    unsigned woff[WC], xoff[XC], xv[XC];
+    const char* wbase = nullptr; const char* xbase = nullptr;      // the two descriptors' bases (uniform)
+    int wrec = 0, xrec = 0;                             // their record counts: 0 from the tile's end on
+    int wsoff = 0, xsoff = 0;                           // the walk: one scalar byte offset per descriptor
     const int q = tid % CPR;                            // this thread's 16-byte piece of a row, the same in all its chunks
     {
         constexpr unsigned D = NT / CPR;                // pixels between two chunks of a thread
@@ -188,6 +215,13 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
         unsigned yo = sd_udiv(pr, mWo, sWo), xo = pr - yo * Wo;
         const unsigned rowrep = ksize == 1 ? 1u : 1u | 1u << ksize | 1u << 2 * ksize;      // bit 0 of every filter row
         const unsigned rowlow = (1u << ksize) - 1u;
+        int pixelA = 0;                                 // ALWAYS: the anchor's pixel index, tap (0, 0) of pixel pix0 (scalar; negative by the padding at an image's corner)
+        if constexpr (ALWAYS) {
+            const unsigned n0 = sd_udiv((unsigned)pix0, mHoWo, sHoWo), pr0 = pix0 - n0 * HoWo, y0 = sd_udiv(pr0, mWo, sWo), x0 = pr0 - y0 * Wo;
+            pixelA = ((int)(n0 * H) + ((int)y0 * stride - pad)) * W + ((int)x0 * stride - pad);
+            xbase = (const char*)in + (long long)pixelA * (4 * cinStride);
+            xrec = (int)SD_F32_WALK_RECORDS;
+        }
 #pragma unroll
         for (int i = 0; i < XC; i++) {
             if (i > 0) {
@@ -206,18 +240,26 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
             tapmask[i] = n < (unsigned)N ? (pair ? mk >> q : mk) : 0;
             // 32-bit pixel index, 24-bit factors (the host refuses larger inputs); the byte offset is 64-bit
             const int pixel = __mul24((int)__umul24(n, H) + yi, W) + xi;
-            xtrue[i] = (const char*)in + ((long long)pixel * (4 * cinStride) + (pair ? 4 * cinStride : 16) * q);
+            if constexpr (ALWAYS) xoff[i] = (unsigned)(pixel - pixelA) * (unsigned)(4 * cinStride) + 16u * q;      // live chunks: in [0, 2^31) (yolo_f32_walk_fits)
+            else xtrue[i] = (const char*)in + ((long long)pixel * (4 * cinStride) + (pair ? 4 * cinStride : 16) * q);
         }
     }
     {
         constexpr int DW = NT / CPR;                    // filters between two chunks of a thread
         // the tile's first filter row in scalar registers; a thread's own row and piece within the tile: a 32-bit byte offset
-        const char* const w0 = (const char*)(wgt + (size_t)co0 * (unsigned)wrow) + (__umul24(tid / CPR, wrow) * 4u + 16u * q);
+        if constexpr (ALWAYS) {
+            wbase = (const char*)(wgt + (size_t)co0 * (unsigned)wrow);
+            wrec = BM * wrow * 4;                       // the tile's BM filter rows (weight rows are padded to the widest filter tile: all of them exist)
 #pragma unroll
-        for (int i = 0; i < WC; i++) {
-            const bool on = (WC * NT == BM * CPR) || tid + NT * i < BM * CPR;
-            wptr[i] = on ? (const float*)(w0 + (size_t)(4 * DW * i) * (unsigned)wrow) : zero;
-            winc[i] = on ? BK : 0;                      // (tap, channel) is one contiguous axis of a filter's weights
+            for (int i = 0; i < WC; i++) woff[i] = __umul24(tid / CPR + DW * i, wrow) * 4u + 16u * q;
+        } else {
+            const char* const w0 = (const char*)(wgt + (size_t)co0 * (unsigned)wrow) + (__umul24(tid / CPR, wrow) * 4u + 16u * q);
+#pragma unroll
+            for (int i = 0; i < WC; i++) {
+                const bool on = (WC * NT == BM * CPR) || tid + NT * i < BM * CPR;
+                wptr[i] = on ? (const float*)(w0 + (size_t)(4 * DW * i) * (unsigned)wrow) : zero;
+                winc[i] = on ? BK : 0;                  // (tap, channel) is one contiguous axis of a filter's weights
+            }
         }
     }
     int nreq = 0;                                       // stages requested so far
@@ -227,8 +269,11 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
 #pragma unroll
         for (int i = 0; i < XC; i++) {
             const bool ok = (tapmask[i] & tapbit) != 0;
-            xptr[i] = ok ? (const float*)xtrue[i] : zero;
-            xinc[i] = ok && !pair ? BK : 0;
+            if constexpr (ALWAYS) xv[i] = ok ? xoff[i] : SD_F32_WALK_SENTINEL;
+            else {
+                xptr[i] = ok ? (const float*)xtrue[i] : zero;
+                xinc[i] = ok && !pair ? BK : 0;
+            }
         }
     };
     auto retap = [&]() {                                // the next tap (`pair`: the next two)
@@ -245,42 +290,58 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
             kw++;
             const bool wrap = kw == ksize;
             if (wrap) kw = 0;
-            const ptrdiff_t d = wrap ? tapRow : tapCol;
+            if constexpr (ALWAYS) xsoff += (int)(wrap ? tapRow : tapCol) - 4 * cin;      // request() has walked the tap's cin channels
+            else {
+                const ptrdiff_t d = wrap ? tapRow : tapCol;
 #pragma unroll
-            for (int i = 0; i < XC; i++) xtrue[i] += d;
+                for (int i = 0; i < XC; i++) xtrue[i] += d;
+            }
             tapbit <<= 1;
         }
         select();
         const bool dead = nreq >= ksteps;               // the tile has no stage left to request: see request() below
+        if constexpr (ALWAYS) { wrec = dead ? 0 : wrec; xrec = dead ? 0 : xrec; }
+        else {
 #pragma unroll
-        for (int i = 0; i < WC; i++) { wptr[i] = dead ? zero : wptr[i]; winc[i] = dead ? 0 : winc[i]; }
+            for (int i = 0; i < WC; i++) { wptr[i] = dead ? zero : wptr[i]; winc[i] = dead ? 0 : winc[i]; }
+        }
     };
     select();
-    // A stage's request is split in two.  request(): its loads and the pointers' post-increments, straight-line -- on the ALWAYS tiles issued by
+    // A stage's request is split in two.  request(): its loads and the walk's two scalar adds (the pointers' post-increments on the 32-filter tiles), straight-line -- on the ALWAYS tiles issued by
     // EVERY K step and 1 + NSET times by the prologue, whether or not the tile has a stage left to ask for.  advance(): the tap walk behind it, with
     // its one branch, placed where it splits no MFMA sequence: behind a step's last MFMA, in front of its barrier.
     // Why unconditional: with `if (stage left) fetch` inside the step the compiler had to assume, at every ds_write, that the younger register
     // set's loads might not have been issued, and waited with vmcnt(3..0) -- for loads requested ONE step earlier; DEEP's two-step distance was in the
     // registers but not in the waits.  With every request always issued the waits are counted (vmcnt(7) on the 128-filter tile), and the step
     // between its first and its last MFMA is one basic block whose instructions can be placed (sd_f32_place).
-    // What a request behind the tile's last stage reads: the zero page A.zero, into a register set that goes to an LDS buffer no MFMA reads
-    // again.  The tile's last real request ends its last tap, so the retap() behind it is where the tile ends (`dead`, wave-uniform: nreq >=
-    // ksteps; it stays set for the 1 + NSET requests that follow, one per remaining step).  No load is formed from an address the parent did
-    // not read, per pointer kind:
-    //   weights       wptr walks [tap][channel] of its filter row contiguously, post-incremented; behind the last real request it points one step
-    //                 past the row (behind the tensor for the last row): the dead retap() replaces it by A.zero with increment 0 before the next load;
-    //   activations   the dead retap() moves tapbit to bit `taps` (pair: bit 10 and up) of the tap masks, which is clear in every mask (mk has
-    //                 bits [0, ksize^2) only): select() gives A.zero with increment 0, exactly as for a padded tap; later retaps shift it further up
-    //                 (three times at most, far below bit 32);
-    //   padded taps   select() as before: A.zero with increment 0 while the tap's mask bit is clear; xtrue is formed and never dereferenced
-    //                 (also behind the tile's end, where it keeps walking);
-    //   chunks beyond npix   tapmask == 0: A.zero at every tap, from the first request on.
-    // retap() only moves VALU registers: no path of the loop issues a load another does not, which is what keeps the waits counted.
+    // What a request behind the tile's last stage reads: nothing.  The tile's last real request ends its last tap, so the retap() behind it is
+    // where the tile ends (`dead`, wave-uniform: nreq >= ksteps; it stays set for the 1 + NSET requests that follow, one per remaining step): it
+    // sets both descriptors' record counts to zero, every lane of every later load is out of range and gets zeros, into a register set that goes
+    // to an LDS buffer no MFMA reads again.  No load reaches an address the parent did not read:
+    //   weights       woff + wsoff walks [tap][channel] of the lane's filter row contiguously; behind the last real request wsoff stands one step
+    //                 past the row: the dead retap() has emptied the descriptor before the next load;
+    //   activations   a live lane's address is anchor + xoff + xsoff = the parent's xtrue + channel offset exactly; behind the tile's end xsoff
+    //                 keeps walking under the empty descriptor;
+    //   padded taps   select() gives SD_F32_WALK_SENTINEL while the tap's mask bit is clear: beyond the records, zeros from the range check;
+    //   chunks beyond npix   tapmask == 0: the sentinel at every tap, from the first request on.
+    // retap() moves scalar registers, one VALU select per activation chunk and nothing else: no path of the loop issues a load another does not,
+    // which is what keeps the waits counted.  (On a tile that is not ALWAYS -- the two 32-filter tiles, whose requests are conditional -- padded
+    // taps, chunks beyond npix and absent weight rows read the zero page A.zero through pointers with increment 0.)
     auto request = [&](const int set) {
+        if constexpr (ALWAYS) {
+            const __amdgpu_buffer_rsrc_t dw = __builtin_amdgcn_make_buffer_rsrc((void*)wbase, 0, wrec, 0x00020000);
+            const __amdgpu_buffer_rsrc_t dx = __builtin_amdgcn_make_buffer_rsrc((void*)xbase, 0, xrec, 0x00020000);
 #pragma unroll
-        for (int i = 0; i < WC; i++) { wr[set][i] = *(const sd_f4*)wptr[i]; wptr[i] += winc[i]; }
+            for (int i = 0; i < WC; i++) wr[set][i] = __builtin_bit_cast(sd_f4, __builtin_amdgcn_raw_buffer_load_b128(dw, (int)woff[i], wsoff, 0));
 #pragma unroll
-        for (int i = 0; i < XC; i++) { xr[set][i] = *(const sd_f4*)xptr[i]; xptr[i] += xinc[i]; }
+            for (int i = 0; i < XC; i++) xr[set][i] = __builtin_bit_cast(sd_f4, __builtin_amdgcn_raw_buffer_load_b128(dx, (int)xv[i], xsoff, 0));
+            wsoff += 4 * BK; xsoff += 4 * BK;
+        } else {
+#pragma unroll
+            for (int i = 0; i < WC; i++) { wr[set][i] = *(const sd_f4*)wptr[i]; wptr[i] += winc[i]; }
+#pragma unroll
+            for (int i = 0; i < XC; i++) { xr[set][i] = *(const sd_f4*)xptr[i]; xptr[i] += xinc[i]; }
+        }
     };
     auto advance = [&]() {
         nreq++;
@@ -332,7 +393,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
     // wait was measured and is not kept: headline 1085.2 / 1086.2 frames/s against 1087.0 / 1087.4 with this order in alternating runs on
     // one box, per-layer fixed cost the same (profiles/conv_f32_epilogue_layers_steps.txt) -- the two other workgroups of the CU cover it.
     // Every tile has at least two K steps (32 stored channels = two 16-channel steps; the first layer's nine taps = five): stage 1 always exists,
-    // stage 2 is the zero page on a two-step tile (advance() behind stage 1 was the tile's last real request).
+    // stage 2 is all zeros on a two-step tile (advance() behind stage 1 was the tile's last real request).
     request(0); advance();
     store(0, 0);
     if (tid < BM / 4) *(sd_f4*)(sBias + 4 * tid) = bq;
@@ -363,7 +424,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 8 ? 1 : (WM == 2 && BK == 16 ? 
             mfmas(kc & 1);
             if (kc == myslot) {                         // stage ks + 1 into the other buffer, stage ks + 1 + NSET requested into the set that frees
                 if constexpr (ALWAYS) {
-                    store(cur ^ 1, DEEP ? par ^ 1 : 0); // the tile's last step writes a zero-page set into the buffer nobody reads again
+                    store(cur ^ 1, DEEP ? par ^ 1 : 0); // the tile's last step writes a set of zeros into the buffer nobody reads again
                     request(DEEP ? par ^ 1 : 0);
                 } else {
                     if (ks + 1 < ksteps) store(cur ^ 1, DEEP ? par ^ 1 : 0);

@@ -478,6 +478,10 @@ int sd_yolo_forward_device(sd_yolo* y, const uint8_t* d_bgr, int width, int heig
                 // the kernels index pixels in 32 bits (k_conv_f32's gather: 24-bit factors) and move between taps by 32-bit byte distances
                 if (S.tapRow > INT_MAX || S.tapRow < INT_MIN || (long long)n * r.H * r.W + 512 > INT_MAX || (long long)n * H * W > INT_MAX || (long long)n * H >= (1 << 23) || W >= (1 << 23))
                     return set_err(SD_ERR_UNSUPPORTED, "convolution too large for the f32 kernels' 32-bit pixel index");
+                // the two unconditional tiles address their staging loads as descriptor base + 32-bit lane offset + scalar walk
+                if ((K.kernel == SD_YK_F32_16_2_2_4 || K.kernel == SD_YK_F32_16_1_2_4) &&
+                    !yolo_f32_walk_fits(K.kernel == SD_YK_F32_16_2_2_4 ? 128 : 256, H, W, r.H, r.W, l.size, r.cinPad, Cs))
+                    return set_err(SD_ERR_UNSUPPORTED, "convolution too large for the f32 kernels' 32-bit staging offsets");
                 A.mHoWo = S.hoWo.m; A.sHoWo = S.hoWo.s; A.mWo = S.wo.m; A.sWo = S.wo.s;
                 A.mPerGroup = S.perGroup.m; A.sPerGroup = S.perGroup.s; A.mGroupY = S.groupY.m; A.sGroupY = S.groupY.s;
                 A.tapCol = (int)S.tapCol; A.tapRow = (int)S.tapRow;

@@ -311,6 +311,25 @@ static inline SdF32Setup yolo_f32_setup(int tilesX, int groupY, int Ho, int Wo, 
     return S;
 }
 
+// The scalar staging walk of k_conv_f32's two unconditional tiles (128 and 64 filters; k_yolo32.h, "The scalar walk"): a staging load's address is
+// descriptor base + per-lane byte offset (32 bits, fixed for the tile) + one scalar byte offset per descriptor that walks the K steps.
+//   SD_F32_WALK_RECORDS    record count of the activations' descriptor: its base, the tile's anchor, is tap (0, 0), channel 0 of the tile's first
+//                          pixel and every live lane's offset + walk + 16 stays below it (yolo_f32_walk_fits)
+//   SD_F32_WALK_SENTINEL   the per-lane offset of a padded tap (and of a pixel beyond the last): outside the records whatever the scalar offset adds,
+//                          so the descriptor's range check answers zeros without touching memory
+#define SD_F32_WALK_RECORDS 0x80000000u
+#define SD_F32_WALK_SENTINEL 0x80000000u
+// Does a layer fit that walk?  A tile of bn output pixels spans at most (bn - 1) / (Ho Wo) + 1 image boundaries, and within an image a pixel's
+// tap (0, 0) lies less than H W input pixels behind another's: a live lane's offset is below ((bn - 1) / (Ho Wo) + 2) H W pixels + its piece (48
+// bytes); the walk adds at most the last tap's distance ((ksize - 1) (W + 1) pixels) and the tap's cin channels.  tests/cpp/conv_f32_offsets_check.cpp
+// walks every lane of the detector's layers against it.
+static inline bool yolo_f32_walk_fits(int bn, int H, int W, int Ho, int Wo, int ksize, int cin, int cinStride)
+{
+    const long long lane = ((long long)((bn - 1) / (Ho * Wo)) + 2) * H * W * 4ll * cinStride + 48;
+    const long long walk = (long long)(ksize - 1) * (W + 1) * 4ll * cinStride + 4ll * cin;
+    return lane + walk + 16 <= (long long)SD_F32_WALK_RECORDS;
+}
+
 // The launch of convolution `l` (the network's first when `first`) with shape record `r` on a batch of n images.
 static inline SdYoloLaunch yolo_plan_launch(const sd_yolo_layer& l, const SdYoloLayerPlan& r, bool first, int n)
 {

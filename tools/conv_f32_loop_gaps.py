@@ -1,7 +1,7 @@
 """What sits between the MFMAs of k_conv_f32's K steps in the compiler's output (developer tool, also used by
 tests/test_conv_f32_loop_schedule.py).
 
-    python tools/conv_f32_loop_gaps.py [--loop] [checkout]
+    python tools/conv_f32_loop_gaps.py [--loop | --json] [checkout]
 
 Compiles tests/cpp/conv_f32_resources.hip as tools/conv_f32_isa_counts.py does (its assembly() and instructions()) and prints, per instantiation
 and per K step in the text (the loop holds two, one per LDS buffer, a third follows it for an odd step count), every gap between two consecutive
@@ -14,7 +14,9 @@ v_mfma with its instructions by class:
   branch    s_cbranch_* / s_branch
 A step is the text from one s_barrier to the next that holds MFMAs; an MFMA gap costs the SIMD about max(the MFMA's 64 cycles, the issue costs of
 what stands in it), so what matters is that no gap collects the step's staging.  --loop prints the steps' instructions themselves (what
-profiles/conv_f32_schedule_isa.txt records); `checkout` names another tree of this repository (the parent's, for the comparison)."""
+profiles/conv_f32_schedule_isa.txt records); --json prints step_counts(), the per-step instruction counts by class that
+tests/golden/conv_f32_walk_parent.json records of a parent commit; `checkout` names another tree of this repository (the parent's, for the
+comparison)."""
 import importlib.util
 import os
 import re
@@ -127,6 +129,52 @@ def metadata(text, tile):
     return md
 
 
+def loop_part(step):
+    """The instructions of a step from its first MFMA to the barrier behind it, tap-change block included: every gap but gap 0 (which, for the
+    first step in the text, also holds blocks in front of the loop), and the tail."""
+    return [ins for gap in step[1:] for ins in gap] + list(step.tail)
+
+
+def staging_loads(step):
+    """[(mnemonic, destination, address VGPR or None)] of the vector-memory instructions of loop_part(step).  A buffer load's address register
+    is its voffset (`buffer_load_dwordx4 v[a:b], vN, s[c:d], sK offen`), a global load's the 64-bit pair."""
+    out = []
+    for op, args in loop_part(step):
+        if classify(op) == "vmem":
+            f = [a.strip() for a in args.split(",")]
+            out.append((op, f[0], f[1] if len(f) > 1 and f[1].startswith("v") else None))
+    return out
+
+
+def valu_writes(gap, reg):
+    """The VALU instructions of `gap` whose destination overlaps VGPR `reg` ("v107", or a pair "v[106:107]")."""
+    r = re.fullmatch(r"v\[(\d+):(\d+)\]", reg)
+    first, last = (int(r.group(1)), int(r.group(2))) if r else (int(reg[1:]),) * 2      # a global load's address is a register pair
+    hits = []
+    for op, args in gap:
+        if classify(op) != "valu":
+            continue
+        dst = args.split(",")[0].strip()
+        m = re.fullmatch(r"v\[(\d+):(\d+)\]", dst)
+        lo, hi = (int(m.group(1)), int(m.group(2))) if m else ((int(dst[1:]),) * 2 if re.fullmatch(r"v\d+", dst) else (-1, -1))
+        if lo <= last and first <= hi:
+            hits.append((op, args))
+    return hits
+
+
+def step_counts(text):
+    """{"16,2,2,4": [per step in the text {"loop": counts by class of loop_part(step), "whole": the same with gap 0}], ...}"""
+    out = {}
+    for tile in TILES:
+        rows = []
+        for st in steps(body(text, tile)):
+            loop = gap_counts(loop_part(st))
+            whole = gap_counts(list(st[0]) + loop_part(st))
+            rows.append({"mfma": len(st), "loop": loop, "whole": whole})
+        out[",".join(str(v) for v in tile)] = rows
+    return out
+
+
 def _line(where, gap):
     c = gap_counts(gap)
     return "    %-14s %s%s" % (where, "  ".join("%s %d" % (k, c[k]) for k in CLASSES if c[k]), "   [%s]" % ", ".join(a for o, a in gap if o == "s_waitcnt") if c["wait"] else "")
@@ -158,7 +206,12 @@ def report(text, loop=False):
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     root = os.path.abspath(args[0]) if args else ROOT
-    print(report(TOOL.assembly(TOOL.find_hipcc(), root), "--loop" in sys.argv))
+    text = TOOL.assembly(TOOL.find_hipcc(), root)
+    if "--json" in sys.argv:
+        import json
+        print(json.dumps(step_counts(text), indent=1))
+    else:
+        print(report(text, "--loop" in sys.argv))
 
 
 if __name__ == "__main__":
