@@ -142,6 +142,11 @@ typedef struct sd_camera {
  * (cell, keypoint index) order, which is the visiting order of GetFeaturesInArea (Frame.cc:735-788). */
 int sd_batch_assign_grid(sd_batch* b, int n_images, const sd_camera* cam, void* stream);
 int sd_batch_download_grid(sd_batch* b, int image, int16_t* cell, int cap);
+/* The sorted form of the grid that the window matchers walk: sorted_idx[0 .. *n_in_grid) = the indices of the in-grid keypoints
+ * ordered by (cell, index); cell_start[c] = the number of in-grid keypoints in cells below c, c = 0 .. 3072 (3073 entries,
+ * cell_start[3072] == *n_in_grid).  Read-only.  SD_ERR_STATE if sd_batch_assign_grid has not run on what the slot holds,
+ * SD_ERR_CAPACITY (with *n_in_grid set) if cap < *n_in_grid. */
+int sd_batch_download_grid_index(sd_batch* b, int image, uint16_t* sorted_idx, int cap, uint16_t* cell_start, int* n_in_grid);
 
 /* Frame::UnprojectStereo (src/Frame.cc:1074-1088) for every keypoint of frames first_image + k*image_step,
  * k < n_frames, using the depth of the preceding stereo / RGB-D step.  Twc_host: n_frames row-major 4x4

@@ -1087,6 +1087,20 @@ int sd_batch_download_grid(sd_batch* b, int image, int16_t* cell, int cap)
     return SD_OK;
 }
 
+int sd_batch_download_grid_index(sd_batch* b, int image, uint16_t* sorted_idx, int cap, uint16_t* cell_start, int* n_in_grid)
+{
+    if (!b || !sorted_idx || !cell_start || !n_in_grid || !slot_ok(b, image)) return SD_ERR_INVALID;
+    if (!b->gridValid[image]) return set_err(SD_ERR_STATE, "download_grid_index: sd_batch_assign_grid has not run on this slot");
+    int rc = sd_batch_sync(b);
+    if (rc != SD_OK) return rc;
+    HIPCHK(hipMemcpy(cell_start, b->d_cellStart + (size_t)image * (SD_GRID_CELLS + 8), (size_t)(SD_GRID_CELLS + 1) * 2, hipMemcpyDeviceToHost));
+    const int total = cell_start[SD_GRID_CELLS];
+    *n_in_grid = total;
+    if (total > cap || total > b->plan.kpCap) return set_err(SD_ERR_CAPACITY, "grid index buffer too small");
+    if (total > 0) HIPCHK(hipMemcpy(sorted_idx, b->d_sortedIdx + (size_t)image * b->plan.kpCap, (size_t)total * 2, hipMemcpyDeviceToHost));
+    return SD_OK;
+}
+
 int sd_batch_unproject(sd_batch* b, int first_image, int image_step, int n_frames, const sd_camera* cam, const float* Twc_host,
                        void* stream_)
 {

@@ -88,6 +88,7 @@ def lib():
         L.sd_batch_download_rgbd.argtypes = [vp, i, vp, vp, i]
         L.sd_batch_assign_grid.argtypes = [vp, i, vp, vp]
         L.sd_batch_download_grid.argtypes = [vp, i, vp, i]
+        L.sd_batch_download_grid_index.argtypes = [vp, i, vp, i, vp, C.POINTER(i)]
         L.sd_batch_unproject.argtypes = [vp, i, i, i, vp, vp, vp]
         L.sd_batch_mappoints_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(i)]
         L.sd_batch_set_mappoints.argtypes = [vp, i, vp, vp, i]
@@ -411,6 +412,13 @@ class Batch:
         out = np.zeros(self.cap, np.int16)
         check(lib().sd_batch_download_grid(self.h, image, _p(out), self.cap))
         return out
+
+    def download_grid_index(self, image):
+        """(sortedIdx[:n_in_grid], cellStart[3073]) of a slot: key-point indices by (cell, index) and the start of every cell."""
+        idx = np.zeros(self.cap, np.uint16); start = np.zeros(GRID_CELLS + 1, np.uint16)
+        n = C.c_int()
+        check(lib().sd_batch_download_grid_index(self.h, image, _p(idx), self.cap, _p(start), C.byref(n)))
+        return idx[:n.value].copy(), start
 
     def unproject(self, image_step, n_frames, cam, Twc, stream=None):
         c = camera_array(cam)
@@ -861,6 +869,7 @@ def distinctive_descriptors(obs_offset, d_obs_desc, d_best_obs, d_desc_out=None,
 
 NEW_MAP_POINT_DTYPE = np.dtype([("neighbour", "<i4"), ("idx1", "<i4"), ("idx2", "<i4"), ("xw", "<f4", (3,))])     # sd_new_map_point
 MAXB = 64             # SD_MAX_BOXES (include/sd_frontend.h)
+GRID_COLS, GRID_ROWS, GRID_CELLS = 64, 48, 64 * 48        # FRAME_GRID_COLS / FRAME_GRID_ROWS (include/Frame.h)
 CLOUD_POINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1")])     # sd_cloud_point
 SENSOR_MONOCULAR, SENSOR_STEREO, SENSOR_RGBD = 0, 1, 2
 
