@@ -66,6 +66,32 @@ static const char* kKernelNames[K_COUNT] = {"k_pyr_level0", "k_pyr_level", "k_fa
 #define SD_PT_TH 16
 struct SdPyrTiles { int tilesX = 0, tilesY = 0, srcRowBytes = 0, srcRowsMax = 0, extOff = 0; size_t lds = 0; bool use = false; };
 
+// ---- THE growth rule of the library-owned tables that follow the largest call seen (the nested groups of sd_batch below).  A group is a
+// list of arrays that share one size: `unit` bytes per unit of that size plus `fixed` bytes each.  need <= cap: nothing happens.  Otherwise
+// the stream the workspace used before this call (`prev`) and the stream of this call are synchronised, since either may still read the old
+// arrays; the cap and the job count of the group's last call (`jobs`, where downloads read the group) go to 0; every array is freed, and only
+// then allocated at max(need, 2 * cap) clipped to `limit` (the bound the caller enforces on `need`; `need` itself for a size the workspace
+// fixes).  A failed allocation leaves the group empty under cap 0: a non-zero cap never stands over a freed array.
+struct SdGrowArray { SdDevMem* buf; size_t unit, fixed = 0; };
+
+static int sd_grow(hipStream_t prev, hipStream_t s, size_t& cap, int* jobs, size_t need, size_t limit, std::initializer_list<SdGrowArray> arrays)
+{
+    if (need <= cap) return SD_OK;
+    if (prev != s) HIPCHK(hipStreamSynchronize(prev));
+    HIPCHK(hipStreamSynchronize(s));
+    const size_t want = std::min(std::max(need, 2 * cap), limit);
+    cap = 0;
+    if (jobs) *jobs = 0;
+    for (const SdGrowArray& a : arrays) a.buf->reset();
+    hipError_t e = hipSuccess;
+    for (const SdGrowArray& a : arrays) if (e == hipSuccess) e = a.buf->alloc(want * a.unit + a.fixed);
+    if (e != hipSuccess) for (const SdGrowArray& a : arrays) a.buf->reset();
+    HIPCHK(e);
+    cap = want;
+    return SD_OK;
+}
+#define SD_MAX_ENTRIES ((size_t)INT_MAX)      // entry tables are addressed through int32 offsets
+
 struct sd_batch {
     std::vector<SdPyrTiles> pyrTiles;      // per level: tile grid of k_pyr_level_tiles
     SdDevBuf<int> d_pyrExt;
@@ -81,6 +107,7 @@ struct sd_batch {
     int nStereo = 0;
     hipStream_t stream = nullptr;
     hipStream_t lastStream = nullptr;
+    hipStream_t prevStream = nullptr;     // lastStream before the pick_stream of this call: growth waits for both
     // device buffers
     SdDevBuf<SdDevPlan> d_plan;
     SdDevBuf<SdCell> d_cells;
@@ -121,7 +148,14 @@ struct sd_batch {
     SdDevBuf<int> d_bowImg; std::vector<uint8_t> bowValid;
     SdDevBuf<float> d_moPts; SdDevBuf<SdMotionNorm> d_moNorm; SdDevBuf<int> d_moCounts; SdDevBuf<double> d_moModels; SdDevBuf<uint8_t> d_moMaskH; SdDevBuf<uint8_t> d_moMaskF;
     SdDevBuf<SdMotionResult> d_moRes; int nMotion = 0;      // TrackHomo model fit
-    SdDevBuf<unsigned> d_lmCand; SdDevBuf<uint8_t> d_lmN; SdDevBuf<uint8_t> d_lmOvf; SdDevBuf<int> d_lmIdx; int lmCap = 0;   // local-map search scratch
+    // sd_batch_search_local_map: frame / offset table (allocated once), and the candidates per local map point, grown with the largest local map seen
+    struct LocalMap {
+        SdDevBuf<int> d_idx; SdDevBuf<unsigned> d_cand; SdDevBuf<uint8_t> d_n, d_ovf; size_t cap = 0;
+        int grow(const sd_batch* b, hipStream_t s, size_t total)
+        {
+            return sd_grow(b->prevStream, s, cap, nullptr, total, SD_MAX_ENTRIES, {{&d_cand, SD_PROJ_K * 4}, {&d_n, 1}, {&d_ovf, 1}});
+        }
+    } localMap;
     SdDevBuf<int> d_match;
     SdDevBuf<int> d_pairs;
     SdDevBuf<int> d_npairs;
@@ -132,41 +166,113 @@ struct sd_batch {
     SdDevBuf<sd_pose_edge> d_poseEdges; SdDevBuf<int> d_poseFirst; SdDevBuf<int> d_poseLast; SdDevBuf<float> d_poseT;
     SdDevBuf<uint8_t> d_poseOut; SdDevBuf<int> d_poseGood; SdDevBuf<sd_camera> d_poseCam; SdDevBuf<int> d_poseMap; SdDevBuf<int> d_poseRan;
     SdDevBuf<float> d_poseTin;
-    // SearchForTriangulation / CreateNewMapPoints (k_triangulate.h), grown on demand: the pair records, and for CreateNewMapPoints the
-    // (keyframe x neighbour) match tables, the per-match triangulation results and the compacted new points per keyframe
-    SdDevBuf<SdTriPair> d_triPairs; int triPairCap = 0; std::vector<SdTriPair> hostTriPairs;     // staging that must outlive the async upload
-    SdDevBuf<int> d_triMatch; SdDevBuf<int> d_triPairList; SdDevBuf<int> d_triNp; SdDevBuf<uint8_t> d_triOk; SdDevBuf<float> d_triXw;
-    int triTableCap = 0;
-    SdDevBuf<int> d_triOff; SdDevBuf<sd_new_map_point> d_triNew; SdDevBuf<int> d_triNnew; int triKfCap = 0, triKfs = 0;
+    // SearchForTriangulation / CreateNewMapPoints (k_triangulate.h), grown on demand: the pair records (host staging that must outlive the
+    // async upload), and for CreateNewMapPoints the (keyframe x neighbour) match tables with the per-match triangulation results, and the
+    // compacted new points per keyframe, which sd_batch_download_new_map_points reads for the `kfs` keyframes of the last call
+    struct Tri {
+        SdDevBuf<SdTriPair> d_pairs; std::vector<SdTriPair> hostPairs; size_t pairCap = 0;
+        SdDevBuf<int> d_match, d_pairList, d_np; SdDevBuf<uint8_t> d_ok; SdDevBuf<float> d_xw; size_t tableCap = 0;
+        SdDevBuf<int> d_off, d_nnew; SdDevBuf<sd_new_map_point> d_new; size_t kfCap = 0; int kfs = 0;
+        int growPairs(const sd_batch* b, hipStream_t s, size_t n) { return sd_grow(b->prevStream, s, pairCap, nullptr, n, SD_MAX_ENTRIES, {{&d_pairs, sizeof(SdTriPair)}}); }
+        int growTables(const sd_batch* b, hipStream_t s, size_t nKf, size_t nP)
+        {
+            const size_t cap = b->plan.kpCap;
+            int rc = sd_grow(b->prevStream, s, kfCap, &kfs, nKf, SD_MAX_ENTRIES, {{&d_off, 4, 4}, {&d_nnew, 4}, {&d_new, cap * sizeof(sd_new_map_point)}});
+            if (rc != SD_OK) return rc;
+            return sd_grow(b->prevStream, s, tableCap, nullptr, nP, SD_MAX_ENTRIES, {{&d_match, cap * 4}, {&d_pairList, cap * 8}, {&d_np, 4}, {&d_ok, cap}, {&d_xw, cap * 12}});
+        }
+    } tri;
     // ORBmatcher::Fuse (k_fuse.h), grown with the largest call seen: job tables (slot, offsets, poses), per-entry results, and the
-    // first-taker table of k_fuse_resolve where [cap] ints do not fit the LDS
-    SdDevBuf<int> d_fuseJobs; SdDevBuf<float> d_fuseT; SdDevBuf<int> d_fuseN; SdDevBuf<int> d_fuseFirst; int fuseJobCap = 0, fuseFirstCap = 0, fuseJobs = 0;
-    SdDevBuf<int2> d_fuseBest; SdDevBuf<SdFuseHit> d_fuseHits; int fuseEntryCap = 0; SdDevBuf<int> d_fuseErr; std::vector<int32_t> fuseOff;
-    // sd_batch_search_by_sim3: pair table and per-pair rows [pairs][cap], grown with the largest call seen
-    SdDevBuf<SdSim3Pair> d_s3Pairs; SdDevBuf<int> d_s3Match1, d_s3Match2, d_s3Match12, d_s3Found, d_s3Err; SdDevBuf<uint8_t> d_s3Already;
-    int s3PairCap = 0, s3Pairs = 0; std::vector<SdSim3Pair> s3Host;
-    // sd_batch_compute_sim3_refine (k_sim3_refine.h): job table, merged matches, built correspondences, optimiser tables, final matches
-    SdDevBuf<SdRefineJob> d_rfJobs; SdDevBuf<int> d_rfMerged, d_rfFinal; SdDevBuf<sd_sim3_opt_corr> d_rfCorr; SdDevBuf<SdSim3OptProb> d_rfProb;
-    SdDevBuf<sd_sim3_opt_result> d_rfOpt; SdDevBuf<uint8_t> d_rfState; SdDevBuf<sd_sim3_refine_result> d_rfOut;
-    int rfJobCap = 0, rfJobs = 0; std::vector<SdRefineJob> rfHost;
-    // the Scw matchers of loop closing (k_loop.h), grown with the largest call seen: the decomposed poses of sd_batch_fuse_sim3 and
-    // sd_batch_search_by_projection_sim3 (host staging that outlives the upload), and for the projection its job tables, the kept keys
-    // per candidate, the per-entry results and the per-job rows [jobs][cap]
-    std::vector<float> loopT; std::vector<int32_t> loopOff;
-    SdDevBuf<int> d_loopJobs; SdDevBuf<float> d_loopT; SdDevBuf<int> d_loopNm; SdDevBuf<int> d_loopAssigned; SdDevBuf<int> d_loopErr;
-    SdDevBuf<unsigned> d_loopList; SdDevBuf<int> d_loopListN; SdDevBuf<int2> d_loopBest; int loopJobCap = 0, loopEntryCap = 0, loopJobs = 0;
+    // first-taker table of k_fuse_resolve where [cap] ints do not fit the LDS (one row per job of THIS call: its size is fixed by the call).
+    // d_err is cleared by the download that reports it; `off` holds the offsets of the last call for the downloads
+    struct Fuse {
+        SdDevBuf<int> d_jobs, d_n, d_first, d_err; SdDevBuf<float> d_T; SdDevBuf<int2> d_best; SdDevBuf<SdFuseHit> d_hits;
+        size_t jobCap = 0, entryCap = 0, firstCap = 0; int jobs = 0; std::vector<int32_t> off;
+        int grow(const sd_batch* b, hipStream_t s, size_t nJobs, size_t total, bool firstInMemory)
+        {
+            if (!d_err) { HIPCHK(d_err.alloc(4)); HIPCHK(hipMemset(d_err, 0, 4)); }
+            int rc = sd_grow(b->prevStream, s, jobCap, &jobs, nJobs, 65535, {{&d_jobs, 8, 4}, {&d_T, 64}, {&d_n, 4}});
+            if (rc == SD_OK) rc = sd_grow(b->prevStream, s, entryCap, &jobs, total, SD_MAX_ENTRIES, {{&d_best, sizeof(int2)}, {&d_hits, sizeof(SdFuseHit)}});
+            if (rc == SD_OK && firstInMemory) rc = sd_grow(b->prevStream, s, firstCap, &jobs, nJobs, nJobs, {{&d_first, (size_t)b->plan.kpCap * 4}});
+            return rc;
+        }
+    } fuse;
+    // sd_batch_search_by_sim3: pair table (staged on the host) and per-pair rows [pairs][cap], grown with the largest call seen;
+    // sd_batch_compute_sim3_refine runs its search over the same tables.  d_err belongs to one call
+    struct Sim3 {
+        SdDevBuf<SdSim3Pair> d_pairs; SdDevBuf<int> d_match1, d_match2, d_match12, d_found, d_err; SdDevBuf<uint8_t> d_already;
+        size_t cap = 0; int pairs = 0; std::vector<SdSim3Pair> host;
+        int grow(const sd_batch* b, hipStream_t s, size_t nPairs)
+        {
+            const size_t row = b->plan.kpCap;
+            if (!d_err) HIPCHK(d_err.alloc(4));
+            return sd_grow(b->prevStream, s, cap, &pairs, nPairs, 32767,
+                           {{&d_pairs, sizeof(SdSim3Pair)}, {&d_match1, row * 4}, {&d_match2, row * 4}, {&d_match12, row * 4}, {&d_found, 4}, {&d_already, row}});
+        }
+    } sim3;
+    // sd_batch_compute_sim3_refine (k_sim3_refine.h): job table (staged on the host), merged matches, built correspondences, optimiser
+    // tables, final matches
+    struct Sim3Refine {
+        SdDevBuf<SdRefineJob> d_jobs; SdDevBuf<int> d_merged, d_final; SdDevBuf<sd_sim3_opt_corr> d_corr; SdDevBuf<SdSim3OptProb> d_prob;
+        SdDevBuf<sd_sim3_opt_result> d_opt; SdDevBuf<uint8_t> d_state; SdDevBuf<sd_sim3_refine_result> d_out;
+        size_t cap = 0; int jobs = 0; std::vector<SdRefineJob> host;
+        int grow(const sd_batch* b, hipStream_t s, size_t nJobs)
+        {
+            const size_t row = b->plan.kpCap;
+            return sd_grow(b->prevStream, s, cap, &jobs, nJobs, 32767,
+                           {{&d_jobs, sizeof(SdRefineJob)}, {&d_merged, row * 4}, {&d_final, row * 4}, {&d_corr, row * sizeof(sd_sim3_opt_corr)},
+                            {&d_prob, sizeof(SdSim3OptProb)}, {&d_opt, sizeof(sd_sim3_opt_result)}, {&d_state, row}, {&d_out, sizeof(sd_sim3_refine_result)}});
+        }
+    } sim3Refine;
+    // the Scw matchers of loop closing (k_loop.h), grown with the largest call seen.  T: the decomposed poses (host staging that outlives
+    // the upload), SHARED by sd_batch_fuse_sim3 and sd_batch_search_by_projection_sim3.  The rest is the projection's: the offsets of the
+    // last call, its job tables, the kept keys per candidate, the per-entry results and the per-job rows [jobs][cap].  d_err belongs to one call
+    struct Loop {
+        std::vector<float> T; std::vector<int32_t> off;
+        SdDevBuf<int> d_jobs, d_nm, d_assigned, d_err, d_listN; SdDevBuf<float> d_T; SdDevBuf<unsigned> d_list; SdDevBuf<int2> d_best;
+        size_t jobCap = 0, entryCap = 0; int jobs = 0;
+        int grow(const sd_batch* b, hipStream_t s, size_t nJobs, size_t total)
+        {
+            if (!d_err) { HIPCHK(d_err.alloc(4)); HIPCHK(hipMemset(d_err, 0, 4)); }
+            int rc = sd_grow(b->prevStream, s, jobCap, &jobs, nJobs, 65535, {{&d_jobs, 8, 4}, {&d_T, 64}, {&d_nm, 4}, {&d_assigned, (size_t)b->plan.kpCap * 4}});
+            if (rc != SD_OK) return rc;
+            return sd_grow(b->prevStream, s, entryCap, &jobs, total, SD_MAX_ENTRIES, {{&d_list, SD_PROJ_K * 4}, {&d_listN, 4}, {&d_best, sizeof(int2)}});
+        }
+    } loop;
     // sd_batch_search_by_projection_reloc (k_reloc.h), grown with the largest call seen: job tables (slots, poses, th, ORBdist; the slot
-    // pairs staged on the host), the kept keys per keyframe feature and the result rows [jobs][cap]
-    std::vector<int2> relocSlots; int relocJobCap = 0, relocJobs = 0;
-    SdDevBuf<int2> d_relocSlots; SdDevBuf<float> d_relocT; SdDevBuf<float> d_relocTh; SdDevBuf<int> d_relocOrb; SdDevBuf<int> d_relocNm;
-    SdDevBuf<unsigned> d_relocList; SdDevBuf<int> d_relocListN; SdDevBuf<int> d_relocExit; SdDevBuf<int2> d_relocBest;
-    SdDevBuf<int> d_relocFrame; SdDevBuf<int> d_relocFrom; SdDevBuf<int> d_relocErr;
+    // pairs staged on the host), the kept keys per keyframe feature and the result rows [jobs][cap].  sd_batch_relocalize_refine reuses
+    // the slot table and the kept keys.  d_err belongs to one call
+    struct Reloc {
+        std::vector<int2> slots; size_t cap = 0; int jobs = 0;
+        SdDevBuf<int2> d_slots, d_best; SdDevBuf<float> d_T, d_th; SdDevBuf<int> d_orb, d_nm, d_listN, d_exit, d_frame, d_from, d_err; SdDevBuf<unsigned> d_list;
+        int grow(const sd_batch* b, hipStream_t s, size_t nJobs)
+        {
+            const size_t row = b->plan.kpCap;
+            if (!d_err) { HIPCHK(d_err.alloc(4)); HIPCHK(hipMemset(d_err, 0, 4)); }
+            return sd_grow(b->prevStream, s, cap, &jobs, nJobs, SD_RELOC_MAX_JOBS,
+                           {{&d_slots, sizeof(int2)}, {&d_T, 64}, {&d_th, 4}, {&d_orb, 4}, {&d_nm, 4}, {&d_list, row * SD_PROJ_K * 4}, {&d_listN, row * 4},
+                            {&d_exit, row * 4}, {&d_best, row * sizeof(int2)}, {&d_frame, row * 4}, {&d_from, row * 4}});
+        }
+    } reloc;
     // sd_batch_relocalize_refine: the assignment after each step P [5][jobs][cap], the two searches' rows [2][jobs][cap], the three
     // optimisations' edges [3][jobs][cap] with their ranges, flags and return values, the poses [4][jobs][16], mvbOutlier [jobs][cap],
-    // the sFound marks [jobs][n_points], the per-job th / ORBdist / camera of the steps (staged on the host), the results
-    SdDevBuf<int> d_rrP, d_rrFrom, d_rrExit, d_rrNm, d_rrGood, d_rrFirst, d_rrLast, d_rrOrb; SdDevBuf<int2> d_rrBest; SdDevBuf<sd_pose_edge> d_rrEdges;
-    SdDevBuf<uint8_t> d_rrEdgeOut, d_rrOutlier, d_rrMark; SdDevBuf<float> d_rrT, d_rrTh; SdDevBuf<sd_camera> d_rrCam; SdDevBuf<sd_reloc_result> d_rrRes;
-    std::vector<float> rrTh; std::vector<int> rrOrb; std::vector<sd_camera> rrCam; int rrJobCap = 0, rrJobs = 0; size_t rrMarkCap = 0;
+    // the sFound marks [jobs][n_points] (as many bytes as THIS call needs), the per-job th / ORBdist / camera of the steps (staged on the
+    // host), the results
+    struct RelocRefine {
+        SdDevBuf<int> d_P, d_from, d_exit, d_nm, d_good, d_first, d_last, d_orb; SdDevBuf<int2> d_best; SdDevBuf<sd_pose_edge> d_edges;
+        SdDevBuf<uint8_t> d_edgeOut, d_outlier, d_mark; SdDevBuf<float> d_T, d_th; SdDevBuf<sd_camera> d_cam; SdDevBuf<sd_reloc_result> d_res;
+        std::vector<float> th; std::vector<int> orb; std::vector<sd_camera> cam; size_t cap = 0, markCap = 0; int jobs = 0;
+        int grow(const sd_batch* b, hipStream_t s, size_t nJobs, size_t markBytes)
+        {
+            const size_t row = b->plan.kpCap;
+            int rc = sd_grow(b->prevStream, s, markCap, &jobs, markBytes, markBytes, {{&d_mark, 1}});
+            if (rc != SD_OK) return rc;
+            return sd_grow(b->prevStream, s, cap, &jobs, nJobs, SD_RELOC_MAX_JOBS,
+                           {{&d_P, 5 * row * 4}, {&d_from, 2 * row * 4}, {&d_exit, 2 * row * 4}, {&d_best, 2 * row * sizeof(int2)}, {&d_nm, 2 * 4}, {&d_good, 3 * 4},
+                            {&d_first, 3 * 4}, {&d_last, 3 * 4}, {&d_edges, 3 * row * sizeof(sd_pose_edge)}, {&d_edgeOut, 3 * row}, {&d_outlier, row}, {&d_T, 4 * 64},
+                            {&d_th, 2 * 4}, {&d_orb, 2 * 4}, {&d_cam, sizeof(sd_camera)}, {&d_res, sizeof(sd_reloc_result)}});
+        }
+    } relocRefine;
     std::vector<sd_camera> pairCam, hPoseCam; std::vector<int32_t> hPoseMap;
     int nPairs = 0;
     int dlPairs = 0;          // pairs sd_batch_download_matches may read (the tracker also keeps pairs at [n_lanes, 2 * n_lanes))
@@ -181,7 +287,15 @@ struct sd_batch {
     SdDevBuf<int> d_dynStart; SdDevBuf<int> d_dynStatus; SdDevBuf<int> d_sepMatches; SdDevBuf<int> d_sepRet;
     SdDevBuf<int2> d_sepPairs;
     SdDevBuf<int2> d_copyPairs;
-    SdDevBuf<unsigned long long> d_cloudBits; SdDevBuf<int> d_cloudRows; SdDevBuf<double> d_cloudT; SdDevBuf<int> d_cloudSlots; size_t cloudCap = 0;
+    // sd_batch_backproject_dense: 64-bit words of point marks (as many as the workspace's geometry needs), row counts, poses, slots
+    struct Cloud {
+        SdDevBuf<unsigned long long> d_bits; SdDevBuf<int> d_rows, d_slots; SdDevBuf<double> d_T; size_t cap = 0;
+        int grow(const sd_batch* b, hipStream_t s, size_t need, int rows3)
+        {
+            const size_t nI = b->maxImages;
+            return sd_grow(b->prevStream, s, cap, nullptr, need, need, {{&d_bits, 8}, {&d_rows, 0, nI * rows3 * 2 * 4}, {&d_T, 0, nI * 16 * 8}, {&d_slots, 0, nI * 4}});
+        }
+    } cloud;
     int itemsCap = 0;
     int nSepPairs = 0;
     const int* sepActive = nullptr;          // active mask of the last separate (tracker mode), applied by update_frame too
@@ -548,6 +662,43 @@ static void drain_profile(sd_batch* b)
 
 static bool slot_ok(const sd_batch* b, int image) { return image >= 0 && image < b->maxImages && b->slotValid[image]; }
 
+// What a call asks of the slots its job table names: in range (else SD_ERR_INVALID), holding results, sd_batch_assign_grid run,
+// sd_batch_compute_bow run (else SD_ERR_STATE).  GRID and BOW are asked together with RESULTS.
+enum { SD_SLOT_RANGE = 1, SD_SLOT_RESULTS = 2, SD_SLOT_GRID = 4, SD_SLOT_BOW = 8 };
+
+// One pass over the n jobs of a table, slot a[i] (and a2[i], where a job names two): the refusal of the first job that fails a test of
+// `need`, a job's tests in the order above.  A call that refuses every slot out of range before any state makes two calls, RANGE first.
+static int check_slots(const sd_batch* b, const char* who, const int32_t* a, const int32_t* a2, int n, int need)
+{
+    auto fails = [&](int i, auto ok) { return !ok(a[i]) || (a2 && !ok(a2[i])); };
+    for (int i = 0; i < n; i++) {
+        if ((need & SD_SLOT_RANGE) && fails(i, [&](int k) { return k >= 0 && k < b->maxImages; })) return set_err(SD_ERR_INVALID, std::string(who) + ": slot out of range");
+        if ((need & SD_SLOT_RESULTS) && fails(i, [&](int k) { return slot_ok(b, k); })) return set_err(SD_ERR_STATE, std::string(who) + ": slot holds no results");
+        if ((need & SD_SLOT_GRID) && fails(i, [&](int k) { return b->gridValid[k] != 0; }))
+            return set_err(SD_ERR_STATE, std::string(who) + ": sd_batch_assign_grid has not run on this slot");
+        if ((need & SD_SLOT_BOW) && fails(i, [&](int k) { return b->d_bowWordF && b->bowValid[k]; }))
+            return set_err(SD_ERR_STATE, std::string(who) + ": sd_batch_compute_bow has not run on this slot");
+    }
+    return SD_OK;
+}
+
+// off[0, n]: the ranges of n jobs in one table; maxLen (optional) receives the longest
+static int check_offsets(const char* who, const int32_t* off, int n, int* maxLen)
+{
+    bool ok = off[0] == 0;
+    int longest = 0;
+    for (int j = 0; j < n && ok; j++) { ok = off[j + 1] >= off[j]; longest = std::max(longest, off[j + 1] - off[j]); }
+    if (!ok) return set_err(SD_ERR_INVALID, std::string(who) + ": offsets must start at 0 and ascend");
+    if (maxLen) *maxLen = longest;
+    return SD_OK;
+}
+
+// The stream of this call: the caller's, or the one the workspace used last
+static hipStream_t pick_stream(sd_batch* b, void* stream_)
+{
+    b->prevStream = b->lastStream;
+    return b->lastStream = stream_ ? (hipStream_t)stream_ : b->lastStream;
+}
 
 static int extract_impl(sd_batch* b, const uint8_t* d_gray, size_t stride, size_t image_pitch, int n_images, void* stream_, int colorMode);
 
@@ -870,8 +1021,7 @@ int sd_batch_stereo_match(sd_batch* b, int n_frames, float mbf, float fx, void* 
     if (2 * n_frames > b->nExtracted) return set_err(SD_ERR_STATE, "stereo_match needs 2*n_frames extracted images (L,R interleaved)");
     if (!(fx > 0) || !(mbf > 0)) return set_err(SD_ERR_INVALID, "mbf and fx must be positive");
     if (b->plan.kpCap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (n_frames == 0) return SD_OK;
     const int H0 = b->plan.lv[0].H;
     // a right keypoint's band is floor(y - r) .. ceil(y + r), r = 2*scale[octave]: +2 covers floor/ceil and (int)y
@@ -931,8 +1081,7 @@ int sd_batch_rgbd_from_u16(sd_batch* b, const uint16_t* d_depth, size_t stride_e
 {
     if (!b || !d_depth || n_images < 0) return SD_ERR_INVALID;
     if (n_images > b->nExtracted) return set_err(SD_ERR_STATE, "rgbd lookup needs extracted images");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (n_images == 0) return SD_OK;
     {
         ProfScope ps(b, s, K_RGBD);
@@ -955,8 +1104,7 @@ int sd_batch_rgbd_from_f32_scaled(sd_batch* b, const float* d_depth, size_t stri
 {
     if (!b || !d_depth || n_images < 0) return SD_ERR_INVALID;
     if (n_images > b->nExtracted) return set_err(SD_ERR_STATE, "rgbd lookup needs extracted images");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (n_images == 0) return SD_OK;
     {
         ProfScope ps(b, s, K_RGBD);
@@ -1054,8 +1202,7 @@ static int assign_grid_impl(sd_batch* b, int n_images, int image_step, const sd_
 {
     if (!b || n_images < 0 || image_step < 1 || !cam_ok(cam)) return set_err(SD_ERR_INVALID, "bad grid arguments");
     if ((n_images - 1) * image_step + 1 > b->nExtracted) return set_err(SD_ERR_STATE, "grid needs extracted images");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (n_images == 0) return SD_OK;
     {
         ProfScope ps(b, s, K_GRID);
@@ -1090,8 +1237,9 @@ int sd_batch_download_grid(sd_batch* b, int image, int16_t* cell, int cap)
 int sd_batch_download_grid_index(sd_batch* b, int image, uint16_t* sorted_idx, int cap, uint16_t* cell_start, int* n_in_grid)
 {
     if (!b || !sorted_idx || !cell_start || !n_in_grid || !slot_ok(b, image)) return SD_ERR_INVALID;
-    if (!b->gridValid[image]) return set_err(SD_ERR_STATE, "download_grid_index: sd_batch_assign_grid has not run on this slot");
-    int rc = sd_batch_sync(b);
+    int rc = check_slots(b, "download_grid_index", &image, nullptr, 1, SD_SLOT_GRID);
+    if (rc != SD_OK) return rc;
+    rc = sd_batch_sync(b);
     if (rc != SD_OK) return rc;
     HIPCHK(hipMemcpy(cell_start, b->d_cellStart + (size_t)image * (SD_GRID_CELLS + 8), (size_t)(SD_GRID_CELLS + 1) * 2, hipMemcpyDeviceToHost));
     const int total = cell_start[SD_GRID_CELLS];
@@ -1107,8 +1255,7 @@ int sd_batch_unproject(sd_batch* b, int first_image, int image_step, int n_frame
     if (!b || n_frames < 0 || first_image != 0 || image_step < 1 || !cam_ok(cam) || !Twc_host)
         return set_err(SD_ERR_INVALID, "bad unproject arguments");
     if (n_frames > 0 && !slot_ok(b, (n_frames - 1) * image_step)) return set_err(SD_ERR_STATE, "unproject needs extracted images");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (n_frames == 0) return SD_OK;
     HIPCHK(hipMemcpyAsync(b->d_pose, Twc_host, (size_t)n_frames * 64, hipMemcpyHostToDevice, s));
     {
@@ -1182,14 +1329,11 @@ static int search_by_projection_impl(sd_batch* b, int pairBase, int n_pairs, con
         (n_pairs > 0 && (!cur_index || !last_index)))
         return set_err(SD_ERR_INVALID, "bad search_by_projection arguments");
     std::vector<int2> idx(n_pairs);
-    for (int p = 0; p < n_pairs; p++) {
-        if (!slot_ok(b, cur_index[p]) || !slot_ok(b, last_index[p]))
-            return set_err(SD_ERR_STATE, "search_by_projection: frame slot holds no results");
-        idx[p] = make_int2(cur_index[p], last_index[p]);
-    }
+    int rc = check_slots(b, "search_by_projection", cur_index, last_index, n_pairs, SD_SLOT_RESULTS);
+    if (rc != SD_OK) return rc;
+    for (int p = 0; p < n_pairs; p++) idx[p] = make_int2(cur_index[p], last_index[p]);
     if (b->plan.kpCap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (pairBase == 0) b->nPairs = 0;
     if (n_pairs == 0) return SD_OK;
     float* dTc = b->d_pose + (size_t)pairBase * 16;
@@ -1232,21 +1376,6 @@ static int search_by_projection_impl(sd_batch* b, int pairBase, int n_pairs, con
     return SD_OK;
 }
 
-// The scratch of sd_batch_search_local_map: frame / offset table, and candidates that grow with the largest local map seen (old ones freed first)
-static int ensure_local_map(sd_batch* b, int total, hipStream_t s)
-{
-    if (!b->d_lmIdx) HIPCHK(b->d_lmIdx.alloc((size_t)(2 * b->maxImages + 2) * sizeof(int)));
-    if (total <= b->lmCap) return SD_OK;
-    HIPCHK(hipStreamSynchronize(s));
-    const int want = std::max(total, 2 * b->lmCap);
-    b->lmCap = 0; b->d_lmCand.reset(); b->d_lmN.reset(); b->d_lmOvf.reset();
-    SdDevBuf<unsigned> cand; SdDevBuf<uint8_t> n, ovf;
-    HIPCHK(cand.alloc((size_t)want * SD_PROJ_K * 4)); HIPCHK(n.alloc((size_t)want)); HIPCHK(ovf.alloc((size_t)want));
-    b->d_lmCand = std::move(cand); b->d_lmN = std::move(n); b->d_lmOvf = std::move(ovf);
-    b->lmCap = want;
-    return SD_OK;
-}
-
 // Tracking::SearchLocalPoints (Tracking.cc:2014-2064): Frame::isInFrustum for every local map point, then
 // ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th) (ORBmatcher.cc:45-129).
 int sd_batch_search_local_map(sd_batch* b, int n_frames, const int32_t* frame_index, const int32_t* point_offset,
@@ -1259,22 +1388,22 @@ int sd_batch_search_local_map(sd_batch* b, int n_frames, const int32_t* frame_in
         (n_frames > 0 && (!frame_index || !point_offset || !Tcw_host || !d_track || !d_point_match || !d_kp_match || !d_nmatches)))
         return set_err(SD_ERR_INVALID, "bad search_local_map arguments");
     if (n_frames == 0) return SD_OK;
-    int maxM = 0;
-    for (int f = 0; f < n_frames; f++) {
-        if (!slot_ok(b, frame_index[f])) return set_err(SD_ERR_STATE, "search_local_map: frame slot holds no results");
-        const int M = point_offset[f + 1] - point_offset[f];
-        if (M < 0 || point_offset[0] != 0) return set_err(SD_ERR_INVALID, "search_local_map: point offsets must start at 0 and ascend");
-        maxM = std::max(maxM, M);
+    int maxM = 0, rc = SD_OK;
+    // frame by frame, the slot and then the ranges up to this frame: a call wrong in both ways gets the code of its first wrong frame
+    for (int f = 0; f < n_frames && rc == SD_OK; f++) {
+        rc = check_slots(b, "search_local_map", frame_index + f, nullptr, 1, SD_SLOT_RESULTS);
+        if (rc == SD_OK) rc = check_offsets("search_local_map", point_offset, f + 1, &maxM);
     }
+    if (rc != SD_OK) return rc;
     const int total = point_offset[n_frames];
     if (total > 0 && (!d_points || !d_point_desc)) return set_err(SD_ERR_INVALID, "search_local_map: no map points given");
     if (b->plan.kpCap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
-    int rc = ensure_local_map(b, total, s);
+    hipStream_t s = pick_stream(b, stream_);
+    if (!b->localMap.d_idx) HIPCHK(b->localMap.d_idx.alloc((size_t)(2 * b->maxImages + 2) * sizeof(int)));
+    rc = b->localMap.grow(b, s, total);
     if (rc != SD_OK) return rc;
-    int* dFrameOf = b->d_lmIdx;
-    int* dOff = b->d_lmIdx + b->maxImages;
+    int* dFrameOf = b->localMap.d_idx;
+    int* dOff = b->localMap.d_idx + b->maxImages;
     HIPCHK(hipMemcpyAsync(dFrameOf, frame_index, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dOff, point_offset, (size_t)(n_frames + 1) * 4, hipMemcpyHostToDevice, s));
     float* dT = b->d_pose;
@@ -1284,14 +1413,14 @@ int sd_batch_search_local_map(sd_batch* b, int n_frames, const int32_t* frame_in
         ProfScope ps(b, s, K_LOCAL_A);
         hipLaunchKernelGGL(k_local_candidates, dim3((maxM + 3) / 4, n_frames), dim3(256), 0, s, KPUN(b), b->d_desc, b->d_uright, b->d_count,
                            b->d_cellOf, b->d_sortedIdx, b->d_cellStart, (const SdMapPoint*)d_points, d_point_desc, dFrameOf, dOff, dT,
-                           (SdTrack*)d_track, b->d_lmCand, b->d_lmN, b->d_lmOvf, b->d_plan, to_cam(cam), th, viewing_cos_limit);
+                           (SdTrack*)d_track, b->localMap.d_cand, b->localMap.d_n, b->localMap.d_ovf, b->d_plan, to_cam(cam), th, viewing_cos_limit);
         LAUNCH_CHECK("k_local_candidates");
     }
     {
         ProfScope ps(b, s, K_LOCAL_B);
         const size_t lds = (size_t)cap * 4 + cap + 16;
         hipLaunchKernelGGL(k_local_resolve, dim3(n_frames), dim3(64), lds, s, KPUN(b), b->d_count, (const SdMapPoint*)d_points, dFrameOf, dOff,
-                           b->d_lmCand, b->d_lmN, b->d_lmOvf, d_occupied, d_point_match, d_kp_match, d_nmatches, b->d_err, b->d_plan, nnratio);
+                           b->localMap.d_cand, b->localMap.d_n, b->localMap.d_ovf, d_occupied, d_point_match, d_kp_match, d_nmatches, b->d_err, b->d_plan, nnratio);
         LAUNCH_CHECK("k_local_resolve");
     }
     return SD_OK;
@@ -1432,15 +1561,15 @@ int sd_batch_compute_bow(sd_batch* b, const sd_vocab* v, int n_images, const int
     if (!b || !v || n_images < 0 || n_images > b->maxImages || (n_images > 0 && !image_index) || levelsup < 0)
         return set_err(SD_ERR_INVALID, "bad compute_bow arguments");
     if (v->h.nNodes <= 1) return set_err(SD_ERR_INVALID, "compute_bow: empty vocabulary");
-    for (int i = 0; i < n_images; i++) if (!slot_ok(b, image_index[i])) return set_err(SD_ERR_STATE, "compute_bow: image slot holds no results");
+    int rc = check_slots(b, "compute_bow", image_index, nullptr, n_images, SD_SLOT_RESULTS);
+    if (rc != SD_OK) return rc;
     const int cap = b->plan.kpCap;
     int sortN = 256;                     // LDS capacity of k_bow_finalize's sort: its per-image sort size starts at 256 too
     while (sortN < cap) sortN <<= 1;
     if (sortN > 8192) return set_err(SD_ERR_UNSUPPORTED, "compute_bow: more than 8192 keypoints per image");
-    int rc = ensure_bow(b);
+    rc = ensure_bow(b);
     if (rc != SD_OK) return rc;
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (n_images == 0) return SD_OK;
     HIPCHK(hipMemcpyAsync(b->d_bowImg, image_index, (size_t)n_images * 4, hipMemcpyHostToDevice, s));
     {
@@ -1511,14 +1640,10 @@ int sd_batch_search_by_bow(sd_batch* b, int n_pairs, const int32_t* kf_index, co
     if (!b || n_pairs < 0 || n_pairs > b->maxImages || (n_pairs > 0 && (!kf_index || !frame_index)))
         return set_err(SD_ERR_INVALID, "bad search_by_bow arguments");
     std::vector<int2> idx(n_pairs);
-    for (int p = 0; p < n_pairs; p++) {
-        if (!slot_ok(b, kf_index[p]) || !slot_ok(b, frame_index[p])) return set_err(SD_ERR_STATE, "search_by_bow: frame slot holds no results");
-        if (!b->d_bowWordF || !b->bowValid[kf_index[p]] || !b->bowValid[frame_index[p]])
-            return set_err(SD_ERR_STATE, "search_by_bow: sd_batch_compute_bow has not run on these slots");
-        idx[p] = make_int2(kf_index[p], frame_index[p]);
-    }
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    int rc = check_slots(b, "search_by_bow", kf_index, frame_index, n_pairs, SD_SLOT_RESULTS | SD_SLOT_BOW);
+    if (rc != SD_OK) return rc;
+    for (int p = 0; p < n_pairs; p++) idx[p] = make_int2(kf_index[p], frame_index[p]);
+    hipStream_t s = pick_stream(b, stream_);
     b->nPairs = 0; b->dlPairs = 0;
     if (n_pairs == 0) return SD_OK;
     HIPCHK(hipMemcpyAsync(b->d_pairIdx, idx.data(), (size_t)n_pairs * sizeof(int2), hipMemcpyHostToDevice, s));
@@ -1600,14 +1725,6 @@ SdLevelTables level_tables(const sd_batch* b)
     L.nlevels = prm.nlevels;
     return L;
 }
-int tri_ensure_pairs(sd_batch* b, int n)
-{
-    if (n <= b->triPairCap) return SD_OK;
-    SdDevBuf<SdTriPair> p;
-    HIPCHK(p.alloc((size_t)n * sizeof(SdTriPair)));
-    b->d_triPairs = std::move(p); b->triPairCap = n;
-    return SD_OK;
-}
 int tri_launch_match(sd_batch* b, int n, const uint8_t* h1, const uint8_t* h2, int onlyStereo, int checkOrientation, int* match, int* pairs,
                      int* np, int* nm, hipStream_t s)
 {
@@ -1616,11 +1733,10 @@ int tri_launch_match(sd_batch* b, int n, const uint8_t* h1, const uint8_t* h2, i
     if (lds > 64 * 1024) HIPCHK(sd_raise_lds_limit((const void*)k_tri_match, (int)lds));
     ProfScope ps(b, s, K_TRI_M);
     hipLaunchKernelGGL(k_tri_match, dim3(n), dim3(SD_TRI_THREADS), lds, s, KPUN(b), b->d_desc, b->d_uright, b->d_count, b->d_fvFeat, b->d_fvRunStart,
-                       b->d_fvRunNode, b->d_bowMeta, h1, h2, b->d_triPairs, level_tables(b), cap, onlyStereo, checkOrientation, match, pairs, np, nm);
+                       b->d_fvRunNode, b->d_bowMeta, h1, h2, b->tri.d_pairs, level_tables(b), cap, onlyStereo, checkOrientation, match, pairs, np, nm);
     LAUNCH_CHECK("k_tri_match");
     return SD_OK;
 }
-bool tri_bow_ok(const sd_batch* b, int slot) { return b->d_bowWordF && b->bowValid[slot]; }
 }
 
 // ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (src/ORBmatcher.cc:814-980)
@@ -1630,26 +1746,20 @@ int sd_batch_search_for_triangulation(sd_batch* b, int n_pairs, const int32_t* k
 {
     if (!b || n_pairs <= 0 || n_pairs > b->maxImages || !cam_ok(cam) || !kf1_index || !kf2_index || !Tcw1_host || !Tcw2_host)
         return set_err(SD_ERR_INVALID, "bad search_for_triangulation arguments");
-    for (int p = 0; p < n_pairs; p++) {
-        if (kf1_index[p] < 0 || kf1_index[p] >= b->maxImages || kf2_index[p] < 0 || kf2_index[p] >= b->maxImages)
-            return set_err(SD_ERR_INVALID, "search_for_triangulation: slot out of range");
-        if (!slot_ok(b, kf1_index[p]) || !slot_ok(b, kf2_index[p])) return set_err(SD_ERR_STATE, "search_for_triangulation: slot holds no results");
-        if (!tri_bow_ok(b, kf1_index[p]) || !tri_bow_ok(b, kf2_index[p]))
-            return set_err(SD_ERR_STATE, "search_for_triangulation: sd_batch_compute_bow has not run on these slots");
-    }
+    int rc = check_slots(b, "search_for_triangulation", kf1_index, kf2_index, n_pairs, SD_SLOT_RANGE | SD_SLOT_RESULTS | SD_SLOT_BOW);
+    if (rc != SD_OK) return rc;
     if (b->plan.kpCap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     b->nPairs = 0; b->dlPairs = 0;
-    std::vector<SdTriPair>& P = b->hostTriPairs;
+    std::vector<SdTriPair>& P = b->tri.hostPairs;
     P.resize(n_pairs);
     for (int p = 0; p < n_pairs; p++) {
         P[p].img1 = kf1_index[p]; P[p].img2 = kf2_index[p]; P[p].row1 = p; P[p].row2 = p;
         tri_pair_setup(Tcw1_host + 16 * (size_t)p, Tcw2_host + 16 * (size_t)p, *cam, nullptr, false, P[p]);
     }
-    int rc = tri_ensure_pairs(b, n_pairs);
+    rc = b->tri.growPairs(b, s, n_pairs);
     if (rc != SD_OK) return rc;
-    HIPCHK(hipMemcpyAsync(b->d_triPairs, P.data(), (size_t)n_pairs * sizeof(SdTriPair), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b->tri.d_pairs, P.data(), (size_t)n_pairs * sizeof(SdTriPair), hipMemcpyHostToDevice, s));
     rc = tri_launch_match(b, n_pairs, d_has_mp1, d_has_mp2, only_stereo != 0, check_orientation != 0, b->d_match, b->d_pairs, b->d_npairs, b->d_nmatch, s);
     if (rc != SD_OK) return rc;
     b->nPairs = n_pairs; b->dlPairs = n_pairs;
@@ -1664,117 +1774,73 @@ int sd_batch_create_new_map_points(sd_batch* b, int n_kf, const int32_t* kf_inde
 {
     if (!b || n_kf <= 0 || !cam_ok(cam) || !kf_index || !kf_Tcw_host || !neigh_offset)
         return set_err(SD_ERR_INVALID, "bad create_new_map_points arguments");
-    if (neigh_offset[0] != 0) return set_err(SD_ERR_INVALID, "create_new_map_points: neighbour offsets must start at 0 and ascend");
-    for (int k = 0; k < n_kf; k++) if (neigh_offset[k + 1] < neigh_offset[k]) return set_err(SD_ERR_INVALID, "create_new_map_points: neighbour offsets must start at 0 and ascend");
+    int rc = check_offsets("create_new_map_points", neigh_offset, n_kf, nullptr);
+    if (rc != SD_OK) return rc;
     const int nP = neigh_offset[n_kf];
     if (nP > 0 && (!neigh_index || !neigh_Tcw_host)) return set_err(SD_ERR_INVALID, "bad create_new_map_points arguments");
-    for (int k = 0; k < n_kf; k++) {
-        if (kf_index[k] < 0 || kf_index[k] >= b->maxImages) return set_err(SD_ERR_INVALID, "create_new_map_points: slot out of range");
-        if (!slot_ok(b, kf_index[k])) return set_err(SD_ERR_STATE, "create_new_map_points: slot holds no results");
-        if (!tri_bow_ok(b, kf_index[k])) return set_err(SD_ERR_STATE, "create_new_map_points: sd_batch_compute_bow has not run on these slots");
-    }
-    for (int p = 0; p < nP; p++) {
-        if (neigh_index[p] < 0 || neigh_index[p] >= b->maxImages) return set_err(SD_ERR_INVALID, "create_new_map_points: slot out of range");
-        if (!slot_ok(b, neigh_index[p])) return set_err(SD_ERR_STATE, "create_new_map_points: slot holds no results");
-        if (!tri_bow_ok(b, neigh_index[p])) return set_err(SD_ERR_STATE, "create_new_map_points: sd_batch_compute_bow has not run on these slots");
-    }
+    rc = check_slots(b, "create_new_map_points", kf_index, nullptr, n_kf, SD_SLOT_RANGE | SD_SLOT_RESULTS | SD_SLOT_BOW);
+    if (rc == SD_OK) rc = check_slots(b, "create_new_map_points", neigh_index, nullptr, nP, SD_SLOT_RANGE | SD_SLOT_RESULTS | SD_SLOT_BOW);
+    if (rc != SD_OK) return rc;
     if (b->plan.kpCap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
-    b->triKfs = 0;
+    hipStream_t s = pick_stream(b, stream_);
+    b->tri.kfs = 0;
     if (d_new) *d_new = nullptr;
     if (d_nnew) *d_nnew = nullptr;
     const size_t cap = b->plan.kpCap;
-    if (n_kf > b->triKfCap) {
-        SdDevBuf<int> off, nn; SdDevBuf<sd_new_map_point> nw;
-        HIPCHK(off.alloc(((size_t)n_kf + 1) * 4)); HIPCHK(nn.alloc((size_t)n_kf * 4)); HIPCHK(nw.alloc((size_t)n_kf * cap * sizeof(sd_new_map_point)));
-        b->d_triOff = std::move(off); b->d_triNnew = std::move(nn); b->d_triNew = std::move(nw); b->triKfCap = n_kf;
-    }
-    if (nP > b->triTableCap) {
-        SdDevBuf<int> m, pl, np; SdDevBuf<uint8_t> ok; SdDevBuf<float> xw;
-        HIPCHK(m.alloc((size_t)nP * cap * 4)); HIPCHK(pl.alloc((size_t)nP * cap * 8)); HIPCHK(np.alloc((size_t)nP * 4));
-        HIPCHK(ok.alloc((size_t)nP * cap)); HIPCHK(xw.alloc((size_t)nP * cap * 12));
-        b->d_triMatch = std::move(m); b->d_triPairList = std::move(pl); b->d_triNp = std::move(np);
-        b->d_triOk = std::move(ok); b->d_triXw = std::move(xw); b->triTableCap = nP;
-    }
-    HIPCHK(hipMemcpyAsync(b->d_triOff, neigh_offset, ((size_t)n_kf + 1) * 4, hipMemcpyHostToDevice, s));
+    rc = b->tri.growTables(b, s, n_kf, nP);
+    if (rc != SD_OK) return rc;
+    HIPCHK(hipMemcpyAsync(b->tri.d_off, neigh_offset, ((size_t)n_kf + 1) * 4, hipMemcpyHostToDevice, s));
     if (nP > 0) {
-        std::vector<SdTriPair>& P = b->hostTriPairs;
+        std::vector<SdTriPair>& P = b->tri.hostPairs;
         P.resize(nP);
         for (int k = 0; k < n_kf; k++)
             for (int p = neigh_offset[k]; p < neigh_offset[k + 1]; p++) {
                 P[p].img1 = kf_index[k]; P[p].img2 = neigh_index[p]; P[p].row1 = k; P[p].row2 = p;
                 tri_pair_setup(kf_Tcw_host + 16 * (size_t)k, neigh_Tcw_host + 16 * (size_t)p, *cam, neigh_median_depth ? neigh_median_depth + p : nullptr, true, P[p]);
             }
-        int rc = tri_ensure_pairs(b, nP);
+        rc = b->tri.growPairs(b, s, nP);
         if (rc != SD_OK) return rc;
-        HIPCHK(hipMemcpyAsync(b->d_triPairs, P.data(), (size_t)nP * sizeof(SdTriPair), hipMemcpyHostToDevice, s));
-        rc = tri_launch_match(b, nP, d_kf_has_mp, d_neigh_has_mp, 0, 0, b->d_triMatch, b->d_triPairList, b->d_triNp, nullptr, s);   // ORBmatcher(0.6, false), bOnlyStereo = false
+        HIPCHK(hipMemcpyAsync(b->tri.d_pairs, P.data(), (size_t)nP * sizeof(SdTriPair), hipMemcpyHostToDevice, s));
+        rc = tri_launch_match(b, nP, d_kf_has_mp, d_neigh_has_mp, 0, 0, b->tri.d_match, b->tri.d_pairList, b->tri.d_np, nullptr, s);   // ORBmatcher(0.6, false), bOnlyStereo = false
         if (rc != SD_OK) return rc;
         SdCamera c; memcpy(&c, cam, sizeof(c));
         const float ratioFactor = 1.5f * (float)b->ex->prm.scaleFactor;
-        HIPCHK(hipMemsetAsync(b->d_triOk, 0, (size_t)nP * cap, s));
+        HIPCHK(hipMemsetAsync(b->tri.d_ok, 0, (size_t)nP * cap, s));
         ProfScope ps(b, s, K_TRI_T);
         hipLaunchKernelGGL(k_tri_triangulate, dim3((unsigned)((cap + 255) / 256), nP), dim3(256), 0, s, KPUN(b), b->d_kp, b->d_uright, b->d_depth,
-                           b->d_triPairs, b->d_triPairList, b->d_triNp, level_tables(b), c, ratioFactor, (int)cap, b->d_triOk, b->d_triXw);
+                           b->tri.d_pairs, b->tri.d_pairList, b->tri.d_np, level_tables(b), c, ratioFactor, (int)cap, b->tri.d_ok, b->tri.d_xw);
         LAUNCH_CHECK("k_tri_triangulate");
     }
     {
         const size_t lds = cap + 16;
         ProfScope ps(b, s, K_TRI_R);
-        hipLaunchKernelGGL(k_tri_resolve, dim3(n_kf), dim3(256), lds, s, b->d_count, b->d_triPairs, b->d_triOff, b->d_triMatch, b->d_triOk, b->d_triXw, (int)cap,
-                           b->d_triNew.get(), b->d_triNnew);
+        hipLaunchKernelGGL(k_tri_resolve, dim3(n_kf), dim3(256), lds, s, b->d_count, b->tri.d_pairs, b->tri.d_off, b->tri.d_match, b->tri.d_ok, b->tri.d_xw, (int)cap,
+                           b->tri.d_new.get(), b->tri.d_nnew);
         LAUNCH_CHECK("k_tri_resolve");
     }
-    b->triKfs = n_kf;
-    if (d_new) *d_new = b->d_triNew;
-    if (d_nnew) *d_nnew = b->d_triNnew;
+    b->tri.kfs = n_kf;
+    if (d_new) *d_new = b->tri.d_new;
+    if (d_nnew) *d_nnew = b->tri.d_nnew;
     return SD_OK;
 }
 
 int sd_batch_download_new_map_points(sd_batch* b, int kf, sd_new_map_point* out, int cap, int* nnew)
 {
     if (!b || !nnew) return set_err(SD_ERR_INVALID, "bad download_new_map_points arguments");
-    if (kf < 0 || kf >= b->triKfs) return set_err(SD_ERR_INVALID, "download_new_map_points: no such keyframe in the last sd_batch_create_new_map_points");
+    if (kf < 0 || kf >= b->tri.kfs) return set_err(SD_ERR_INVALID, "download_new_map_points: no such keyframe in the last sd_batch_create_new_map_points");
     int rc = sd_batch_sync(b);
     if (rc != SD_OK) return rc;
     int n = 0;
-    HIPCHK(hipMemcpy(&n, b->d_triNnew + kf, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&n, b->tri.d_nnew + kf, 4, hipMemcpyDeviceToHost));
     *nnew = n;
     if (n > cap) return set_err(SD_ERR_CAPACITY, "new map point buffer too small");
-    if (out && n > 0) HIPCHK(hipMemcpy(out, b->d_triNew + (size_t)kf * b->plan.kpCap, (size_t)n * sizeof(sd_new_map_point), hipMemcpyDeviceToHost));
+    if (out && n > 0) HIPCHK(hipMemcpy(out, b->tri.d_new + (size_t)kf * b->plan.kpCap, (size_t)n * sizeof(sd_new_map_point), hipMemcpyDeviceToHost));
     return SD_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // LocalMapping::SearchInNeighbors: ORBmatcher::Fuse(pKF, vpMapPoints, th) and MapPoint::ComputeDistinctiveDescriptors (k_fuse.h)
 // ---------------------------------------------------------------------------------------------------------
-// Job tables and per-entry scratch of sd_batch_fuse: they grow with the largest call seen (old ones freed first), as ensure_local_map does
-static int ensure_fuse(sd_batch* b, int n_jobs, int total, bool firstInMemory, hipStream_t s)
-{
-    const size_t cap = b->plan.kpCap;
-    if (!b->d_fuseErr) { HIPCHK(b->d_fuseErr.alloc(4)); HIPCHK(hipMemset(b->d_fuseErr, 0, 4)); }
-    if (n_jobs > b->fuseJobCap || total > b->fuseEntryCap || (firstInMemory && n_jobs > b->fuseFirstCap)) HIPCHK(hipStreamSynchronize(s));
-    if (n_jobs > b->fuseJobCap) {
-        const int want = std::max(n_jobs, 2 * b->fuseJobCap);
-        b->fuseJobCap = 0; b->d_fuseJobs.reset(); b->d_fuseT.reset(); b->d_fuseN.reset();
-        HIPCHK(b->d_fuseJobs.alloc(((size_t)2 * want + 1) * 4)); HIPCHK(b->d_fuseT.alloc((size_t)want * 64)); HIPCHK(b->d_fuseN.alloc((size_t)want * 4));
-        b->fuseJobCap = want;
-    }
-    if (total > b->fuseEntryCap) {
-        const int want = std::max(total, 2 * b->fuseEntryCap);
-        b->fuseEntryCap = 0; b->d_fuseBest.reset(); b->d_fuseHits.reset();
-        HIPCHK(b->d_fuseBest.alloc((size_t)want * sizeof(int2))); HIPCHK(b->d_fuseHits.alloc((size_t)want * sizeof(SdFuseHit)));
-        b->fuseEntryCap = want;
-    }
-    if (firstInMemory && n_jobs > b->fuseFirstCap) {
-        b->fuseFirstCap = 0;
-        HIPCHK(b->d_fuseFirst.alloc((size_t)n_jobs * cap * 4));
-        b->fuseFirstCap = n_jobs;
-    }
-    return SD_OK;
-}
-
 // sim3 = the job's pose is a similarity Scw (ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)): decomposed here (sd_scw.h), searched
 // by k_loop_search<0>; the tail is the same k_fuse_resolve
 static int fuse_impl(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Tcw_host, const int32_t* cand_offset,
@@ -1788,66 +1854,58 @@ static int fuse_impl(sd_batch* b, int n_jobs, const int32_t* kf_index, const flo
     if (d_nfused) *d_nfused = nullptr;
     if (!b || n_jobs < 0 || n_jobs > 65535 || n_points < 0 || !cam_ok(cam) || !(th > 0) || (n_jobs > 0 && (!kf_index || !Tcw_host || !cand_offset)))
         return set_err(SD_ERR_INVALID, "bad fuse arguments");
-    b->fuseJobs = 0;
+    b->fuse.jobs = 0;
     if (n_jobs == 0) return SD_OK;
-    if (cand_offset[0] != 0) return set_err(SD_ERR_INVALID, "fuse: candidate offsets must start at 0 and ascend");
     int maxM = 0;
-    for (int j = 0; j < n_jobs; j++) {
-        const int M = cand_offset[j + 1] - cand_offset[j];
-        if (M < 0 || cand_offset[j] < 0) return set_err(SD_ERR_INVALID, "fuse: candidate offsets must start at 0 and ascend");
-        maxM = std::max(maxM, M);
-        if (kf_index[j] < 0 || kf_index[j] >= b->maxImages) return set_err(SD_ERR_INVALID, "fuse: slot out of range");
-    }
-    for (int j = 0; j < n_jobs; j++) {
-        if (!slot_ok(b, kf_index[j])) return set_err(SD_ERR_STATE, "fuse: slot holds no results");
-        if (!b->gridValid[kf_index[j]]) return set_err(SD_ERR_STATE, "fuse: sd_batch_assign_grid has not run on this slot");
-    }
+    int rc = check_offsets("fuse", cand_offset, n_jobs, &maxM);
+    if (rc == SD_OK) rc = check_slots(b, "fuse", kf_index, nullptr, n_jobs, SD_SLOT_RANGE);
+    if (rc == SD_OK) rc = check_slots(b, "fuse", kf_index, nullptr, n_jobs, SD_SLOT_RESULTS | SD_SLOT_GRID);
+    if (rc != SD_OK) return rc;
     const int total = cand_offset[n_jobs];
     if (total > 0 && (!d_cand_point || !d_points || !d_point_desc || n_points == 0)) return set_err(SD_ERR_INVALID, "fuse: entries but no map points given");
     const int cap = b->plan.kpCap;
     if (cap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     // the first-taker table of k_fuse_resolve: [cap] ints in LDS while that fits beside the scan, else one row per job in memory
     const size_t lds = (size_t)cap * 4 + 16;
     const bool firstInMemory = lds > SD_LDS_MAX_BYTES - 2048;
-    int rc = ensure_fuse(b, n_jobs, total, firstInMemory, s);
+    rc = b->fuse.grow(b, s, n_jobs, total, firstInMemory);
     if (rc != SD_OK) return rc;
-    int* dFrameOf = b->d_fuseJobs;
-    int* dOff = b->d_fuseJobs + n_jobs;
-    b->fuseOff.assign(cand_offset, cand_offset + n_jobs + 1);
+    int* dFrameOf = b->fuse.d_jobs;
+    int* dOff = b->fuse.d_jobs + n_jobs;
+    b->fuse.off.assign(cand_offset, cand_offset + n_jobs + 1);
     HIPCHK(hipMemcpyAsync(dFrameOf, kf_index, (size_t)n_jobs * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dOff, cand_offset, ((size_t)n_jobs + 1) * 4, hipMemcpyHostToDevice, s));
     if (sim3) {
-        b->loopT.resize((size_t)n_jobs * 16);
-        for (int j = 0; j < n_jobs; j++) sd_scw_decompose(Tcw_host + (size_t)j * 16, b->loopT.data() + (size_t)j * 16);
-        Tcw_host = b->loopT.data();
+        b->loop.T.resize((size_t)n_jobs * 16);
+        for (int j = 0; j < n_jobs; j++) sd_scw_decompose(Tcw_host + (size_t)j * 16, b->loop.T.data() + (size_t)j * 16);
+        Tcw_host = b->loop.T.data();
     }
-    HIPCHK(hipMemcpyAsync(b->d_fuseT, Tcw_host, (size_t)n_jobs * 64, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b->fuse.d_T, Tcw_host, (size_t)n_jobs * 64, hipMemcpyHostToDevice, s));
     if (maxM > 0 && sim3) {
         ProfScope ps(b, s, K_LOOP_F);
         hipLaunchKernelGGL(k_loop_search<0>, dim3((maxM + 3) / 4, n_jobs), dim3(256), 0, s, KPUN(b), b->d_desc, b->d_uright, b->d_sortedIdx, b->d_cellStart,
-                           b->d_count, (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->d_fuseT, (const int*)nullptr,
-                           b->d_fuseBest.get(), (unsigned*)nullptr, (int*)nullptr, b->d_fuseErr.get(), level_tables(b), to_cam(cam), th, cap);
+                           b->d_count, (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->fuse.d_T, (const int*)nullptr,
+                           b->fuse.d_best.get(), (unsigned*)nullptr, (int*)nullptr, b->fuse.d_err.get(), level_tables(b), to_cam(cam), th, cap);
         LAUNCH_CHECK("k_loop_search<0>");
     } else if (maxM > 0) {
         ProfScope ps(b, s, K_FUSE_S);
         hipLaunchKernelGGL(k_fuse_search, dim3((maxM + 3) / 4, n_jobs), dim3(256), 0, s, KPUN(b), b->d_desc, b->d_uright, b->d_sortedIdx, b->d_cellStart,
-                           (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->d_fuseT, b->d_fuseBest.get(),
-                           b->d_fuseErr.get(), level_tables(b), to_cam(cam), th, cap);
+                           (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->fuse.d_T, b->fuse.d_best.get(),
+                           b->fuse.d_err.get(), level_tables(b), to_cam(cam), th, cap);
         LAUNCH_CHECK("k_fuse_search");
     }
     {
         if (!firstInMemory && lds > 64 * 1024) HIPCHK(sd_raise_lds_limit((const void*)k_fuse_resolve, (int)lds));
         ProfScope ps(b, s, K_FUSE_R);
-        hipLaunchKernelGGL(k_fuse_resolve, dim3(n_jobs), dim3(256), firstInMemory ? 0 : lds, s, b->d_count, dFrameOf, dOff, b->d_fuseBest.get(), d_kf_state, cap,
-                           firstInMemory ? b->d_fuseFirst.get() : nullptr, b->d_fuseHits.get(), b->d_fuseN.get());
+        hipLaunchKernelGGL(k_fuse_resolve, dim3(n_jobs), dim3(256), firstInMemory ? 0 : lds, s, b->d_count, dFrameOf, dOff, b->fuse.d_best.get(), d_kf_state, cap,
+                           firstInMemory ? b->fuse.d_first.get() : nullptr, b->fuse.d_hits.get(), b->fuse.d_n.get());
         LAUNCH_CHECK("k_fuse_resolve");
     }
-    b->fuseJobs = n_jobs;
-    if (d_best) *d_best = (int32_t*)b->d_fuseBest.get();
-    if (d_hits) *d_hits = (sd_fuse_hit*)b->d_fuseHits.get();
-    if (d_nfused) *d_nfused = b->d_fuseN;
+    b->fuse.jobs = n_jobs;
+    if (d_best) *d_best = (int32_t*)b->fuse.d_best.get();
+    if (d_hits) *d_hits = (sd_fuse_hit*)b->fuse.d_hits.get();
+    if (d_nfused) *d_nfused = b->fuse.d_n;
     return SD_OK;
 }
 
@@ -1880,21 +1938,14 @@ int sd_batch_search_by_bow_kf(sd_batch* b, int n_pairs, const int32_t* kf1_index
     if (!b || n_pairs < 0 || n_pairs > b->maxImages || (n_pairs > 0 && (!kf1_index || !kf2_index)))
         return set_err(SD_ERR_INVALID, "bad search_by_bow_kf arguments");
     std::vector<int2> idx(n_pairs);
-    for (int p = 0; p < n_pairs; p++) {
-        if (kf1_index[p] < 0 || kf1_index[p] >= b->maxImages || kf2_index[p] < 0 || kf2_index[p] >= b->maxImages)
-            return set_err(SD_ERR_INVALID, "search_by_bow_kf: slot out of range");
-        idx[p] = make_int2(kf1_index[p], kf2_index[p]);
-    }
-    for (int p = 0; p < n_pairs; p++) {
-        if (!slot_ok(b, kf1_index[p]) || !slot_ok(b, kf2_index[p])) return set_err(SD_ERR_STATE, "search_by_bow_kf: slot holds no results");
-        if (!b->d_bowWordF || !b->bowValid[kf1_index[p]] || !b->bowValid[kf2_index[p]])
-            return set_err(SD_ERR_STATE, "search_by_bow_kf: sd_batch_compute_bow has not run on these slots");
-    }
+    int rc = check_slots(b, "search_by_bow_kf", kf1_index, kf2_index, n_pairs, SD_SLOT_RANGE);
+    if (rc == SD_OK) rc = check_slots(b, "search_by_bow_kf", kf1_index, kf2_index, n_pairs, SD_SLOT_RESULTS | SD_SLOT_BOW);
+    if (rc != SD_OK) return rc;
+    for (int p = 0; p < n_pairs; p++) idx[p] = make_int2(kf1_index[p], kf2_index[p]);
     const int cap = b->plan.kpCap;
     const size_t lds = (size_t)cap * 4 + 2 * (size_t)cap + 16;
     if (lds > SD_LDS_MAX_BYTES - 1024) return set_err(SD_ERR_UNSUPPORTED, "search_by_bow_kf: the key-point capacity exceeds the LDS tables");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     b->nPairs = 0; b->dlPairs = 0;
     if (n_pairs == 0) return SD_OK;
     HIPCHK(hipMemcpyAsync(b->d_pairIdx, idx.data(), (size_t)n_pairs * sizeof(int2), hipMemcpyHostToDevice, s));
@@ -1910,28 +1961,6 @@ int sd_batch_search_by_bow_kf(sd_batch* b, int n_pairs, const int32_t* kf1_index
     return SD_OK;
 }
 
-// Job tables and scratch of sd_batch_search_by_projection_sim3: they grow with the largest call seen (old ones freed first), as ensure_fuse does
-static int ensure_loop(sd_batch* b, int n_jobs, int total, hipStream_t s)
-{
-    const size_t cap = b->plan.kpCap;
-    if (!b->d_loopErr) { HIPCHK(b->d_loopErr.alloc(4)); HIPCHK(hipMemset(b->d_loopErr, 0, 4)); }
-    if (n_jobs > b->loopJobCap || total > b->loopEntryCap) HIPCHK(hipStreamSynchronize(s));
-    if (n_jobs > b->loopJobCap) {
-        const int want = std::max(n_jobs, 2 * b->loopJobCap);
-        b->loopJobCap = 0; b->d_loopJobs.reset(); b->d_loopT.reset(); b->d_loopNm.reset(); b->d_loopAssigned.reset();
-        HIPCHK(b->d_loopJobs.alloc(((size_t)2 * want + 1) * 4)); HIPCHK(b->d_loopT.alloc((size_t)want * 64)); HIPCHK(b->d_loopNm.alloc((size_t)want * 4));
-        HIPCHK(b->d_loopAssigned.alloc((size_t)want * cap * 4));
-        b->loopJobCap = want;
-    }
-    if (total > b->loopEntryCap) {
-        const int want = std::max(total, 2 * b->loopEntryCap);
-        b->loopEntryCap = 0; b->d_loopList.reset(); b->d_loopListN.reset(); b->d_loopBest.reset();
-        HIPCHK(b->d_loopList.alloc((size_t)want * SD_PROJ_K * 4)); HIPCHK(b->d_loopListN.alloc((size_t)want * 4)); HIPCHK(b->d_loopBest.alloc((size_t)want * sizeof(int2)));
-        b->loopEntryCap = want;
-    }
-    return SD_OK;
-}
-
 // ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoints, vector<MapPoint*>& vpMatched, int th)
 // (src/ORBmatcher.cc:290-403)
 int sd_batch_search_by_projection_sim3(sd_batch* b, int n_jobs, const int32_t* kf_index, const float* Scw_host, const int32_t* cand_offset,
@@ -1944,97 +1973,89 @@ int sd_batch_search_by_projection_sim3(sd_batch* b, int n_jobs, const int32_t* k
     if (d_nmatches) *d_nmatches = nullptr;
     if (!b || n_jobs < 0 || n_jobs > 65535 || n_points < 0 || !cam_ok(cam) || th <= 0 || (n_jobs > 0 && (!kf_index || !Scw_host || !cand_offset || !d_matched)))
         return set_err(SD_ERR_INVALID, "bad search_by_projection_sim3 arguments");
-    b->loopJobs = 0;
+    b->loop.jobs = 0;
     if (n_jobs == 0) return SD_OK;
-    if (cand_offset[0] != 0) return set_err(SD_ERR_INVALID, "search_by_projection_sim3: candidate offsets must start at 0 and ascend");
     int maxM = 0;
-    for (int j = 0; j < n_jobs; j++) {
-        const int M = cand_offset[j + 1] - cand_offset[j];
-        if (M < 0 || cand_offset[j] < 0) return set_err(SD_ERR_INVALID, "search_by_projection_sim3: candidate offsets must start at 0 and ascend");
-        maxM = std::max(maxM, M);
-        if (kf_index[j] < 0 || kf_index[j] >= b->maxImages) return set_err(SD_ERR_INVALID, "search_by_projection_sim3: slot out of range");
-    }
-    for (int j = 0; j < n_jobs; j++) {
-        if (!slot_ok(b, kf_index[j])) return set_err(SD_ERR_STATE, "search_by_projection_sim3: slot holds no results");
-        if (!b->gridValid[kf_index[j]]) return set_err(SD_ERR_STATE, "search_by_projection_sim3: sd_batch_assign_grid has not run on this slot");
-    }
+    int rc = check_offsets("search_by_projection_sim3", cand_offset, n_jobs, &maxM);
+    if (rc == SD_OK) rc = check_slots(b, "search_by_projection_sim3", kf_index, nullptr, n_jobs, SD_SLOT_RANGE);
+    if (rc == SD_OK) rc = check_slots(b, "search_by_projection_sim3", kf_index, nullptr, n_jobs, SD_SLOT_RESULTS | SD_SLOT_GRID);
+    if (rc != SD_OK) return rc;
     const int total = cand_offset[n_jobs];
     if (total > 0 && (!d_cand_point || !d_points || !d_point_desc || n_points == 0))
         return set_err(SD_ERR_INVALID, "search_by_projection_sim3: entries but no map points given");
     const int cap = b->plan.kpCap;
     if (cap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
-    int rc = ensure_loop(b, n_jobs, total, s);
+    hipStream_t s = pick_stream(b, stream_);
+    rc = b->loop.grow(b, s, n_jobs, total);
     if (rc != SD_OK) return rc;
-    int* dFrameOf = b->d_loopJobs;
-    int* dOff = b->d_loopJobs + n_jobs;
-    b->loopOff.assign(cand_offset, cand_offset + n_jobs + 1);
-    b->loopT.resize((size_t)n_jobs * 16);
-    for (int j = 0; j < n_jobs; j++) sd_scw_decompose(Scw_host + (size_t)j * 16, b->loopT.data() + (size_t)j * 16);
-    HIPCHK(hipMemsetAsync(b->d_loopErr, 0, 4, s));               // the flag belongs to this call: every job's download reports it
+    int* dFrameOf = b->loop.d_jobs;
+    int* dOff = b->loop.d_jobs + n_jobs;
+    b->loop.off.assign(cand_offset, cand_offset + n_jobs + 1);
+    b->loop.T.resize((size_t)n_jobs * 16);
+    for (int j = 0; j < n_jobs; j++) sd_scw_decompose(Scw_host + (size_t)j * 16, b->loop.T.data() + (size_t)j * 16);
+    HIPCHK(hipMemsetAsync(b->loop.d_err, 0, 4, s));               // the flag belongs to this call: every job's download reports it
     HIPCHK(hipMemcpyAsync(dFrameOf, kf_index, (size_t)n_jobs * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dOff, cand_offset, ((size_t)n_jobs + 1) * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(b->d_loopT, b->loopT.data(), (size_t)n_jobs * 64, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b->loop.d_T, b->loop.T.data(), (size_t)n_jobs * 64, hipMemcpyHostToDevice, s));
     if (maxM > 0) {
         ProfScope ps(b, s, K_LOOP_P);
         hipLaunchKernelGGL(k_loop_search<1>, dim3((maxM + 3) / 4, n_jobs), dim3(256), 0, s, KPUN(b), b->d_desc, b->d_uright, b->d_sortedIdx, b->d_cellStart,
-                           b->d_count, (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->d_loopT, d_matched,
-                           (int2*)nullptr, b->d_loopList.get(), b->d_loopListN.get(), b->d_loopErr.get(), level_tables(b), to_cam(cam), (float)th, cap);
+                           b->d_count, (const SdMapPoint*)d_points, d_point_desc, n_points, dFrameOf, dOff, d_cand_point, b->loop.d_T, d_matched,
+                           (int2*)nullptr, b->loop.d_list.get(), b->loop.d_listN.get(), b->loop.d_err.get(), level_tables(b), to_cam(cam), (float)th, cap);
         LAUNCH_CHECK("k_loop_search<1>");
     }
     {
         ProfScope ps(b, s, K_LOOP_A);
-        hipLaunchKernelGGL(k_loop_assign, dim3(n_jobs), dim3(64), (size_t)((cap + 31) / 32) * 4 + 16, s, dOff, b->d_loopList.get(), b->d_loopListN.get(), cap,
-                           b->d_loopAssigned.get(), b->d_loopBest.get(), b->d_loopNm.get(), b->d_err.get());
+        hipLaunchKernelGGL(k_loop_assign, dim3(n_jobs), dim3(64), (size_t)((cap + 31) / 32) * 4 + 16, s, dOff, b->loop.d_list.get(), b->loop.d_listN.get(), cap,
+                           b->loop.d_assigned.get(), b->loop.d_best.get(), b->loop.d_nm.get(), b->d_err.get());
         LAUNCH_CHECK("k_loop_assign");
     }
-    b->loopJobs = n_jobs;
-    if (d_assigned) *d_assigned = b->d_loopAssigned;
-    if (d_best) *d_best = (int32_t*)b->d_loopBest.get();
-    if (d_nmatches) *d_nmatches = b->d_loopNm;
+    b->loop.jobs = n_jobs;
+    if (d_assigned) *d_assigned = b->loop.d_assigned;
+    if (d_best) *d_best = (int32_t*)b->loop.d_best.get();
+    if (d_nmatches) *d_nmatches = b->loop.d_nm;
     return SD_OK;
 }
 
 int sd_batch_download_projection_sim3(sd_batch* b, int job, int32_t* assigned, int cap, int32_t* best, int cap_entries, int* n_entries, int* nmatches)
 {
     if (!b || !n_entries || !nmatches || cap_entries < 0) return set_err(SD_ERR_INVALID, "bad download_projection_sim3 arguments");
-    if (job < 0 || job >= b->loopJobs) return set_err(SD_ERR_INVALID, "download_projection_sim3: no such job in the last sd_batch_search_by_projection_sim3");
+    if (job < 0 || job >= b->loop.jobs) return set_err(SD_ERR_INVALID, "download_projection_sim3: no such job in the last sd_batch_search_by_projection_sim3");
     int rc = sd_batch_sync(b);
     if (rc != SD_OK) return rc;
     int err = 0;
-    HIPCHK(hipMemcpy(&err, b->d_loopErr, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&err, b->loop.d_err, 4, hipMemcpyDeviceToHost));
     if (err) return set_err(SD_ERR_INVALID, "search_by_projection_sim3: a candidate or a matched entry names a point outside its table");
-    const int e0 = b->loopOff[job], n = b->loopOff[job + 1] - e0;
+    const int e0 = b->loop.off[job], n = b->loop.off[job + 1] - e0;
     *n_entries = n;
-    HIPCHK(hipMemcpy(nmatches, b->d_loopNm + job, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(nmatches, b->loop.d_nm + job, 4, hipMemcpyDeviceToHost));
     if (best && n > cap_entries) return set_err(SD_ERR_CAPACITY, "projection_sim3 result buffers too small");
     if (assigned && cap < b->plan.kpCap) return set_err(SD_ERR_CAPACITY, "the assigned row needs kp_capacity entries");
-    if (assigned) HIPCHK(hipMemcpy(assigned, b->d_loopAssigned + (size_t)job * b->plan.kpCap, (size_t)b->plan.kpCap * 4, hipMemcpyDeviceToHost));
-    if (best && n > 0) HIPCHK(hipMemcpy(best, b->d_loopBest + e0, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+    if (assigned) HIPCHK(hipMemcpy(assigned, b->loop.d_assigned + (size_t)job * b->plan.kpCap, (size_t)b->plan.kpCap * 4, hipMemcpyDeviceToHost));
+    if (best && n > 0) HIPCHK(hipMemcpy(best, b->loop.d_best + e0, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
     return SD_OK;
 }
 
 int sd_batch_download_fuse(sd_batch* b, int job, int32_t* best, sd_fuse_hit* hits, int cap_entries, int* n_entries, int* nfused)
 {
     if (!b || !n_entries || !nfused || cap_entries < 0) return set_err(SD_ERR_INVALID, "bad download_fuse arguments");
-    if (job < 0 || job >= b->fuseJobs) return set_err(SD_ERR_INVALID, "download_fuse: no such job in the last sd_batch_fuse");
+    if (job < 0 || job >= b->fuse.jobs) return set_err(SD_ERR_INVALID, "download_fuse: no such job in the last sd_batch_fuse");
     int rc = sd_batch_sync(b);
     if (rc != SD_OK) return rc;
     int err = 0;
-    HIPCHK(hipMemcpy(&err, b->d_fuseErr, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&err, b->fuse.d_err, 4, hipMemcpyDeviceToHost));
     if (err) {
-        HIPCHK(hipMemset(b->d_fuseErr, 0, 4));
+        HIPCHK(hipMemset(b->fuse.d_err, 0, 4));
         return set_err(SD_ERR_INVALID, "fuse: an entry names a point outside [-1, n_points)");
     }
-    const int e0 = b->fuseOff[job], n = b->fuseOff[job + 1] - e0;
+    const int e0 = b->fuse.off[job], n = b->fuse.off[job + 1] - e0;
     *n_entries = n;
     int nf = 0;
-    HIPCHK(hipMemcpy(&nf, b->d_fuseN + job, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&nf, b->fuse.d_n + job, 4, hipMemcpyDeviceToHost));
     *nfused = nf;
     if (n > cap_entries) return set_err(SD_ERR_CAPACITY, "fuse result buffers too small");
-    if (best && n > 0) HIPCHK(hipMemcpy(best, b->d_fuseBest + e0, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
-    if (hits && nf > 0) HIPCHK(hipMemcpy(hits, b->d_fuseHits + e0, (size_t)nf * sizeof(SdFuseHit), hipMemcpyDeviceToHost));
+    if (best && n > 0) HIPCHK(hipMemcpy(best, b->fuse.d_best + e0, (size_t)n * sizeof(int2), hipMemcpyDeviceToHost));
+    if (hits && nf > 0) HIPCHK(hipMemcpy(hits, b->fuse.d_hits + e0, (size_t)nf * sizeof(SdFuseHit), hipMemcpyDeviceToHost));
     return SD_OK;
 }
 
@@ -2073,8 +2094,7 @@ static int estimate_motion_impl(sd_batch* b, int n_pairs, void* stream_, const i
     if (!b) return set_err(SD_ERR_INVALID, "null batch");
     b->nMotion = 0;
     if (n_pairs <= 0) return set_err(SD_ERR_STATE, "estimate_motion: no preceding sd_batch_search_by_projection");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     const size_t cap = b->plan.kpCap;
     int rc = ensure_motion(b);
     if (rc != SD_OK) return rc;
@@ -2145,8 +2165,7 @@ int sd_batch_undistort_keypoints(sd_batch* b, int n_images, const float* K4, con
 {
     if (!b || n_images < 0 || n_images > b->nExtracted || !K4 || !dist5 || !d_keys_un) return set_err(SD_ERR_INVALID, "bad undistort_keypoints arguments");
     if (n_images == 0) return SD_OK;
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     const int cap = b->plan.kpCap;
     hipLaunchKernelGGL(k_undistort_keypoints, dim3((cap + 255) / 256, n_images), dim3(256), 0, s, b->d_kp, b->d_count, cap, to_distortion(K4, dist5),
                        dist5[0] == 0.0f ? 1 : 0, d_keys_un);                      // mDistCoef.at<float>(0) == 0.0 -> mvKeysUn = mvKeys
@@ -2175,8 +2194,7 @@ int sd_batch_set_distortion(sd_batch* b, const float* K4, const float* dist5)
 int sd_batch_undistort(sd_batch* b, int n_slots, const int32_t* slots, void* stream_)
 {
     if (!b || n_slots < 0 || n_slots > b->maxImages || (n_slots > 0 && !slots)) return set_err(SD_ERR_INVALID, "bad undistort arguments");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (!b->hasDist || n_slots == 0) return SD_OK;
     for (int i = 0; i < n_slots; i++) if (slots[i] < 0 || slots[i] >= b->maxImages) return set_err(SD_ERR_INVALID, "bad undistort slot");
     HIPCHK(hipMemcpyAsync(b->d_unSlots, slots, (size_t)n_slots * 4, hipMemcpyHostToDevice, s));
@@ -2261,16 +2279,14 @@ static int copy_frames_impl(sd_batch* b, int n, const int2* d_pairs, int src0, i
 int sd_batch_copy_frame(sd_batch* b, int src, int dst, void* stream_)
 {
     if (!b || !slot_ok(b, src) || dst < 0 || dst >= b->maxImages || src == dst) return set_err(SD_ERR_INVALID, "bad copy_frame slots");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     return copy_frames_impl(b, 1, nullptr, src, dst, &src, &dst, s);
 }
 
 int sd_batch_copy_frames(sd_batch* b, int n, const int32_t* src, const int32_t* dst, void* stream_)
 {
     if (!b || n < 0 || n > b->maxImages || (n > 0 && (!src || !dst))) return set_err(SD_ERR_INVALID, "bad copy_frames arguments");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (n == 0) return SD_OK;
     std::vector<int2>& pr = b->hostCopyPairs;
     pr.resize(n);
@@ -2712,22 +2728,6 @@ int sd_sim3_ransac_host(int n_problems, const int32_t* corr_offset, const sd_sim
 }
 
 // ---------------------------------------------------------------- ORBmatcher::SearchBySim3 (k_sim3.h)
-// `prev`: the stream of the batch's previous call, which may still be reading the rows that growth frees
-static int ensure_sim3(sd_batch* b, int n_pairs, hipStream_t s, hipStream_t prev)
-{
-    if (!b->d_s3Err) HIPCHK(b->d_s3Err.alloc(4));
-    if (n_pairs <= b->s3PairCap) return SD_OK;
-    if (prev != s) HIPCHK(hipStreamSynchronize(prev));
-    HIPCHK(hipStreamSynchronize(s));
-    const size_t want = (size_t)std::max(n_pairs, 2 * b->s3PairCap), rows = want * b->plan.kpCap;
-    b->s3PairCap = 0;
-    b->d_s3Pairs.reset(); b->d_s3Match1.reset(); b->d_s3Match2.reset(); b->d_s3Match12.reset(); b->d_s3Found.reset(); b->d_s3Already.reset();
-    HIPCHK(b->d_s3Pairs.alloc(want * sizeof(SdSim3Pair))); HIPCHK(b->d_s3Match1.alloc(rows * 4)); HIPCHK(b->d_s3Match2.alloc(rows * 4));
-    HIPCHK(b->d_s3Match12.alloc(rows * 4)); HIPCHK(b->d_s3Found.alloc(want * 4)); HIPCHK(b->d_s3Already.alloc(rows));
-    b->s3PairCap = (int)want;
-    return SD_OK;
-}
-
 static int sim3_search_launch(sd_batch* b, int n_pairs, const sd_camera* cam, float th, const sd_map_point* d_points, const uint8_t* d_point_desc,
                               int n_points, const int32_t* d_kf1_point, const int32_t* d_kf2_point, const int32_t* d_matched12, hipStream_t s);
 
@@ -2740,29 +2740,22 @@ int sd_batch_search_by_sim3(sd_batch* b, int n_pairs, const int32_t* kf1_index, 
     if (!b || n_pairs < 0 || n_pairs > 32767 || n_points < 0 || !cam_ok(cam) || !(th > 0) ||
         (n_pairs > 0 && (!kf1_index || !kf2_index || !Tcw1_host || !Tcw2_host || !s12 || !R12 || !t12 || !d_kf1_point || !d_kf2_point || !d_matched12)))
         return set_err(SD_ERR_INVALID, "bad search_by_sim3 arguments");
-    b->s3Pairs = 0;
+    b->sim3.pairs = 0;
     if (n_pairs == 0) return SD_OK;
     if (n_points > 0 && (!d_points || !d_point_desc)) return set_err(SD_ERR_INVALID, "search_by_sim3: n_points but no point table");
-    for (int p = 0; p < n_pairs; p++)
-        if (kf1_index[p] < 0 || kf1_index[p] >= b->maxImages || kf2_index[p] < 0 || kf2_index[p] >= b->maxImages)
-            return set_err(SD_ERR_INVALID, "search_by_sim3: slot out of range");
-    for (int p = 0; p < n_pairs; p++) {
-        if (!slot_ok(b, kf1_index[p]) || !slot_ok(b, kf2_index[p])) return set_err(SD_ERR_STATE, "search_by_sim3: slot holds no results");
-        if (!b->gridValid[kf1_index[p]] || !b->gridValid[kf2_index[p]])
-            return set_err(SD_ERR_STATE, "search_by_sim3: sd_batch_assign_grid has not run on both slots");
-    }
+    int rc = check_slots(b, "search_by_sim3", kf1_index, kf2_index, n_pairs, SD_SLOT_RANGE);
+    if (rc == SD_OK) rc = check_slots(b, "search_by_sim3", kf1_index, kf2_index, n_pairs, SD_SLOT_RESULTS | SD_SLOT_GRID);
+    if (rc != SD_OK) return rc;
     const int cap = b->plan.kpCap;
     if (cap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
-    const hipStream_t prev = b->lastStream;
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : prev;
-    b->lastStream = s;
-    int rc = ensure_sim3(b, n_pairs, s, prev);
+    hipStream_t s = pick_stream(b, stream_);
+    rc = b->sim3.grow(b, s, n_pairs);
     if (rc != SD_OK) return rc;
-    HIPCHK(hipMemsetAsync(b->d_s3Err, 0, 4, s));               // the flag belongs to this call: every pair's download reports it
+    HIPCHK(hipMemsetAsync(b->sim3.d_err, 0, 4, s));               // the flag belongs to this call: every pair's download reports it
     // the transformation between the cameras (ORBmatcher.cc:1276-1278), as DESIGN Q39 freezes it
-    b->s3Host.resize(n_pairs);
+    b->sim3.host.resize(n_pairs);
     for (int p = 0; p < n_pairs; p++) {
-        SdSim3Pair& P = b->s3Host[p];
+        SdSim3Pair& P = b->sim3.host[p];
         memcpy(P.T1, Tcw1_host + (size_t)p * 16, 64); memcpy(P.T2, Tcw2_host + (size_t)p * 16, 64);
         const float sc = s12[p];
         const float* R = R12 + (size_t)p * 9;
@@ -2778,27 +2771,27 @@ int sd_batch_search_by_sim3(sd_batch* b, int n_pairs, const int32_t* kf1_index, 
         P.T12[15] = 1.f; P.T21[15] = 1.f;
         P.slot1 = kf1_index[p]; P.slot2 = kf2_index[p]; P.pad[0] = P.pad[1] = 0;
     }
-    HIPCHK(hipMemcpyAsync(b->d_s3Pairs, b->s3Host.data(), (size_t)n_pairs * sizeof(SdSim3Pair), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b->sim3.d_pairs, b->sim3.host.data(), (size_t)n_pairs * sizeof(SdSim3Pair), hipMemcpyHostToDevice, s));
     rc = sim3_search_launch(b, n_pairs, cam, th, d_points, d_point_desc, n_points, d_kf1_point, d_kf2_point, d_matched12, s);
     if (rc != SD_OK) return rc;
-    b->s3Pairs = n_pairs;
+    b->sim3.pairs = n_pairs;
     return SD_OK;
 }
 
-// the three kernels of SearchBySim3 over the pair table b->d_s3Pairs (filled by the caller, on the host or on the device)
+// the three kernels of SearchBySim3 over the pair table b->sim3.d_pairs (filled by the caller, on the host or on the device)
 static int sim3_search_launch(sd_batch* b, int n_pairs, const sd_camera* cam, float th, const sd_map_point* d_points, const uint8_t* d_point_desc,
                               int n_points, const int32_t* d_kf1_point, const int32_t* d_kf2_point, const int32_t* d_matched12, hipStream_t s)
 {
     const int cap = b->plan.kpCap;
     const size_t rows = (size_t)n_pairs * cap;
-    HIPCHK(hipMemsetAsync(b->d_s3Already, 0, rows, s));
-    HIPCHK(hipMemsetAsync(b->d_s3Match1, 0xFF, rows * 4, s)); HIPCHK(hipMemsetAsync(b->d_s3Match2, 0xFF, rows * 4, s));
-    HIPCHK(hipMemsetAsync(b->d_s3Match12, 0xFF, rows * 4, s));
+    HIPCHK(hipMemsetAsync(b->sim3.d_already, 0, rows, s));
+    HIPCHK(hipMemsetAsync(b->sim3.d_match1, 0xFF, rows * 4, s)); HIPCHK(hipMemsetAsync(b->sim3.d_match2, 0xFF, rows * 4, s));
+    HIPCHK(hipMemsetAsync(b->sim3.d_match12, 0xFF, rows * 4, s));
     SdSim3SearchArgs A;
     A.kp = KPUN(b); A.desc = b->d_desc; A.uRight = b->d_uright; A.sortedIdx = b->d_sortedIdx; A.cellStart = b->d_cellStart; A.count = b->d_count;
-    A.pairs = b->d_s3Pairs; A.mps = (const SdMapPoint*)d_points; A.mpDesc = d_point_desc; A.nPoints = n_points;
-    A.kfPoint[0] = d_kf1_point; A.kfPoint[1] = d_kf2_point; A.matched12 = d_matched12; A.already2 = b->d_s3Already;
-    A.vnMatch[0] = b->d_s3Match1; A.vnMatch[1] = b->d_s3Match2; A.match12 = b->d_s3Match12; A.nFound = b->d_s3Found; A.errFlag = b->d_s3Err; A.cap = cap;
+    A.pairs = b->sim3.d_pairs; A.mps = (const SdMapPoint*)d_points; A.mpDesc = d_point_desc; A.nPoints = n_points;
+    A.kfPoint[0] = d_kf1_point; A.kfPoint[1] = d_kf2_point; A.matched12 = d_matched12; A.already2 = b->sim3.d_already;
+    A.vnMatch[0] = b->sim3.d_match1; A.vnMatch[1] = b->sim3.d_match2; A.match12 = b->sim3.d_match12; A.nFound = b->sim3.d_found; A.errFlag = b->sim3.d_err; A.cap = cap;
     {
         ProfScope ps(b, s, K_SIM3_M);
         hipLaunchKernelGGL(k_sim3_mark, dim3((cap + 255) / 256, n_pairs), dim3(256), 0, s, A);
@@ -2820,18 +2813,18 @@ static int sim3_search_launch(sd_batch* b, int n_pairs, const sd_camera* cam, fl
 int sd_batch_download_sim3_matches(sd_batch* b, int pair, int32_t* match12, int32_t* vnMatch1, int32_t* vnMatch2, int cap, int* n_found)
 {
     if (!b || !n_found) return set_err(SD_ERR_INVALID, "bad download_sim3_matches arguments");
-    if (pair < 0 || pair >= b->s3Pairs) return set_err(SD_ERR_INVALID, "download_sim3_matches: no such pair in the last sd_batch_search_by_sim3");
+    if (pair < 0 || pair >= b->sim3.pairs) return set_err(SD_ERR_INVALID, "download_sim3_matches: no such pair in the last sd_batch_search_by_sim3");
     int rc = sd_batch_sync(b);
     if (rc != SD_OK) return rc;
     int err = 0;
-    HIPCHK(hipMemcpy(&err, b->d_s3Err, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&err, b->sim3.d_err, 4, hipMemcpyDeviceToHost));
     if (err) return set_err(SD_ERR_INVALID, "search_by_sim3: a feature names a point outside [-1, n_points)");
     if (cap < b->plan.kpCap) return set_err(SD_ERR_CAPACITY, "sim3 match buffers need kp_capacity entries");
     const size_t row = (size_t)pair * b->plan.kpCap, bytes = (size_t)b->plan.kpCap * 4;
-    if (match12) HIPCHK(hipMemcpy(match12, b->d_s3Match12 + row, bytes, hipMemcpyDeviceToHost));
-    if (vnMatch1) HIPCHK(hipMemcpy(vnMatch1, b->d_s3Match1 + row, bytes, hipMemcpyDeviceToHost));
-    if (vnMatch2) HIPCHK(hipMemcpy(vnMatch2, b->d_s3Match2 + row, bytes, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(n_found, b->d_s3Found + pair, 4, hipMemcpyDeviceToHost));
+    if (match12) HIPCHK(hipMemcpy(match12, b->sim3.d_match12 + row, bytes, hipMemcpyDeviceToHost));
+    if (vnMatch1) HIPCHK(hipMemcpy(vnMatch1, b->sim3.d_match1 + row, bytes, hipMemcpyDeviceToHost));
+    if (vnMatch2) HIPCHK(hipMemcpy(vnMatch2, b->sim3.d_match2 + row, bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(n_found, b->sim3.d_found + pair, 4, hipMemcpyDeviceToHost));
     return SD_OK;
 }
 
@@ -3020,13 +3013,13 @@ int sd_batch_first_separate(sd_batch* b, int n_frames, const int32_t* slots, con
     if (!b || n_frames < 0 || n_frames > b->maxImages || (n_frames > 0 && (!slots || !boxes || !n_boxes || !box_idx)))
         return set_err(SD_ERR_INVALID, "bad first_separate arguments");
     if (!b->cullOk) return set_err(SD_ERR_UNSUPPORTED, "more key points per image than the dynamic-object kernels' LDS tables hold (about 6,800)");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (n_frames == 0) return SD_OK;
     std::vector<SdFrameBoxes>& h = b->hostBoxes;
     h.resize(n_frames);
     for (int f = 0; f < n_frames; f++) {
-        if (!slot_ok(b, slots[f])) return set_err(SD_ERR_STATE, "first_separate: slot holds no results");
+        int rc = check_slots(b, "first_separate", slots + f, nullptr, 1, SD_SLOT_RESULTS);
+        if (rc != SD_OK) return rc;
         if (n_boxes[f] < 0 || n_boxes[f] > SD_MAXB) return set_err(SD_ERR_CAPACITY, "more than SD_MAX_BOXES boxes in a frame");
         memset(&h[f], 0, sizeof(SdFrameBoxes));
         h[f].nb = n_boxes[f];
@@ -3121,14 +3114,14 @@ static int separate_impl(sd_batch* b, int n_pairs, const int32_t* cur_index, con
     if (!b->cullOk) return set_err(SD_ERR_UNSUPPORTED, "more key points per image than the dynamic-object kernels' LDS tables hold (about 6,800)");
     const bool fromMotion = n_pairs > 0 && !HorF;          // HorF == flag == NULL: pair p uses the model fit of pair p
     if (fromMotion && b->nMotion < n_pairs) return set_err(SD_ERR_STATE, "separate: no sd_batch_estimate_motion results for these pairs");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     b->nSepPairs = 0;
     if (n_pairs == 0) return SD_OK;
     std::vector<int2>& idx = b->hostPairs;
     idx.resize(n_pairs);
     for (int p = 0; p < n_pairs; p++) {
-        if (!slot_ok(b, cur_index[p]) || !slot_ok(b, ref_index[p])) return set_err(SD_ERR_STATE, "separate: slot holds no results");
+        int rc = check_slots(b, "separate", cur_index + p, ref_index + p, 1, SD_SLOT_RESULTS);
+        if (rc != SD_OK) return rc;
         if (!fromMotion && flag[p] != 1 && flag[p] != 2) return set_err(SD_ERR_INVALID, "separate: flag must be 1 (H) or 2 (F)");
         if (last_slot ? !slot_ok(b, last_slot[p]) : (n_last[p] < 0 || n_last[p] > SD_MAXB)) return set_err(SD_ERR_INVALID, "separate: bad n_last / last slot");
         idx[p] = make_int2(cur_index[p], ref_index[p]);
@@ -3184,8 +3177,7 @@ int sd_batch_update_frame(sd_batch* b, int only_if_static, void* stream_)
 {
     if (!b) return SD_ERR_INVALID;
     if (b->nSepPairs <= 0) return set_err(SD_ERR_STATE, "update_frame needs a preceding separate");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     SdSepArgs G;
     G.pairIdx = b->d_sepPairs; G.HorF = b->d_HorF; G.flag = b->d_sepFlag; G.lastIdx = b->d_lastIdx; G.lastStatus = b->d_lastStatus;
     G.nLast = b->d_nLast; G.dynStart = b->d_dynStart; G.dynStatus = b->d_dynStatus; G.matches = b->d_sepMatches; G.ret = b->d_sepRet;
@@ -3283,20 +3275,6 @@ int sd_batch_reset_kernel_times(sd_batch* b)
     return SD_OK;
 }
 
-// The scratch of sd_batch_backproject_dense: `need` 64-bit words of point marks, grown as needed (the old group is freed first)
-static int ensure_cloud(sd_batch* b, size_t need, int rows3, hipStream_t s)
-{
-    if (b->cloudCap >= need) return SD_OK;
-    HIPCHK(hipStreamSynchronize(s));
-    b->cloudCap = 0; b->d_cloudBits.reset(); b->d_cloudRows.reset(); b->d_cloudT.reset(); b->d_cloudSlots.reset();
-    SdDevBuf<unsigned long long> bits; SdDevBuf<int> rows, slots; SdDevBuf<double> T;
-    HIPCHK(bits.alloc(need * 8)); HIPCHK(rows.alloc((size_t)b->maxImages * rows3 * 2 * 4));
-    HIPCHK(T.alloc((size_t)b->maxImages * 16 * 8)); HIPCHK(slots.alloc((size_t)b->maxImages * 4));
-    b->d_cloudBits = std::move(bits); b->d_cloudRows = std::move(rows); b->d_cloudT = std::move(T); b->d_cloudSlots = std::move(slots);
-    b->cloudCap = need;
-    return SD_OK;
-}
-
 // PointCloudMapping::generatePointCloud (src/pointcloudmapping.cc:59-103) for frame slots of the batch
 int sd_batch_backproject_dense(sd_batch* b, int n_frames, const int32_t* slots, const uint8_t* d_color, size_t color_stride,
                                size_t color_pitch, const uint16_t* d_depth, size_t depth_stride_elems, size_t depth_pitch_elems,
@@ -3310,20 +3288,18 @@ int sd_batch_backproject_dense(sd_batch* b, int n_frames, const int32_t* slots, 
     if (cap_points < cols3 * rows3) return set_err(SD_ERR_CAPACITY, "cap_points must be at least ceil(W/3) * ceil(H/3)");
     if (words > 64) return set_err(SD_ERR_UNSUPPORTED, "image wider than 12288 pixels");
     if (color_stride < (size_t)3 * W || depth_stride_elems < (size_t)W || (d_mask && mask_stride < (size_t)W)) return set_err(SD_ERR_INVALID, "stride smaller than width");
-    hipStream_t s = stream_ ? (hipStream_t)stream_ : b->lastStream;
-    b->lastStream = s;
+    hipStream_t s = pick_stream(b, stream_);
     if (n_frames == 0) return SD_OK;
-    for (int f = 0; f < n_frames; f++) if (!slot_ok(b, slots[f])) return set_err(SD_ERR_STATE, "backproject_dense: slot holds no frame");
-    const size_t need = (size_t)b->maxImages * rows3 * words;
-    int rc = ensure_cloud(b, need, rows3, s);
+    int rc = check_slots(b, "backproject_dense", slots, nullptr, n_frames, SD_SLOT_RESULTS);
+    if (rc == SD_OK) rc = b->cloud.grow(b, s, (size_t)b->maxImages * rows3 * words, rows3);
     if (rc != SD_OK) return rc;
-    HIPCHK(hipMemcpyAsync(b->d_cloudT, Twc_host, (size_t)n_frames * 128, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(b->d_cloudSlots, slots, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b->cloud.d_T, Twc_host, (size_t)n_frames * 128, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b->cloud.d_slots, slots, (size_t)n_frames * 4, hipMemcpyHostToDevice, s));
     SdCloudArgs A;
-    A.fb = b->d_fb; A.slots = b->d_cloudSlots; A.color = d_color; A.colorStride = color_stride; A.colorPitch = color_pitch;
+    A.fb = b->d_fb; A.slots = b->cloud.d_slots; A.color = d_color; A.colorStride = color_stride; A.colorPitch = color_pitch;
     A.depth = d_depth; A.depthStride = depth_stride_elems; A.depthPitch = depth_pitch_elems; A.depthFactor = depth_factor;
     A.mask = d_mask; A.maskStride = mask_stride; A.maskPitch = mask_pitch; A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy;
-    A.Twc = b->d_cloudT; A.W = W; A.H = H; A.cols3 = cols3; A.rows3 = rows3; A.words = words; A.bits = b->d_cloudBits; A.rowCount = b->d_cloudRows;
+    A.Twc = b->cloud.d_T; A.W = W; A.H = H; A.cols3 = cols3; A.rows3 = rows3; A.words = words; A.bits = b->cloud.d_bits; A.rowCount = b->cloud.d_rows;
     A.points = (sd_cloud_point_dev*)d_points; A.capPoints = cap_points; A.counts = d_counts;
     hipLaunchKernelGGL(k_cloud_mark, dim3(rows3, n_frames), dim3(256), 0, s, A);
     LAUNCH_CHECK("k_cloud_mark");

@@ -13,21 +13,27 @@ int sd_set_err(int code, const std::string& msg);        // defined in sd_api.hi
 hipError_t sd_raise_lds_limit(const void* kernel, int bytes);
 #define SD_LDS_MAX_BYTES (160 * 1024)      // LDS of one gfx950 workgroup: above it a per-key-point table goes to device memory
 
-// Device memory owned by one object: hipFree on destruction, move-only, read as a plain T* wherever a pointer is expected.
-template <typename T>
-class SdDevBuf {
+// Device memory owned by one object: hipFree on destruction, move-only.  The untyped owner, so that buffers of different element types can
+// be listed together (sd_grow in sd_api.hip).
+class SdDevMem {
 public:
-    SdDevBuf() = default;
-    SdDevBuf(SdDevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }        // declaring the moves deletes the copies
-    SdDevBuf& operator=(SdDevBuf&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
-    ~SdDevBuf() { reset(); }
+    SdDevMem() = default;
+    SdDevMem(SdDevMem&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }        // declaring the moves deletes the copies
+    SdDevMem& operator=(SdDevMem&& o) noexcept { if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; } return *this; }
+    ~SdDevMem() { reset(); }
     // frees what the buffer held, then allocates `bytes`; on failure the buffer stays empty
-    hipError_t alloc(size_t bytes) { reset(); void* p = nullptr; hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) p_ = (T*)p; return e; }
+    hipError_t alloc(size_t bytes) { reset(); void* p = nullptr; hipError_t e = hipMalloc(&p, bytes); if (e == hipSuccess) p_ = p; return e; }
     void reset() { if (p_) (void)hipFree(p_); p_ = nullptr; }
-    T* get() const { return p_; }
-    operator T*() const { return p_; }
-private:
-    T* p_ = nullptr;
+protected:
+    void* p_ = nullptr;
+};
+
+// SdDevMem read as a plain T* wherever a pointer is expected.
+template <typename T>
+class SdDevBuf : public SdDevMem {
+public:
+    T* get() const { return (T*)p_; }
+    operator T*() const { return (T*)p_; }
 };
 
 #define HIPCHK(call)                                                                                      \

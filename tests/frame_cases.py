@@ -583,9 +583,10 @@ class Workspace:
         torch.cuda.synchronize()
 
 
-def run_cloud(ws, call, cap_points=None, fill=SENTINEL):
+def run_cloud(ws, call, cap_points=None, fill=SENTINEL, stream=None):
     """One sd_batch_backproject_dense on the call's three frames: colour, depth and mask with padded strides and pitches (depth and
-    mask strides differ; the padding holds depths that would be kept and mask values that would mask).
+    mask strides differ; the padding holds depths that would be kept and mask values that would mask).  stream: a HIP stream handle to
+    launch on (the inputs are complete before the call).
     -> (counts (n, 2) i32, points (n, cap_points) CLOUD_POINT_DTYPE, frames, the SdError of a refused call or None)"""
     import torch
     g = ws.g
@@ -604,10 +605,11 @@ def run_cloud(ws, call, cap_points=None, fill=SENTINEL):
     d_pts = torch.full((n, cap_points, CLOUD_POINT_DTYPE.itemsize), fill, dtype=torch.uint8, device="cuda")
     d_cnt = torch.full((n, 2), -7, dtype=torch.int32, device="cuda")
     err = None
+    torch.cuda.synchronize()
     try:
         ws.b.backproject_dense(call["slots"], d_color.data_ptr(), cs, cp, d_depth.data_ptr(), ds, dp, call["factor"],
                                d_mask.data_ptr() if call["use_mask"] else 0, ms, mp, cloud_camera(g), np.stack([f["Twc"] for f in frames]),
-                               d_pts.data_ptr(), cap_points, d_cnt.data_ptr())
+                               d_pts.data_ptr(), cap_points, d_cnt.data_ptr(), stream=stream)
     except ws.fe.SdError as e:
         err = e
     torch.cuda.synchronize()

@@ -77,6 +77,25 @@ def test_dense_cloud(wsof, CO, gname):
     assert filled
 
 
+def test_dense_cloud_on_a_fresh_workspace_and_two_streams(gpu, fe, CO):
+    """Two calls on a fresh 752 x 240 workspace, each on a stream of its own: the first allocates the marks, both equal the oracle."""
+    import torch
+    ws = fc.Workspace(fe, sc.GEOMS[fc.CLOUD_GEOMS[0]])
+    try:
+        g, cam = ws.g, fc.cloud_camera(ws.g)
+        assert (g.W, g.H) == (752, 240)
+        streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+        for call, st in zip(fc.cloud_calls(g)[:2], streams):
+            cnt, pts, frames, err = fc.run_cloud(ws, call, stream=st.cuda_stream)
+            assert err is None, "%s: %s" % (call["name"], err)
+            for f, fr in enumerate(frames):
+                ref, masked = fc.oracle_cloud(CO, fr, call["factor"], call["use_mask"], cam)
+                assert (int(cnt[f, 0]), int(cnt[f, 1])) == (len(ref), masked) and pts[f, :len(ref)].tobytes() == ref.tobytes(), "%s frame %d" % (call["name"], f)
+                assert (fc.bits(pts[f, len(ref):]) == fc.SENTINEL).all()
+    finally:
+        ws.close()
+
+
 def test_dense_cloud_limits(wsof, fe):
     """n_frames = 0 does nothing; cap_points one below ceil(W / 3) * ceil(H / 3) is refused and nothing is written."""
     import torch

@@ -136,6 +136,21 @@ def test_job_sizes(ws):
     check_project(ws, sc, upload=False)
 
 
+def test_projection_tables_grow_with_a_larger_second_call(gpu, fe, synth):
+    """A fresh workspace: one job of one candidate, then 4 jobs of 120 candidates each (the job and the entry tables both grow), then the
+    first call again."""
+    w = lc.Workspace(fe, 4, tc.vocabulary(synth, 5))
+    try:
+        small = lc.with_scale(fc.contention_scene(1), 1.0)
+        small["th_proj"] = 3
+        big = lc.random_scw_scene(1)
+        assert len(big["jobs"]) == 4 and sum(len(j[1]) for j in big["jobs"]) == 480
+        for sc in (small, big, small):
+            check_project(w, sc)
+    finally:
+        w.close()
+
+
 def test_all_candidates_contend_for_one_feature(ws):
     sc = lc.with_scale(fc.contention_scene(40), 2.0)
     (best, hits, nf), = check_fuse(ws, sc)

@@ -133,6 +133,22 @@ def test_random_scenes(ws, orc, seed):
     assert sum(w["nm"] for w in wants) > 50
 
 
+def test_local_map_scratch_grows_with_a_larger_second_call(gpu, fe, synth, orc):
+    """A fresh workspace: one frame with one point, then two frames with a few hundred points, then the first call again."""
+    w = fc.Workspace(fe, 2, tc.vocabulary(synth, 5))
+    try:
+        B = pc.LocalB("lm_growth_one")
+        B.simple("only")
+        small = dict(name="lm_growth_small", th=3.0, nnratio=0.8, cos_limit=0.5, frames=[B.build()])
+        big = pc.random_lm_scene(1, n_frames=2)
+        assert sum(len(F["points"]) for F in big["frames"]) > 200
+        assert check_lm(w, orc, small)[0]["nm"] == 1
+        check_lm(w, orc, big)
+        assert check_lm(w, orc, small)[0]["nm"] == 1
+    finally:
+        w.close()
+
+
 def test_frame_frame_result_is_independent_of_slot_and_neighbours(ws, orc, ff_scenes):
     """The same pair as pair 0 of 1, and as pair 3 of 5 on other slots with an empty pair before it: the same bytes."""
     order = {P["name"]: P for P in ff_scenes["ff_order"]["pairs"]}

@@ -51,6 +51,17 @@ def test_refine_removes_a_match_the_search_added(ws):
     assert total > 10
 
 
+def test_refine_tables_grow_with_a_larger_second_call(gpu, fe, synth):
+    """A fresh workspace: one job, then three (the search's tables and the refine tables grow in one call), then the first call again."""
+    w = fc.Workspace(fe, 6, tc.vocabulary(synth, 5))
+    try:
+        small, big = rc.refine_scene(31, 120, 1), rc.refine_scene(32, 120, 3)
+        for scene in (small, big, small):
+            check_scene(w, scene)
+    finally:
+        w.close()
+
+
 def test_refine_job_independence_and_refusals(ws, fe):
     scene = rc.refine_scene(5, 200, 4, not_found=(2,))
     got, _ = check_scene(ws, scene)
