@@ -337,6 +337,60 @@ int sd_sim3_ransac_device(int n_problems, const int32_t* corr_offset, const sd_s
 /* The same from host arrays: uploads, runs, synchronises. */
 int sd_sim3_ransac_host(int n_problems, const int32_t* corr_offset, const sd_sim3_corr* corr, const sd_sim3_problem* problems,
                         double probability, int min_inliers, int max_iterations, sd_sim3_result* results, uint8_t* inliers);
+/* ---- PnPsolver (include/PnPsolver.h, src/PnPsolver.cc), as Tracking::Relocalization drives it (src/Tracking.cc:2256-2309) ----
+ * Up to SD_PNP_MAX_PROBLEMS independent PnPsolver problems in one launch sequence: the 4-point EPnP RANSAC with Refine of one (lost frame,
+ * candidate key frame) pair each (DESIGN Q46).  A problem is what the constructor gathers (PnPsolver.cc:67-110): one record per kept
+ * correspondence, in key-point order -- xw = mvP3Dw, uv = mvP2D (mvKeysUn[i].pt), sigma2 = mvLevelSigma2[octave], tag = i (carried,
+ * never read) -- plus fx fy cx cy, a 64-bit seed, start_iteration = mnIterations on entry (0 for a first call) and n_iterations = the
+ * argument of iterate (the reference passes 5).  The sampler is Q39's: draw d of iteration it is sd_splitmix64(sd_splitmix64(seed) +
+ * 4 it + d) modulo the current size of vAvailableIndices, mapped through the swap-with-back removal of :188-201. */
+typedef struct sd_pnp_corr {
+    float xw[3];
+    float uv[2];
+    float sigma2;
+    int32_t tag;
+} sd_pnp_corr;                                    /* 28 bytes */
+typedef struct sd_pnp_problem {
+    float fx, fy, cx, cy;                         /* F.fx .. F.cy (:104-107) */
+    uint64_t seed;
+    int32_t start_iteration, n_iterations;
+} sd_pnp_problem;                                 /* 32 bytes */
+/* What iterate(n_iterations) leaves (PnPsolver.cc:165-258).  The loop condition `mnIterations < mRansacMaxIts || nCurrentIterations <
+ * nIterations` makes a call run iterations start + 1 .. end, end = max(max_its, start_iteration + n_iterations): a first call is find().
+ *   kind 1  Refine() succeeded (:226-236): Tcw = mRefinedTcw, n_inliers = mnRefinedInliers, the mask is mvbRefinedInliers, iteration =
+ *           mnIterations at the return (the lowest it in (start, end] with count >= min_inliers whose best passes Refine), no_more = 0
+ *   kind 2  nothing refined but a best exists (:241-255): Tcw = mBestTcw, n_inliers = mnBestInliers, the best mask, no_more = 1
+ *   kind 0  empty pose (N < min_inliers, :173-177, or no hypothesis reached min_inliers): no_more = 1, Tcw and the mask zero
+ * best_iteration / best_inliers: the iteration that set mnBestInliers (the EARLIEST of equal counts, :212 is strict; 0 = none) and its
+ * count; n_refines: Refine() evaluations of this call (one per distinct best).  min_inliers / max_its: mRansacMinInliers / mRansacMaxIts
+ * after SetRansacParameters (:121-157).  Tcw row-major 4x4, R and t narrowed to f32 once. */
+typedef struct sd_pnp_result {
+    int32_t kind, no_more, iteration, n_inliers, best_iteration, best_inliers, n_refines, min_inliers, max_its, reserved;
+    float Tcw[16];
+} sd_pnp_result;                                  /* 104 bytes */
+#define SD_PNP_MAX_CORRESPONDENCES 4096           /* per problem */
+#define SD_PNP_MAX_ITERATIONS 4096                /* max_iterations, and start_iteration + n_iterations */
+#define SD_PNP_MAX_PROBLEMS 65535                 /* per call */
+/* Problem p owns correspondences [corr_offset[p], corr_offset[p+1]) of d_corr; corr_offset [n_problems + 1] and problems [n_problems]
+ * are HOST arrays, d_ arrays device memory.  probability .. th2: SetRansacParameters' six arguments (the reference passes 0.99, 10, 300,
+ * 4, 0.5, 5.991), evaluated on the host as written (:121-157).  Out: d_results [n_problems]; d_inliers [correspondences] u8, indexed like
+ * d_corr: entry e is vbInliers[d_corr[e].tag] of the returned kind.  d_counts (nullable, device, [n_problems * counts_stride] int32):
+ * a debug copy of the inlier counts, row p holding mnInliersi of iterations 1 .. end in [0, end) (end = 0 for a problem that runs none);
+ * counts_stride must then be >= every end.  d_poses (nullable, device, [n_problems * counts_stride * 12] f64): the hypotheses themselves,
+ * mRi row-major then mti, laid out like d_counts.
+ * min_set != 4, more than SD_PNP_MAX_PROBLEMS problems, more than SD_PNP_MAX_CORRESPONDENCES in a problem, max_iterations or
+ * start_iteration + n_iterations outside [1, SD_PNP_MAX_ITERATIONS], start_iteration < 0, n_iterations < 1, min_inliers < 0, probability
+ * outside (0, 1), epsilon outside (0, 1], th2 <= 0, offsets that do not start at 0 or decrease: SD_ERR_INVALID before anything is
+ * launched, never a truncation.  Stateless with respect to sd_batch.  Asynchronous on `stream` with no host synchronisation, except that
+ * the problem table goes through a ring of 8 library-owned device tables per device and the library-owned workspace (grown with the
+ * largest call seen) is shared by the calls on one device, as for sd_sim3_ransac_device. */
+int sd_pnp_ransac_device(int n_problems, const int32_t* corr_offset, const sd_pnp_corr* d_corr, const sd_pnp_problem* problems,
+                         double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2,
+                         sd_pnp_result* d_results, uint8_t* d_inliers, int32_t* d_counts, double* d_poses, int counts_stride, void* stream);
+/* The same from host arrays: uploads, runs, synchronises.  counts / poses (nullable, host) as d_counts / d_poses. */
+int sd_pnp_ransac_host(int n_problems, const int32_t* corr_offset, const sd_pnp_corr* corr, const sd_pnp_problem* problems,
+                       double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2,
+                       sd_pnp_result* results, uint8_t* inliers, int32_t* counts, double* poses, int counts_stride);
 /* ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241), as LoopClosing::ComputeSim3 calls it after SearchBySim3 (:326) ----
  * Up to SD_SIM3_MAX_PROBLEMS independent problems in one launch: one free Sim3 vertex, two projection edges per correspondence
  * (x1 = S12 X2 and x2 = S12^-1 X1), Huber with delta = (float)sqrt(th2), g2o's Levenberg-Marquardt with NUMERIC Jacobians (delta =
@@ -677,6 +731,28 @@ int sd_batch_relocalize_refine(sd_batch* b, int n_jobs, const int32_t* frame_ind
  * and mvbOutlier (written only where a key point had an edge, as the reference does: a key point whose outlier was set to NULL keeps its
  * flag).  Each pointer is nullable; the rows need cap >= kp_capacity entries. */
 int sd_batch_download_reloc(sd_batch* b, int job, sd_reloc_result* result, int32_t* frame_point, uint8_t* outlier, int cap);
+/* ---- Tracking::Relocalization, lines 2256-2358, for any number of (frame slot, keyframe slot) jobs as ONE launch sequence with no host round
+ * trip (DESIGN Q46): the PnPsolver constructor's gather, iterate(n_iterations), lines 2300-2309 and the cascade of sd_batch_relocalize_refine.
+ * d_bow_match [n_jobs][cap] i32 (device): row j = vvpMapPointMatches of the job per FRAME key point, a point index or -1 (what
+ * sd_batch_search_by_bow leaves).  The gather keeps, in key-point order, every match whose point has its good flag set (bit 0 of
+ * sd_map_point.flags, the flag the reloc matcher reads; PnPsolver.cc:83-85): xw from d_points, uv = mvKeysUn[i].pt and sigma2 =
+ * mvLevelSigma2[octave] from the frame slot, tag = i.  problems [n_jobs] (host): fx fy cx cy, seed, start_iteration, n_iterations per job;
+ * probability .. th2 as for sd_pnp_ransac_device.  N is a device value here, so SetRansacParameters is evaluated on the host for EVERY N in
+ * [0, cap] (as written, :121-157) into a table the device reads, and the stage is launched against the caps.  The PnP record of a job is what
+ * sd_pnp_ransac_device gives for the gathered problem.  Then mvpMapPoints[i] = the match where vbInliers[i], else -1 (:2300-2309), and the
+ * cascade runs from the DEVICE pose; a job of kind 0 has an all -1 row, so no step of the cascade does anything for it (nGood = 0).  Its
+ * results are those sd_batch_relocalize_refine gives when fed that pose and row.  kp_capacity above SD_PNP_MAX_CORRESPONDENCES:
+ * SD_ERR_UNSUPPORTED; otherwise the refusals of the two calls it joins.  Still with the caller: the `nmatches < 15` discard (:2260-2264; a job
+ * with fewer matches is simply not submitted), vbDiscarded (from no_more), the `break` over candidates and mnLastRelocFrameId. */
+int sd_batch_relocalize_pnp(sd_batch* b, int n_jobs, const int32_t* frame_index, const int32_t* kf_index, const sd_pnp_problem* problems,
+                            double probability, int min_inliers, int max_iterations, int min_set, float epsilon, float th2,
+                            const int32_t* d_bow_match, const int32_t* d_kf_point, const sd_map_point* d_points, const uint8_t* d_point_desc,
+                            int n_points, const sd_camera* cam, sd_reloc_result** d_results, void* stream);
+/* Job `job` of the last sd_batch_relocalize_pnp (every pointer nullable): the PnP record; the gathered problem (n_corr rows of corr, their
+ * inlier bytes); the row handed to the cascade; and what sd_batch_download_reloc reports.  corr / inliers / row / frame_point / outlier hold
+ * kp_capacity entries (cap >= that). */
+int sd_batch_download_reloc_pnp(sd_batch* b, int job, sd_pnp_result* pnp, int32_t* n_corr, sd_pnp_corr* corr, uint8_t* inliers, int32_t* row,
+                                sd_reloc_result* result, int32_t* frame_point, uint8_t* outlier, int cap);
 /* What optimisation `stage` (0 .. 2) of the job saw and decided: its edges in order, mvbOutlier per edge, the pose it started from.
  * n_edges = 0 for a stage that did not run. */
 int sd_batch_download_reloc_optimisation(sd_batch* b, int job, int stage, sd_pose_edge* edges, uint8_t* edge_outlier, int cap_edges,

@@ -27,6 +27,7 @@
 #include "k_sim3.h"
 #include "k_sim3_opt.h"
 #include "k_sim3_refine.h"
+#include "k_pnp.h"
 #include "k_loop.h"
 #include "k_reloc.h"
 #include "k_kfdb.h"
@@ -273,6 +274,21 @@ struct sd_batch {
                             {&d_th, 2 * 4}, {&d_orb, 2 * 4}, {&d_cam, sizeof(sd_camera)}, {&d_res, sizeof(sd_reloc_result)}});
         }
     } relocRefine;
+    // sd_batch_relocalize_pnp: per job the gathered problem [jobs][cap], its mask, record, problem row and caller's record, the row and pose
+    // handed to the cascade, and the SetRansacParameters table per N [cap + 1]
+    struct RelocPnp {
+        SdDevBuf<sd_pnp_corr> d_corr; SdDevBuf<uint8_t> d_inl; SdDevBuf<sd_pnp_result> d_res; SdDevBuf<SdPnpProb> d_prob; SdDevBuf<sd_pnp_problem> d_in;
+        SdDevBuf<int> d_row; SdDevBuf<float> d_T; SdDevBuf<int2> d_table; std::vector<int2> table; size_t cap = 0, tableCap = 0; int jobs = 0;
+        int grow(const sd_batch* b, hipStream_t s, size_t nJobs)
+        {
+            const size_t row = b->plan.kpCap;
+            int rc = sd_grow(b->prevStream, s, tableCap, &jobs, row + 1, row + 1, {{&d_table, sizeof(int2)}});
+            if (rc != SD_OK) return rc;
+            return sd_grow(b->prevStream, s, cap, &jobs, nJobs, SD_RELOC_MAX_JOBS,
+                           {{&d_corr, row * sizeof(sd_pnp_corr)}, {&d_inl, row}, {&d_res, sizeof(sd_pnp_result)}, {&d_prob, sizeof(SdPnpProb)},
+                            {&d_in, sizeof(sd_pnp_problem)}, {&d_row, row * 4}, {&d_T, 64}});
+        }
+    } relocPnp;
     std::vector<sd_camera> pairCam, hPoseCam; std::vector<int32_t> hPoseMap;
     int nPairs = 0;
     int dlPairs = 0;          // pairs sd_batch_download_matches may read (the tracker also keeps pairs at [n_lanes, 2 * n_lanes))
@@ -3314,5 +3330,6 @@ int sd_batch_backproject_dense(sd_batch* b, int n_frames, const int32_t* slots, 
 #include "sd_reloc.inc"
 #include "sd_sim3_opt.inc"
 #include "sd_sim3_refine.inc"
+#include "sd_pnp.inc"
 
 } // extern "C"

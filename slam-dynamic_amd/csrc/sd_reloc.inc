@@ -85,6 +85,12 @@ int sd_batch_download_reloc_matches(sd_batch* b, int job, int32_t* frame_point, 
 // ---------------------------------------------------------------------------------------------------------
 static_assert(sizeof(sd_reloc_result) == 284, "sd_reloc_result is 7 ints and 4 poses");
 
+// The body of the cascade on stream s for checked arguments.  The poses come from the host (Tcw_host) or, when that is null, from device
+// memory (d_Tcw, [n_jobs][16], read on s): sd_batch_relocalize_pnp's hand-over.
+static int reloc_refine_run(sd_batch* b, int n_jobs, const int32_t* frame_index, const int32_t* kf_index, const float* Tcw_host, const float* d_Tcw,
+                            const int32_t* d_kf_point, const int32_t* d_frame_point, const sd_map_point* d_points, const uint8_t* d_point_desc,
+                            int n_points, const sd_camera* cam, sd_reloc_result** d_results, hipStream_t s);
+
 int sd_batch_relocalize_refine(sd_batch* b, int n_jobs, const int32_t* frame_index, const int32_t* kf_index, const float* Tcw_host,
                                const int32_t* d_kf_point, const int32_t* d_frame_point, const sd_map_point* d_points, const uint8_t* d_point_desc,
                                int n_points, const sd_camera* cam, sd_reloc_result** d_results, void* stream_)
@@ -101,7 +107,16 @@ int sd_batch_relocalize_refine(sd_batch* b, int n_jobs, const int32_t* frame_ind
     if (n_points > 0 && (!d_points || !d_point_desc)) return set_err(SD_ERR_INVALID, "relocalize_refine: n_points but no map points given");
     const int cap = b->plan.kpCap;
     if (cap > 65535) return set_err(SD_ERR_UNSUPPORTED, "more than 65535 keypoints per image");
-    hipStream_t s = pick_stream(b, stream_);
+    return reloc_refine_run(b, n_jobs, frame_index, kf_index, Tcw_host, nullptr, d_kf_point, d_frame_point, d_points, d_point_desc, n_points, cam, d_results,
+                            pick_stream(b, stream_));
+}
+
+static int reloc_refine_run(sd_batch* b, int n_jobs, const int32_t* frame_index, const int32_t* kf_index, const float* Tcw_host, const float* d_Tcw,
+                            const int32_t* d_kf_point, const int32_t* d_frame_point, const sd_map_point* d_points, const uint8_t* d_point_desc,
+                            int n_points, const sd_camera* cam, sd_reloc_result** d_results, hipStream_t s)
+{
+    int rc = SD_OK;
+    const int cap = b->plan.kpCap;
     const size_t markBytes = std::max<size_t>((size_t)n_jobs * (size_t)n_points, 16);
     rc = b->reloc.grow(b, s, n_jobs);                             // the slot table and the kept keys are the matcher's
     if (rc == SD_OK) rc = b->relocRefine.grow(b, s, n_jobs, markBytes);
@@ -119,7 +134,8 @@ int sd_batch_relocalize_refine(sd_batch* b, int n_jobs, const int32_t* frame_ind
     const SdMapPoint* mps = (const SdMapPoint*)d_points;
     HIPCHK(hipMemsetAsync(b->reloc.d_err, 0, 4, s));
     HIPCHK(hipMemcpyAsync(b->reloc.d_slots, b->reloc.slots.data(), J * sizeof(int2), hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(T[0], Tcw_host, J * 64, hipMemcpyHostToDevice, s));
+    if (Tcw_host) HIPCHK(hipMemcpyAsync(T[0], Tcw_host, J * 64, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(T[0], d_Tcw, J * 64, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(b->relocRefine.d_th, b->relocRefine.th.data(), 2 * J * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(b->relocRefine.d_orb, b->relocRefine.orb.data(), 2 * J * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(b->relocRefine.d_cam, b->relocRefine.cam.data(), J * sizeof(sd_camera), hipMemcpyHostToDevice, s));

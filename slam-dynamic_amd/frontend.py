@@ -142,6 +142,8 @@ def lib():
         L.sd_local_ba_profile.argtypes = [i, vp]
         L.sd_sim3_ransac_device.argtypes = [i, vp, vp, vp, C.c_double, i, i, vp, vp, vp, vp]
         L.sd_sim3_ransac_host.argtypes = [i, vp, vp, vp, C.c_double, i, i, vp, vp]
+        L.sd_pnp_ransac_device.argtypes = [i, vp, vp, vp, C.c_double, i, i, i, C.c_float, C.c_float, vp, vp, vp, vp, i, vp]
+        L.sd_pnp_ransac_host.argtypes = [i, vp, vp, vp, C.c_double, i, i, i, C.c_float, C.c_float, vp, vp, vp, vp, i]
         L.sd_sim3_optimize_device.argtypes = [i, vp, vp, vp, vp, vp, vp]
         L.sd_batch_compute_sim3_refine.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_float, i, vp, vp, i, vp, vp, vp]
         L.sd_batch_download_sim3_refine.argtypes = [vp, i, vp, vp, i]
@@ -164,6 +166,8 @@ def lib():
         L.sd_batch_download_reloc_matches.argtypes = [vp, i, vp, vp, vp, vp, i, C.POINTER(i)]
         L.sd_batch_relocalize_refine.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, i, vp, C.POINTER(vp), vp]
         L.sd_batch_download_reloc.argtypes = [vp, i, vp, vp, vp, i]
+        L.sd_batch_relocalize_pnp.argtypes = [vp, i, vp, vp, vp, C.c_double, i, i, i, C.c_float, C.c_float, vp, vp, vp, vp, i, vp, C.POINTER(vp), vp]
+        L.sd_batch_download_reloc_pnp.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i]
         L.sd_batch_download_reloc_optimisation.argtypes = [vp, i, i, vp, vp, i, C.POINTER(i), vp]
         L.sd_batch_download_reloc_search.argtypes = [vp, i, i, vp, vp, vp, vp, vp, i, C.POINTER(i)]
         L.sd_batch_search_by_sim3.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, f, vp, vp, i, vp, vp, vp, vp]
@@ -640,6 +644,31 @@ class Batch:
                                                C.c_void_p(d_points or 0), C.c_void_p(d_point_desc or 0), int(n_points), _p(c), C.byref(d_res),
                                                C.c_void_p(stream or 0)))
         return d_res.value
+
+    def relocalize_pnp(self, frame_index, kf_index, problems, d_bow_match, d_kf_point, d_points, d_point_desc, cam, stream=None, *, n_points,
+                       probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991):
+        """Job j = lines 2256-2358 of Tracking::Relocalization for frame slot frame_index[j] and candidate keyframe slot kf_index[j] as one
+        launch sequence: the PnPsolver gather from row j of d_bow_match ([n_jobs][cap] i32 device: point index or -1 per frame key point),
+        iterate(problems[j].n_iterations) (problems: PNP_PROBLEM_DTYPE), lines 2300-2309 and the cascade from the device pose.  -> device
+        pointer of the sd_reloc_result records; everything through download_reloc_pnp."""
+        c = camera_array(cam)
+        fi = np.ascontiguousarray(frame_index, np.int32).reshape(-1); ki = np.ascontiguousarray(kf_index, np.int32).reshape(-1)
+        pr = np.ascontiguousarray(problems, PNP_PROBLEM_DTYPE).reshape(-1)
+        if len(ki) != len(fi) or len(pr) != len(fi):
+            raise ValueError("relocalize_pnp: one frame slot, one keyframe slot and one problem record per job")
+        d_res = C.c_void_p()
+        check(lib().sd_batch_relocalize_pnp(self.h, len(fi), _p(fi), _p(ki), _p(pr), probability, min_inliers, max_iterations, min_set, epsilon, th2,
+                                            C.c_void_p(d_bow_match or 0), C.c_void_p(d_kf_point or 0), C.c_void_p(d_points or 0),
+                                            C.c_void_p(d_point_desc or 0), int(n_points), _p(c), C.byref(d_res), C.c_void_p(stream or 0)))
+        return d_res.value
+
+    def download_reloc_pnp(self, job):
+        """Job `job` of the last relocalize_pnp -> dict(pnp (PNP_RESULT_DTYPE scalar), corr (N,) PNP_CORR_DTYPE and inliers (N,) u8 of the
+        gathered problem, row (cap,) i32 handed to the cascade, result (RELOC_RESULT_DTYPE scalar), frame_point (cap,), outlier (cap,))."""
+        pnp = np.zeros(1, PNP_RESULT_DTYPE); n = C.c_int(); corr = np.zeros(self.cap, PNP_CORR_DTYPE); inl = np.zeros(self.cap, np.uint8)
+        row = np.zeros(self.cap, np.int32); res = np.zeros(1, RELOC_RESULT_DTYPE); fp = np.zeros(self.cap, np.int32); out = np.zeros(self.cap, np.uint8)
+        check(lib().sd_batch_download_reloc_pnp(self.h, job, _p(pnp), C.byref(n), _p(corr), _p(inl), _p(row), _p(res), _p(fp), _p(out), self.cap))
+        return dict(pnp=pnp[0], corr=corr[:n.value].copy(), inliers=inl[:n.value].copy(), row=row, result=res[0], frame_point=fp, outlier=out)
 
     def download_reloc(self, job):
         """Job `job` of the last relocalize_refine -> (result (RELOC_RESULT_DTYPE scalar), frame_point (cap,) i32, outlier (cap,) u8)."""
@@ -1261,6 +1290,53 @@ def sim3_ransac(corr_offset, corr, problems, probability=0.99, min_inliers=20, m
                                       C.c_void_p(d_r.data_ptr()), C.c_void_p(d_i.data_ptr()), None, C.c_void_p(stream)))
     torch.cuda.synchronize()
     return d_r.cpu().numpy().view(SIM3_RESULT_DTYPE)[:n].copy(), d_i.cpu().numpy()[:len(c)].copy()
+
+
+# ---- PnPsolver on the device (include/sd_frontend.h: sd_pnp_ransac_*) ----
+PNP_CORR_DTYPE = np.dtype([("xw", "<f4", (3,)), ("uv", "<f4", (2,)), ("sigma2", "<f4"), ("tag", "<i4")])                # sd_pnp_corr
+PNP_PROBLEM_DTYPE = np.dtype([("K", "<f4", (4,)), ("seed", "<u8"), ("start_iteration", "<i4"), ("n_iterations", "<i4")])   # sd_pnp_problem; K = fx fy cx cy
+PNP_RESULT_DTYPE = np.dtype([("kind", "<i4"), ("no_more", "<i4"), ("iteration", "<i4"), ("n_inliers", "<i4"), ("best_iteration", "<i4"),
+                             ("best_inliers", "<i4"), ("n_refines", "<i4"), ("min_inliers", "<i4"), ("max_its", "<i4"), ("reserved", "<i4"),
+                             ("Tcw", "<f4", (16,))])                                                      # sd_pnp_result
+PNP_MAX_CORRESPONDENCES, PNP_MAX_ITERATIONS, PNP_MAX_PROBLEMS = 4096, 4096, 65535
+
+
+def pnp_ransac(corr_offset, corr, problems, probability=0.99, min_inliers=10, max_iterations=300, min_set=4, epsilon=0.5, th2=5.991,
+               device=False, counts=False):
+    """n independent PnPsolver::iterate problems in one launch sequence (sd_pnp_ransac_host; device=True goes through
+    sd_pnp_ransac_device with torch-owned device arrays and one explicit synchronisation).  corr_offset (n + 1,) int32, corr (E,)
+    PNP_CORR_DTYPE, problems (n,) PNP_PROBLEM_DTYPE; the other arguments are SetRansacParameters'.  Returns (results (n,)
+    PNP_RESULT_DTYPE, inliers (E,) u8, in the order of corr) in either form; counts=True appends the debug download: an (n, stride) int32
+    array whose row p holds the inlier counts of iterations 1 .. end of problem p and an (n, stride, 12) f64 array of the hypotheses
+    (mRi row-major, mti), stride = the largest iteration count the arguments allow."""
+    off = np.ascontiguousarray(corr_offset, np.int32).reshape(-1)
+    n = len(off) - 1
+    c = np.ascontiguousarray(corr, PNP_CORR_DTYPE).reshape(-1)
+    pr = np.ascontiguousarray(problems, PNP_PROBLEM_DTYPE).reshape(-1)
+    assert len(pr) == n
+    res = np.zeros(max(n, 1), PNP_RESULT_DTYPE); inl = np.zeros(max(len(c), 1), np.uint8)
+    stride = max([int(max_iterations)] + [int(q["start_iteration"]) + int(q["n_iterations"]) for q in pr]) if counts else 0
+    cnt = np.zeros((max(n, 1), max(stride, 1)), np.int32) if counts else None
+    pos = np.zeros((max(n, 1), max(stride, 1), 12), np.float64) if counts else None
+    if not device:
+        check(lib().sd_pnp_ransac_host(n, _p(off), _p(c), _p(pr), probability, min_inliers, max_iterations, min_set, epsilon, th2, _p(res),
+                                       _p(inl), _p(cnt) if counts else None, _p(pos) if counts else None, stride))
+        return (res[:n], inl[:len(c)], cnt[:n], pos[:n]) if counts else (res[:n], inl[:len(c)])
+    import torch
+    lib()
+    d_c = torch.from_numpy(c.view(np.uint8).reshape(-1).copy() if len(c) else np.zeros(1, np.uint8)).cuda()
+    d_r = torch.zeros(max(n, 1) * PNP_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    d_i = torch.zeros(max(len(c), 1), dtype=torch.uint8, device="cuda")
+    d_n = torch.zeros((max(n, 1), max(stride, 1)), dtype=torch.int32, device="cuda") if counts else None
+    d_p = torch.zeros((max(n, 1), max(stride, 1), 12), dtype=torch.float64, device="cuda") if counts else None
+    stream = torch.cuda.current_stream().cuda_stream
+    check(lib().sd_pnp_ransac_device(n, _p(off), C.c_void_p(d_c.data_ptr()), _p(pr), probability, min_inliers, max_iterations, min_set, epsilon,
+                                     th2, C.c_void_p(d_r.data_ptr()), C.c_void_p(d_i.data_ptr()),
+                                     C.c_void_p(d_n.data_ptr()) if counts else None, C.c_void_p(d_p.data_ptr()) if counts else None, stride,
+                                     C.c_void_p(stream)))
+    torch.cuda.synchronize()
+    out = (d_r.cpu().numpy().view(PNP_RESULT_DTYPE)[:n].copy(), d_i.cpu().numpy()[:len(c)].copy())
+    return out + (d_n.cpu().numpy()[:n].copy(), d_p.cpu().numpy()[:n].copy()) if counts else out
 
 
 # ---- Optimizer::OptimizeSim3 on the device (include/sd_frontend.h: sd_sim3_optimize_*) ----
