@@ -10,6 +10,7 @@
 #include "k_sort.h"
 #include "k_extract.h"
 #include "k_area.h"
+#include "k_match.h"
 
 // Keypoints of BOTH eyes bucketed by integer row (counting sort in LDS, grid = (frames, 2 eyes)): rowStart[y] .. rowStart[y+1] are
 // the keypoints of that image with (int)y == y.  The order inside a bucket is irrelevant: the matcher takes the lexicographic minimum of
@@ -417,7 +418,6 @@ __global__ void __launch_bounds__(256) k_hamming_matrix(const uint8_t* __restric
 //   k_proj_candidates   ORBmatcher::SearchByProjection, search part   src/ORBmatcher.cc:407-485,1485-1570
 //   k_proj_resolve      ... assignment order, rotation histogram      src/ORBmatcher.cc:487-559,1572-1627
 // =====================================================================================
-#define SD_HISTO 30       // HISTO_LENGTH, ORBmatcher.cc:39
 
 // cell id = posX*48 + posY, or -1 when the keypoint falls outside the 64x48 grid.  The reference's
 // per-cell index lists are ordered by keypoint index, so (cell id, index) is the visiting order of
@@ -700,7 +700,7 @@ __global__ void __launch_bounds__(64) k_proj_resolve(
     uint8_t* s_bin = s_taken + capA;                        // [capA] rotation bin of pair p
     uint8_t* s_n = s_bin + capA;                            // [capA] candidate count (<= 64) of every Last-frame point | 0x80 if it has observations
     __shared__ int s_hist[SD_HISTO];
-    __shared__ int s_ind[3];
+    __shared__ SdRotKeep s_keep;
     const int pair = blockIdx.x, lane = threadIdx.x;
     const int imgC = pairIdx[pair].x, imgL = pairIdx[pair].y;
     const int Nl = count[imgL], Nc = count[imgC];
@@ -730,7 +730,6 @@ __global__ void __launch_bounds__(64) k_proj_resolve(
     }
     if (lane < SD_HISTO) s_hist[lane] = 0;
     __syncthreads();
-    const float factor = 1.0f / SD_HISTO;
     int np = 0;
     for (int base = 0; base < Nl; base += 64) {
         const int i = base + lane;
@@ -788,13 +787,7 @@ __global__ void __launch_bounds__(64) k_proj_resolve(
             const int p = np + __popcll(pm & ((1ull << lane) - 1ull));
             pairs[2 * p] = i; pairs[2 * p + 1] = pick;
             int bin = 0;
-            if (checkOrientation) {
-                float rot = s_angL[i] - s_angC[pick];
-                if (rot < 0.0f) rot += 360.0f;
-                bin = (int)roundf(rot * factor);
-                if (bin == SD_HISTO) bin = 0;
-                atomicAdd(&s_hist[bin], 1);
-            }
+            if (checkOrientation) { bin = sd_rot_bin(s_angL[i], s_angC[pick]); atomicAdd(&s_hist[bin], 1); }
             s_bin[p] = (uint8_t)bin;
         }
         np += __popcll(pm);
@@ -802,25 +795,11 @@ __global__ void __launch_bounds__(64) k_proj_resolve(
     }
     int culled = 0;
     if (checkOrientation) {
-        if (lane == 0) {
-            // ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:1758-1799)
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int b = 0; b < SD_HISTO; b++) {
-                const int s = s_hist[b];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-                else if (s > max3) { max3 = s; ind3 = b; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-            s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-        }
+        if (lane == 0) s_keep = sd_three_maxima(s_hist);
         __syncthreads();
-        const int i1 = s_ind[0], i2 = s_ind[1], i3 = s_ind[2];
-        for (int p = lane; p < np; p += 64) {
-            const int b = s_bin[p];
-            if (b != i1 && b != i2 && b != i3) { s_match[pairs[2 * p + 1]] = -1; culled++; }
-        }
+        const SdRotKeep keep = s_keep;
+        for (int p = lane; p < np; p += 64)
+            if (!keep.keeps(s_bin[p])) { s_match[pairs[2 * p + 1]] = -1; culled++; }
 #pragma unroll
         for (int s = 32; s > 0; s >>= 1) culled += __shfl_xor(culled, s, 64);
         __syncthreads();

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "k_area.h"
+#include "k_match.h"
 #include "k_bow.h"
 
 struct SdFuseHit { int cand, idx, dist, action, other; };       // sd_fuse_hit
@@ -96,9 +97,7 @@ __global__ void __launch_bounds__(256) k_fuse_search(
             }
         }
     }
-    unsigned w = bestKey;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)w, d, 64); w = o < w ? o : w; }
+    const unsigned w = sd_wave_min_u32(bestKey);
     int2 out = make_int2(-1, 256);
     if (w != 0xFFFFFFFFu) {
         const unsigned long long who = __ballot(bestKey == w);           // keys are unique: the walk position is in the low bits
@@ -188,8 +187,7 @@ __global__ void __launch_bounds__(256) k_distinctive(int nPoints, const int* __r
             }
             key = ((unsigned)lo << 16) | (unsigned)lane;
         }
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)key, d, 64); key = o < key ? o : key; }
+        key = sd_wave_min_u32(key);
         bestRow = (int)(key & 0xFFFFu);                 // the first row with the strictly smallest median
     } else {
         int bestMedian = 0x7FFFFFFF;

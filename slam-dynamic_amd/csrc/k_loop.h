@@ -17,7 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "k_area.h"
-#include "k_bow.h"
+#include "k_match.h"
 #include "k_fuse.h"
 
 #define SD_ERR_LOOP_LIST 128     // bit of the workspace's capacity flag (sd_batch_sync)
@@ -134,9 +134,7 @@ __global__ void __launch_bounds__(256) k_loop_search(
         }
     }
     if (MODE == 0) {
-        unsigned w = bestKey;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)w, d, 64); w = o < w ? o : w; }
+        const unsigned w = sd_wave_min_u32(bestKey);
         int2 out = make_int2(-1, 256);
         if (w != 0xFFFFFFFFu) {
             const unsigned long long who = __ballot(bestKey == w);           // keys are unique: the walk position is in the low bits
@@ -211,9 +209,9 @@ __global__ void __launch_bounds__(64) k_loop_assign(const int* __restrict__ cand
 }
 
 // ---------------------------------------------------------------- ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12)
-// The structure of k_search_by_bow (k_bow.h): one workgroup per pair, a wave per FeatureVector node both keyframes share, KF1's
-// features of the node in order, best and second best over the not-yet-taken valid KF2 features; the register path up to SD_BOW_REGF
-// KF2 features, the memory path beyond.  What differs: the result is indexed by the KF1 feature (match12[idx1] = idx2), KF2 has a
+// The shared body of k_match.h: one workgroup per pair, a wave per FeatureVector node both keyframes share, KF1's features of the node
+// in order, best and second best over the not-yet-taken valid KF2 features; the register path up to SD_BOW_REGF KF2 features, the
+// memory path beyond.  What differs from k_search_by_bow: the result is indexed by the KF1 feature (match12[idx1] = idx2), KF2 has a
 // validity mask too, the acceptance is bestDist1 < TH_LOW (strict), and the histogram holds idx1.
 __global__ void __launch_bounds__(64 * SD_BOW_WAVES) k_search_by_bow_kf(
     const sd_keypoint* __restrict__ kp, const uint8_t* __restrict__ desc, const int* __restrict__ count,
@@ -221,176 +219,6 @@ __global__ void __launch_bounds__(64 * SD_BOW_WAVES) k_search_by_bow_kf(
     const int* __restrict__ meta, const uint8_t* __restrict__ valid1 /*nullable [pair][cap]*/, const uint8_t* __restrict__ valid2,
     const int2* __restrict__ pairIdx, int cap, float nnratio, int checkOrientation, int* __restrict__ matchOut, int* __restrict__ nmatchOut)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    int* s_match = (int*)smem;                               // [cap] match12
-    uint8_t* s_bin = (uint8_t*)(s_match + cap);              // [cap] by idx1
-    uint8_t* s_taken = s_bin + cap;                          // [cap] vbMatched2 (the memory path)
-    __shared__ int s_hist[SD_HISTO];
-    __shared__ int s_ind[3];
-    __shared__ int s_nm;
-    const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int img1 = pairIdx[pair].x, img2 = pairIdx[pair].y;
-    const int N1 = count[img1], N2 = count[img2];
-    for (int i = tid; i < N1; i += 64 * SD_BOW_WAVES) s_match[i] = -1;
-    for (int i = tid; i < N2; i += 64 * SD_BOW_WAVES) s_taken[i] = 0;
-    if (tid < SD_HISTO) s_hist[tid] = 0;
-    if (tid == 0) s_nm = 0;
-    __syncthreads();
-    const int runs1 = meta[img1 * 4 + 1], runs2 = meta[img2 * 4 + 1];
-    const int* rs1 = fvRunStart + (size_t)img1 * (cap + 1);
-    const int* rs2 = fvRunStart + (size_t)img2 * (cap + 1);
-    const unsigned* rn1 = fvRunNode + (size_t)img1 * cap;
-    const unsigned* rn2 = fvRunNode + (size_t)img2 * cap;
-    const unsigned* ff1 = fvFeat + (size_t)img1 * cap;
-    const unsigned* ff2 = fvFeat + (size_t)img2 * cap;
-    const uint8_t* d1 = desc + (size_t)img1 * cap * 32;
-    const uint8_t* d2 = desc + (size_t)img2 * cap * 32;
-    const sd_keypoint* k1p = kp + (size_t)img1 * cap;
-    const sd_keypoint* k2p = kp + (size_t)img2 * cap;
-    const uint8_t* v1 = valid1 ? valid1 + (size_t)pair * cap : nullptr;
-    const uint8_t* v2 = valid2 ? valid2 + (size_t)pair * cap : nullptr;
-    const float factor = 1.0f / SD_HISTO;
-    int nm = 0;
-    for (int rk = wv; rk < runs1; rk += SD_BOW_WAVES) {
-        const unsigned node = rn1[rk];
-        int lo = 0, hi = runs2;                               // lower_bound of node in KF2's runs
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (rn2[mid] < node) lo = mid + 1; else hi = mid; }
-        if (lo >= runs2 || rn2[lo] != node) continue;
-        const int a0 = rs1[rk], a1 = rs1[rk + 1], c0 = rs2[lo], c1 = rs2[lo + 1];
-        if (c1 - c0 <= SD_BOW_REGF) {
-            // ---- the register path: lane l owns KF2 positions l and l + 64 of the node and their taken flags
-            unsigned i2l[2]; uint4 f0[2], f1[2]; bool freeF[2];
-#pragma unroll
-            for (int q = 0; q < 2; q++) {
-                const int c = c0 + lane + 64 * q;
-                freeF[q] = c < c1;
-                i2l[q] = freeF[q] ? ff2[c] : 0u;
-                if (freeF[q] && v2 && !v2[i2l[q]]) freeF[q] = false;
-                const uint4* pf = (const uint4*)(d2 + (size_t)i2l[q] * 32);
-                f0[q] = pf[0]; f1[q] = pf[1];
-            }
-            for (int kb = a0; kb < a1; kb += 64) {
-                const int a = kb + lane;
-                const unsigned i1l = a < a1 ? ff1[a] : 0u;
-                const int ok1 = a < a1 && (!v1 || v1[i1l]);
-                const uint4* pk = (const uint4*)(d1 + (size_t)i1l * 32);
-                const uint4 kl0 = pk[0], kl1 = pk[1];
-                const float ang1 = k1p[i1l].angle;
-                const int nstep = a1 - kb < 64 ? a1 - kb : 64;
-                for (int t = 0; t < nstep; t++) {
-                    if (!__builtin_amdgcn_readlane(ok1, t)) continue;
-                    uint4 k0, k1;
-                    k0.x = (unsigned)__builtin_amdgcn_readlane((int)kl0.x, t); k0.y = (unsigned)__builtin_amdgcn_readlane((int)kl0.y, t);
-                    k0.z = (unsigned)__builtin_amdgcn_readlane((int)kl0.z, t); k0.w = (unsigned)__builtin_amdgcn_readlane((int)kl0.w, t);
-                    k1.x = (unsigned)__builtin_amdgcn_readlane((int)kl1.x, t); k1.y = (unsigned)__builtin_amdgcn_readlane((int)kl1.y, t);
-                    k1.z = (unsigned)__builtin_amdgcn_readlane((int)kl1.z, t); k1.w = (unsigned)__builtin_amdgcn_readlane((int)kl1.w, t);
-                    unsigned key[2];
-#pragma unroll
-                    for (int q = 0; q < 2; q++)
-                        key[q] = freeF[q] ? (((unsigned)sd_hamming256(k0, k1, f0[q], f1[q]) << 16) | (unsigned)(lane + 64 * q)) : 0xFFFFFFFFu;
-                    unsigned b1 = key[0] < key[1] ? key[0] : key[1];
-                    unsigned b2 = key[0] < key[1] ? key[1] : key[0];
-#pragma unroll
-                    for (int d = 32; d > 0; d >>= 1) {
-                        const unsigned o1 = (unsigned)__shfl_xor((int)b1, d, 64), o2 = (unsigned)__shfl_xor((int)b2, d, 64);
-                        const unsigned hi1 = b1 > o1 ? b1 : o1, lo2 = b2 < o2 ? b2 : o2;
-                        b1 = b1 < o1 ? b1 : o1;
-                        b2 = hi1 < lo2 ? hi1 : lo2;
-                    }
-                    if (b1 == 0xFFFFFFFFu) continue;
-                    const int bestDist1 = (int)(b1 >> 16), bestDist2 = b2 == 0xFFFFFFFFu ? 256 : (int)(b2 >> 16);
-                    if (bestDist1 < SD_TH_LOW && (float)bestDist1 < nnratio * (float)bestDist2) {
-                        const int pos = (int)(b1 & 0xFFFFu);
-                        const unsigned i1t = (unsigned)__builtin_amdgcn_readlane((int)i1l, t);
-                        const float a1t = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ang1), t));
-                        if ((pos & 63) == lane) {
-                            const int q = pos >> 6;
-                            const unsigned i2 = q ? i2l[1] : i2l[0];
-                            if (q) freeF[1] = false; else freeF[0] = false;
-                            s_match[i1t] = (int)i2;
-                            int bin = 0;
-                            if (checkOrientation) {
-                                float rot = a1t - k2p[i2].angle;
-                                if (rot < 0.0f) rot += 360.0f;
-                                bin = (int)roundf(rot * factor);
-                                if (bin == SD_HISTO) bin = 0;
-                                atomicAdd(&s_hist[bin], 1);
-                            }
-                            s_bin[i1t] = (uint8_t)bin;
-                        }
-                        nm++;
-                    }
-                }
-            }
-        } else {
-            // ---- the memory path: lanes over KF2's features of the node, the taken flags in LDS
-            for (int a = a0; a < a1; a++) {
-                const unsigned i1 = ff1[a];
-                if (v1 && !v1[i1]) continue;
-                const uint4* pk = (const uint4*)(d1 + (size_t)i1 * 32);
-                const uint4 k0 = pk[0], k1 = pk[1];
-                unsigned b1 = 0xFFFFFFFFu, b2 = 0xFFFFFFFFu;     // smallest and second smallest (distance << 16 | position in the node)
-                for (int c = c0 + lane; c < c1; c += 64) {
-                    const unsigned i2 = ff2[c];
-                    if (s_taken[i2] || (v2 && !v2[i2])) continue;
-                    const uint4* pf = (const uint4*)(d2 + (size_t)i2 * 32);
-                    const unsigned key = ((unsigned)sd_hamming256(k0, k1, pf[0], pf[1]) << 16) | (unsigned)(c - c0);
-                    if (key < b1) { b2 = b1; b1 = key; } else if (key < b2) b2 = key;
-                }
-#pragma unroll
-                for (int d = 32; d > 0; d >>= 1) {
-                    const unsigned o1 = (unsigned)__shfl_xor((int)b1, d, 64), o2 = (unsigned)__shfl_xor((int)b2, d, 64);
-                    const unsigned hi1 = b1 > o1 ? b1 : o1, lo2 = b2 < o2 ? b2 : o2;
-                    b1 = b1 < o1 ? b1 : o1;
-                    b2 = hi1 < lo2 ? hi1 : lo2;
-                }
-                if (b1 == 0xFFFFFFFFu) continue;                  // no free valid KF2 feature in this node
-                const int bestDist1 = (int)(b1 >> 16), bestDist2 = b2 == 0xFFFFFFFFu ? 256 : (int)(b2 >> 16);
-                if (bestDist1 < SD_TH_LOW && (float)bestDist1 < nnratio * (float)bestDist2) {
-                    const unsigned i2 = ff2[c0 + (int)(b1 & 0xFFFFu)];
-                    if (lane == 0) {
-                        s_match[i1] = (int)i2;
-                        s_taken[i2] = 1;
-                        int bin = 0;
-                        if (checkOrientation) {
-                            float rot = k1p[i1].angle - k2p[i2].angle;
-                            if (rot < 0.0f) rot += 360.0f;
-                            bin = (int)roundf(rot * factor);
-                            if (bin == SD_HISTO) bin = 0;
-                            atomicAdd(&s_hist[bin], 1);
-                        }
-                        s_bin[i1] = (uint8_t)bin;
-                    }
-                    nm++;
-                    __builtin_amdgcn_wave_barrier();
-                }
-                __threadfence_block();                            // s_taken written by lane 0 is read by every lane next round
-            }
-        }
-    }
-    if (lane == 0) atomicAdd(&s_nm, nm);
-    __syncthreads();
-    if (checkOrientation) {
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;     // ComputeThreeMaxima (ORBmatcher.cc:1758-1799)
-            for (int b = 0; b < SD_HISTO; b++) {
-                const int s = s_hist[b];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-                else if (s > max3) { max3 = s; ind3 = b; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-            s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-        }
-        __syncthreads();
-        const int i1 = s_ind[0], i2 = s_ind[1], i3 = s_ind[2];
-        int culled = 0;
-        for (int i = tid; i < N1; i += 64 * SD_BOW_WAVES)
-            if (s_match[i] >= 0) { const int b = s_bin[i]; if (b != i1 && b != i2 && b != i3) { s_match[i] = -1; culled++; } }
-        if (culled) atomicSub(&s_nm, culled);
-        __syncthreads();
-    }
-    for (int i = tid; i < cap; i += 64 * SD_BOW_WAVES) matchOut[(size_t)pair * cap + i] = i < N1 ? s_match[i] : -1;
-    if (tid == 0) nmatchOut[pair] = s_nm;
+    sd_search_by_bow<true, true>(kp, desc, count, fvFeat, fvRunStart, fvRunNode, meta, valid1, valid2, pairIdx, cap, nnratio,
+                                 checkOrientation, matchOut, nmatchOut);
 }

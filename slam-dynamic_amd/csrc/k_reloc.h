@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "k_area.h"
+#include "k_match.h"
 #include "k_loop.h"
 
 #define SD_RELOC_ERR_POINT 1     // a d_kf_point or d_frame_point value outside [-1, n_points)
@@ -153,16 +154,6 @@ __global__ void __launch_bounds__(256) k_reloc_search(
     if (lane == 0) exitCode[e] = ex;
 }
 
-// rot = kf angle - frame angle -> rotation bin (ORBmatcher.cc:1719-1724)
-__device__ __forceinline__ int sd_reloc_bin(float angleKf, float angleFrame)
-{
-    float rot = angleKf - angleFrame;
-    if (rot < 0.0f) rot += 360.0f;
-    int bin = (int)roundf(rot * (1.0f / SD_HISTO));
-    if (bin == SD_HISTO) bin = 0;
-    return (unsigned)bin < (unsigned)SD_HISTO ? bin : 0;         // angles outside [0, 360): the reference asserts
-}
-
 // One wave per job: the keyframe's features in order, 64 per chunk (see the head of k_loop.h).  taken = one bit per frame feature in
 // dynamic LDS ((cap + 31) / 32 words).  Lane l owns the features p = l (mod 64) in the replay and in the culling pass, so what a
 // lane reads back from memory it wrote itself.
@@ -178,7 +169,7 @@ __global__ void __launch_bounds__(64) k_reloc_assign(
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned* taken = (unsigned*)smem;
     __shared__ int s_hist[SD_HISTO];
-    __shared__ int s_ind[3];
+    __shared__ SdRotKeep s_keep;
     const int job = blockIdx.x, lane = threadIdx.x;
     const int fimg = slots[job].x, kimg = slots[job].y;
     const int N1 = min(count[kimg], cap), N2 = min(count[fimg], cap);
@@ -239,7 +230,7 @@ __global__ void __launch_bounds__(64) k_reloc_assign(
                     atomicOr(&taken[pickIdx >> 5], 1u << (pickIdx & 31));
                     int m = krow[p];
                     frow[pickIdx] = m; arow[pickIdx] = p; nm++;
-                    atomicAdd(&s_hist[sd_reloc_bin(kkp[p].angle, fkp[pickIdx].angle)], 1);
+                    atomicAdd(&s_hist[sd_rot_bin(kkp[p].angle, fkp[pickIdx].angle)], 1);
                 }
                 if (pickIdx < 0 && total > SD_PROJ_K) atomicOr(capFlag, SD_ERR_LOOP_LIST);     // every kept key taken, the window held more
                 exitCode[e] = take ? SD_RELOC_MATCHED : (pickIdx < 0 ? SD_RELOC_NO_FREE : SD_RELOC_ABOVE_DIST);
@@ -250,27 +241,15 @@ __global__ void __launch_bounds__(64) k_reloc_assign(
         }
     }
     __syncthreads();
-    if (lane == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;     // ComputeThreeMaxima (ORBmatcher.cc:1758-1799)
-        for (int b = 0; b < SD_HISTO; b++) {
-            const int s = s_hist[b];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-            else if (s > max3) { max3 = s; ind3 = b; }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-    }
+    if (lane == 0) s_keep = sd_three_maxima(s_hist);
     __syncthreads();
-    const int i1 = s_ind[0], i2 = s_ind[1], i3 = s_ind[2];
+    const SdRotKeep keep = s_keep;
     for (int p = lane; p < cap; p += 64) {
         const size_t e = r0 + p;
         if (p >= N1) { exitCode[e] = SD_RELOC_NULL; best[e] = make_int2(-1, 256); continue; }
         if (exitCode[e] != SD_RELOC_MATCHED) continue;
         const int idx = best[e].x;
-        const int b = sd_reloc_bin(kkp[p].angle, fkp[idx].angle);
-        if (b != i1 && b != i2 && b != i3) { frow[idx] = -1; arow[idx] = -1; exitCode[e] = SD_RELOC_CULLED; nm--; }
+        if (!keep.keeps(sd_rot_bin(kkp[p].angle, fkp[idx].angle))) { frow[idx] = -1; arow[idx] = -1; exitCode[e] = SD_RELOC_CULLED; nm--; }
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) nm += __shfl_xor(nm, d, 64);

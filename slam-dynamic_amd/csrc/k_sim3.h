@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "k_area.h"
+#include "k_match.h"
 #include "k_motion.h"
 
 #define SD_SIM3_CHUNK 512            // correspondences staged in LDS at a time (12 floats each, 24 KB)
@@ -444,9 +445,7 @@ __global__ void __launch_bounds__(256) k_sim3_search(SdSim3SearchArgs A, SdLevel
             }
         }
     }
-    unsigned w = bestKey;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)w, d, 64); w = o < w ? o : w; }
+    const unsigned w = sd_wave_min_u32(bestKey);
     int out = -1;
     if (w != 0xFFFFFFFFu && (int)(w >> 16) <= SD_SIM3_TH_HIGH) {
         const unsigned long long who = __ballot(bestKey == w);           // keys are unique: the walk position is in the low bits

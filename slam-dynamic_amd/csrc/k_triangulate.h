@@ -11,11 +11,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "k_frame.h"
+#include "k_match.h"
 #include "k_bow.h"
 
 #define SD_TRI_WAVES 16
 #define SD_TRI_THREADS (64 * SD_TRI_WAVES)
-#define SD_TRI_REGF 128          // KF2 features of a node that the register path holds (two per lane); larger nodes stream from memory
 #define SD_TRI_SWEEPS 8          // Jacobi sweeps of the 4x4 null vector (Q29)
 
 struct SdTriPair {
@@ -42,15 +42,9 @@ __device__ __forceinline__ unsigned sd_tri_key(int dist, int pos, bool ok2, bool
     return ((unsigned)dist << 16) | (unsigned)(0xFFFF - pos);           // minimum distance, the LAST position on a tie
 }
 
-__device__ __forceinline__ unsigned sd_wave_min_u32(unsigned k)
-{
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)k, d, 64); k = o < k ? o : k; }
-    return k;
-}
-
-// One workgroup per pair, one wave per vocabulary node both FeatureVectors share; the wave walks KF1's features of the node one
-// after the other, its lanes run over KF2's features of the node.
+// One workgroup per pair, one wave per vocabulary node both FeatureVectors share (the node pairing of k_match.h); the wave walks KF1's
+// features of the node one after the other, its lanes run over KF2's features of the node: in registers up to SD_BOW_REGF of them, from
+// memory beyond.
 __global__ void __launch_bounds__(SD_TRI_THREADS) k_tri_match(
     const sd_keypoint* __restrict__ kpUn, const uint8_t* __restrict__ desc, const float* __restrict__ uRight, const int* __restrict__ count,
     const unsigned* __restrict__ fvFeat, const int* __restrict__ fvRunStart, const unsigned* __restrict__ fvRunNode,
@@ -63,7 +57,7 @@ __global__ void __launch_bounds__(SD_TRI_THREADS) k_tri_match(
     int* s_cnt = s_match + cap;                              // [SD_TRI_THREADS]
     uint8_t* s_bin = (uint8_t*)(s_cnt + SD_TRI_THREADS);     // [cap]
     __shared__ int s_hist[SD_HISTO];
-    __shared__ int s_ind[3];
+    __shared__ SdRotKeep s_keep;
     __shared__ int s_total;
     __shared__ float s_scale[SD_MAX_LEVELS], s_sigma2[SD_MAX_LEVELS];
     const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -74,17 +68,9 @@ __global__ void __launch_bounds__(SD_TRI_THREADS) k_tri_match(
     if (tid < SD_HISTO) s_hist[tid] = 0;
     if (tid < SD_MAX_LEVELS) { s_scale[tid] = L.scale[tid]; s_sigma2[tid] = L.sigma2[tid]; }
     __syncthreads();
-    const int runs1 = P->skip ? 0 : meta[img1 * 4 + 1], runs2 = meta[img2 * 4 + 1];
-    const int* rs1 = fvRunStart + (size_t)img1 * (cap + 1);
-    const int* rs2 = fvRunStart + (size_t)img2 * (cap + 1);
-    const unsigned* rn1 = fvRunNode + (size_t)img1 * cap;
-    const unsigned* rn2 = fvRunNode + (size_t)img2 * cap;
-    const unsigned* ff1 = fvFeat + (size_t)img1 * cap;
-    const unsigned* ff2 = fvFeat + (size_t)img2 * cap;
-    const uint8_t* d1 = desc + (size_t)img1 * cap * 32;
-    const uint8_t* d2 = desc + (size_t)img2 * cap * 32;
-    const sd_keypoint* k1 = kpUn + (size_t)img1 * cap;
-    const sd_keypoint* k2 = kpUn + (size_t)img2 * cap;
+    const SdFvView V1 = sd_fv_view(kpUn, desc, fvFeat, fvRunStart, fvRunNode, meta, img1, cap);
+    const SdFvView V2 = sd_fv_view(kpUn, desc, fvFeat, fvRunStart, fvRunNode, meta, img2, cap);
+    const int runs1 = P->skip ? 0 : V1.runs;
     const float* ur1 = uRight + (size_t)img1 * cap;
     const float* ur2 = uRight + (size_t)img2 * cap;
     const uint8_t* h1 = hasMp1 ? hasMp1 + (size_t)P->row1 * cap : nullptr;
@@ -92,14 +78,11 @@ __global__ void __launch_bounds__(SD_TRI_THREADS) k_tri_match(
     const float ex = P->ex, ey = P->ey;
     const float F00 = P->F12[0], F01 = P->F12[1], F02 = P->F12[2], F10 = P->F12[3], F11 = P->F12[4], F12_ = P->F12[5],
                 F20 = P->F12[6], F21 = P->F12[7], F22 = P->F12[8];
-    const float factor = 1.0f / SD_HISTO;
     for (int r1 = wv; r1 < runs1; r1 += SD_TRI_WAVES) {
-        const unsigned node = rn1[r1];
-        int lo = 0, hi = runs2;                               // lower_bound of the node in KF2's runs
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (rn2[mid] < node) lo = mid + 1; else hi = mid; }
-        if (lo >= runs2 || rn2[lo] != node) continue;
-        const int a0 = rs1[r1], a1 = rs1[r1 + 1], c0 = rs2[lo], c1 = rs2[lo + 1];
-        const bool inRegs = c1 - c0 <= SD_TRI_REGF;
+        const SdNodePair n = sd_fv_pair(V1, r1, V2);
+        if (!n.found) continue;
+        const int a0 = n.a0, a1 = n.a1, c0 = n.c0, c1 = n.c1;
+        const bool inRegs = c1 - c0 <= SD_BOW_REGF;
         // register path: lane l owns positions l and l + 64 of the node's KF2 list for the whole node
         bool ok2[2] = {false, false}, mono2[2] = {false, false}, nearEp[2] = {false, false};
         uint4 g0[2], g1[2]; float x2[2], y2[2]; double th[2];
@@ -108,8 +91,8 @@ __global__ void __launch_bounds__(SD_TRI_THREADS) k_tri_match(
             g0[q] = make_uint4(0, 0, 0, 0); g1[q] = g0[q]; x2[q] = 0.f; y2[q] = 0.f; th[q] = 0.0;
             const int c = c0 + lane + 64 * q;
             if (inRegs && c < c1) {
-                const unsigned i2 = ff2[c];
-                const sd_keypoint kp = k2[i2];
+                const unsigned i2 = V2.feat[c];
+                const sd_keypoint kp = V2.kp[i2];
                 const bool st2 = ur2[i2] >= 0;
                 ok2[q] = !(h2 && h2[i2]) && (!onlyStereo || st2);
                 mono2[q] = !st2;
@@ -117,17 +100,17 @@ __global__ void __launch_bounds__(SD_TRI_THREADS) k_tri_match(
                 nearEp[q] = dx * dx + dy * dy < 100 * s_scale[kp.octave];
                 th[q] = 3.84 * (double)s_sigma2[kp.octave];
                 x2[q] = kp.x; y2[q] = kp.y;
-                const uint4* pf = (const uint4*)(d2 + (size_t)i2 * 32);
+                const uint4* pf = (const uint4*)(V2.desc + (size_t)i2 * 32);
                 g0[q] = pf[0]; g1[q] = pf[1];
             }
         }
         for (int a = a0; a < a1; a++) {                       // wave-uniform
-            const unsigned i1 = ff1[a];
+            const unsigned i1 = V1.feat[a];
             if (h1 && h1[i1]) continue;
             const bool st1 = ur1[i1] >= 0;
             if (onlyStereo && !st1) continue;
-            const sd_keypoint kp1 = k1[i1];
-            const uint4* pk = (const uint4*)(d1 + (size_t)i1 * 32);
+            const sd_keypoint kp1 = V1.kp[i1];
+            const uint4* pk = (const uint4*)(V1.desc + (size_t)i1 * 32);
             const uint4 e0 = pk[0], e1 = pk[1];
             const float la = kp1.x * F00 + kp1.y * F10 + F20;             // the epipolar line of kp1 in KF2
             const float lb = kp1.x * F01 + kp1.y * F11 + F21;
@@ -143,11 +126,11 @@ __global__ void __launch_bounds__(SD_TRI_THREADS) k_tri_match(
                 }
             } else {
                 for (int c = c0 + lane; c < c1; c += 64) {
-                    const unsigned i2 = ff2[c];
-                    const sd_keypoint kp = k2[i2];
+                    const unsigned i2 = V2.feat[c];
+                    const sd_keypoint kp = V2.kp[i2];
                     const bool st2 = ur2[i2] >= 0;
                     const float dx = ex - kp.x, dy = ey - kp.y;
-                    const uint4* pf = (const uint4*)(d2 + (size_t)i2 * 32);
+                    const uint4* pf = (const uint4*)(V2.desc + (size_t)i2 * 32);
                     const unsigned key = sd_tri_key(sd_hamming256(e0, e1, pf[0], pf[1]), c - c0, !(h2 && h2[i2]) && (!onlyStereo || st2), !st1,
                                                     !st2, dx * dx + dy * dy < 100 * s_scale[kp.octave], la, lb, lc, den, kp.x, kp.y,
                                                     3.84 * (double)s_sigma2[kp.octave]);
@@ -157,38 +140,21 @@ __global__ void __launch_bounds__(SD_TRI_THREADS) k_tri_match(
             best = sd_wave_min_u32(best);
             if (best == 0xFFFFFFFFu) continue;
             if (lane == 0) {
-                const unsigned i2 = ff2[c0 + (0xFFFF - (int)(best & 0xFFFFu))];
+                const unsigned i2 = V2.feat[c0 + (0xFFFF - (int)(best & 0xFFFFu))];
                 s_match[i1] = (int)i2;
                 int bin = 0;
-                if (checkOrientation) {
-                    float rot = kp1.angle - k2[i2].angle;
-                    if (rot < 0.0f) rot += 360.0f;
-                    bin = (int)roundf(rot * factor);
-                    if (bin == SD_HISTO) bin = 0;
-                    atomicAdd(&s_hist[bin], 1);
-                }
+                if (checkOrientation) { bin = sd_rot_bin(kp1.angle, V2.kp[i2].angle); atomicAdd(&s_hist[bin], 1); }
                 s_bin[i1] = (uint8_t)bin;
             }
         }
     }
     __syncthreads();
     if (checkOrientation) {
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;     // ComputeThreeMaxima (ORBmatcher.cc:1758-1799)
-            for (int b = 0; b < SD_HISTO; b++) {
-                const int s = s_hist[b];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-                else if (s > max3) { max3 = s; ind3 = b; }
-            }
-            if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-            s_ind[0] = ind1; s_ind[1] = ind2; s_ind[2] = ind3;
-        }
+        if (tid == 0) s_keep = sd_three_maxima(s_hist);
         __syncthreads();
-        const int i1 = s_ind[0], i2 = s_ind[1], i3 = s_ind[2];
+        const SdRotKeep keep = s_keep;
         for (int i = tid; i < N1; i += SD_TRI_THREADS)
-            if (s_match[i] >= 0) { const int b = s_bin[i]; if (b != i1 && b != i2 && b != i3) s_match[i] = -1; }
+            if (s_match[i] >= 0 && !keep.keeps(s_bin[i])) s_match[i] = -1;
         __syncthreads();
     }
     // vMatchedPairs: (idx1, idx2) in ascending idx1.  Thread t owns idx1 in [t * per, (t + 1) * per)

@@ -15,8 +15,6 @@
 #define SD_HALF_PATCH 15    // HALF_PATCH_SIZE, ORBextractor.cc:73
 #define SD_PATCH 31         // PATCH_SIZE, ORBextractor.cc:72
 #define SD_MAX_LEVELS 12
-#define SD_TH_HIGH 100      // ORBmatcher.cc:37
-#define SD_TH_LOW 50        // ORBmatcher.cc:38
 
 struct SdLevel {            // POD, copied to the device by value
     int W, H;               // interior size of mvImagePyramid[level]

@@ -27,7 +27,7 @@ BRANCHES = ["shared_node", "skip_mp1", "skip_onlystereo1", "skip_mp2", "skip_onl
 PATHS = ["none", "svd", "unproject1", "unproject2"]
 OUTCOMES = ["created", "low_parallax", "w0", "z1", "z2", "reproj1_mono", "reproj1_stereo", "reproj2_mono", "reproj2_stereo", "dist0",
             "scale_low", "scale_high", "no_depth"]
-REGF = 128                # SD_TRI_REGF: KF2 features of a node that the device's register path holds
+REGF = 128                # SD_BOW_REGF: KF2 features of a node that the device's register path holds
 LEVELSUP = 2              # on the L = 3 vocabulary: FeatureVector nodes are the level-1 nodes
 GEOM = dict(W=640, H=480, nfeatures=600, scale=1.2, nlevels=8)          # the workspace of the crafted cases (its images are never read)
 CAM = dict(fx=F32(718.856), fy=F32(718.856), cx=F32(607.1928), cy=F32(185.2157), mbf=F32(386.1448))
