@@ -21,6 +21,23 @@ static_assert(sizeof(Edge) == 32, "edge record");
 struct Quat { double x, y, z, w; };                      // Eigen::Quaterniond coefficient order
 struct SE3 { Quat r; double t[3]; };
 
+// ---- the path report (sd_pose_oracle_paths): which branches a solve took.  Null unless a report was asked for. ----
+enum { END_NOT_RUN = 0, END_TEN_ITERATIONS = 1, END_QMAX = 2, END_RHO_ZERO = 3, END_NSTOP = 4, END_NO_ACTIVE_EDGE = 5 };
+struct Report {
+    int quatBranch = -1;         // Quaterniond(Matrix3d) of the most recent call: 0 tr > 0, 1 / 2 / 3 largest diagonal entry 0 / 1 / 2
+    int wFlipped = 0;            // normalizeRotation negated the most recent quaternion
+    int priorBranch = -1, priorFlipped = 0;
+    int smallAngleExp = 0;       // SE3Quat::exp calls with theta < 1e-5
+    int nonFinite = 0;           // some chi2 (active sum or classification) was inf or NaN
+    int ending[4] = {0, 0, 0, 0}, rejected[4] = {0, 0, 0, 0};
+    int reentered = 0;           // flags that went from outlier to inlier between two rounds
+    int lastRoundChanges = 0;    // flags the round without the robust kernel changed
+    int otherBranches = 0;       // bit b: some later Quaterniond(Matrix3d) (in exp) took branch b
+    double margin = DBL_MAX;     // min |chi2 - thr| / thr over every classification
+};
+thread_local Report* g_rep = nullptr;
+thread_local int g_flipBranch = -1;           // modes 128 / 512 / 1024: the `tr <= 0` branch whose w gets the wrong sign
+
 // ---- Eigen leaves (recalled: Eigen is not vendored in the reference) ----
 void q_normalize(Quat& q)
 {
@@ -29,6 +46,7 @@ void q_normalize(Quat& q)
 }
 void normalize_rotation(Quat& q)                         // SE3Quat::normalizeRotation
 {
+    if (g_rep) g_rep->wFlipped = q.w < 0;
     if (q.w < 0) { q.x = -q.x; q.y = -q.y; q.z = -q.z; q.w = -q.w; }
     q_normalize(q);
 }
@@ -38,6 +56,7 @@ Quat q_from_matrix(const double m[3][3])                 // Quaterniond(const Ma
     double c[4];                                         // x, y, z
     const double tr = m[0][0] + m[1][1] + m[2][2];
     if (tr > 0) {
+        if (g_rep) g_rep->quatBranch = 0;
         double t = std::sqrt(tr + 1.0);
         q.w = 0.5 * t;
         t = 0.5 / t;
@@ -50,10 +69,12 @@ Quat q_from_matrix(const double m[3][3])                 // Quaterniond(const Ma
     if (m[1][1] > m[0][0]) i = 1;
     if (m[2][2] > m[i][i]) i = 2;
     const int j = (i + 1) % 3, k = (j + 1) % 3;
+    if (g_rep) g_rep->quatBranch = 1 + i;
     double t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
     c[i] = 0.5 * t;
     t = 0.5 / t;
     q.w = (m[k][j] - m[j][k]) * t;
+    if (g_flipBranch == i) q.w = -q.w;
     c[j] = (m[j][i] + m[i][j]) * t;
     c[k] = (m[k][i] + m[i][k]) * t;
     q.x = c[0]; q.y = c[1]; q.z = c[2];
@@ -111,6 +132,7 @@ SE3 se3_exp(const double u[6])                            // SE3Quat::exp
     double Om2[3][3], R[3][3], V[3][3];
     mat3_mul(Om, Om, Om2);
     if (theta < 0.00001) {
+        if (g_rep) g_rep->smallAngleExp++;
         for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++) R[i][j] = V[i][j] = ((i == j ? 1.0 : 0.0) + Om[i][j]) + Om2[i][j];
     } else {
@@ -123,7 +145,9 @@ SE3 se3_exp(const double u[6])                            // SE3Quat::exp
     }
     double t[3];
     for (int i = 0; i < 3; i++) t[i] = V[i][0] * up[0] + V[i][1] * up[1] + V[i][2] * up[2];
-    return se3_from_rt(R, t);
+    const SE3 s = se3_from_rt(R, t);
+    if (g_rep) g_rep->otherBranches |= 1 << g_rep->quatBranch;
+    return s;
 }
 SE3 to_se3quat(const float* T)                            // Converter::toSE3Quat
 {
@@ -246,6 +270,7 @@ double active_chi(const Problem& P, const SE3& s)
         double e[3];
         const int D = edge_error(P.E[i], P.c, s, e, P.f64_invz);
         const double c2 = chi2_of(e, D, (double)P.E[i].inv_sigma2);
+        if (g_rep && !std::isfinite(c2)) g_rep->nonFinite = 1;
         if (P.robust) {
             const double delta = D == 2 ? dM : dS, dsqr = delta * delta;
             chi += c2 <= dsqr ? c2 : 2 * std::sqrt(c2) * delta - dsqr;
@@ -287,17 +312,18 @@ void build_system(const Problem& P, const SE3& s, double H[6][6], double b[6])
     }
 }
 
-struct RoundInfo { int iterations, lastRejected; };
+struct RoundInfo { int iterations, lastRejected, ending, rejected; };
 
 // SparseOptimizer::optimize(10) with OptimizationAlgorithmLevenberg; returns the final estimate and the pose of the last error pass
-int optimize(const Problem& P, SE3& est, SE3& errPose, RoundInfo& ri)
+int optimize(const Problem& P, SE3& est, SE3& errPose, RoundInfo& ri, bool lambdaInitSkipsNaN)
 {
-    ri.iterations = 0; ri.lastRejected = 0;
+    ri.iterations = 0; ri.lastRejected = 0; ri.ending = END_NO_ACTIVE_EDGE; ri.rejected = 0;
     int nActive = 0;
     for (int i = 0; i < P.n; i++) nActive += P.level[i] == 0;
     if (nActive == 0) return -1;                          // no active vertex: "0 vertices to optimize"
     double lambda = 0, x[6] = {0, 0, 0, 0, 0, 0};
     int ni = 2, nBad = 0;
+    ri.ending = END_TEN_ITERATIONS;
     for (int it = 0; it < 10; it++) {
         ri.iterations++;
         double currentChi = active_chi(P, est);
@@ -307,7 +333,7 @@ int optimize(const Problem& P, SE3& est, SE3& errPose, RoundInfo& ri)
         build_system(P, est, H, b);
         if (it == 0) {
             double md = 0;
-            for (int j = 0; j < 6; j++) md = std::max(std::fabs(H[j][j]), md);
+            for (int j = 0; j < 6; j++) md = lambdaInitSkipsNaN ? std::fmax(std::fabs(H[j][j]), md) : std::max(std::fabs(H[j][j]), md);
             lambda = 1e-5 * md; ni = 2; nBad = 0;
         }
         double rho = 0;
@@ -341,12 +367,13 @@ int optimize(const Problem& P, SE3& est, SE3& errPose, RoundInfo& ri)
                 ni *= 2;
                 est = backup;
                 ri.lastRejected = 1;
+                ri.rejected++;
             }
             qmax++;
         } while (rho < 0 && qmax < 10);
-        if (qmax == 10 || rho == 0) break;               // Terminate
+        if (qmax == 10 || rho == 0) { ri.ending = qmax == 10 ? END_QMAX : END_RHO_ZERO; break; }      // Terminate
         if ((iniChi - currentChi) * 1e3 < iniChi) nBad++; else nBad = 0;
-        if (nBad >= 3) break;
+        if (nBad >= 3) { ri.ending = END_NSTOP; break; }
     }
     return ri.iterations;
 }
@@ -355,7 +382,10 @@ int optimize(const Problem& P, SE3& est, SE3& errPose, RoundInfo& ri)
 
 // mode bit 0..7 = options of PoseOptimization (0 = the reference; the others are VARIANTS the tests use to show that a quirk matters):
 //   1: classification recomputes every error at the final estimate (no stale cache)   2: no restart from the input pose per round
-//   4: stereo invz in f64
+//   4: stereo invz in f64   8: computeLambdaInit takes the maximum with fmax (skips a NaN diagonal; the reference's std::max does not)
+//   VARIANTS of the classification, for showing which crafted case notices them: 16: chi2 >= threshold   32: the compare in f64
+//   128 / 512 / 1024: the i = 0 / 1 / 2 branch of Quaterniond(Matrix3d) negates w   (option 1 doubles as the variant "est where the
+//   reference reads errPose")
 // mode 256: per-edge evaluation instead of a solve: pose = aux[0..6] (qx qy qz qw tx ty tz), delta = aux[7..12]; writes for edge i
 //   aux[13 + 21 i ..] = error at exp(delta) * pose (3), Jacobian at pose (3 x 6 row-major); option 4 applies.
 // PoseOptimization: edges [n_edges] in edge order, cam5 = fx fy cx cy mbf, Tcw [16] row-major in/out (untouched when < 3 edges),
@@ -366,7 +396,8 @@ extern "C" int sd_pose_oracle(int mode, int n_edges, const void* edges, const fl
 {
     const Edge* E = (const Edge*)edges;
     const Cam c = {cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
-    const bool fresh = mode & 1, noRestart = mode & 2, f64z = mode & 4;
+    const bool fresh = mode & 1, noRestart = mode & 2, f64z = mode & 4, lamSkip = mode & 8, geq = mode & 16, cmp64 = mode & 32;
+    g_flipBranch = mode & 128 ? 0 : mode & 512 ? 1 : mode & 1024 ? 2 : -1;
     if (mode & 256) {
         SE3 s;
         s.r = {aux[0], aux[1], aux[2], aux[3]};
@@ -386,6 +417,7 @@ extern "C" int sd_pose_oracle(int mode, int n_edges, const void* edges, const fl
     for (int i = 0; i < n_edges; i++) outlier[i] = 0;     // mvbOutlier[i] = false for every edge
     if (n_edges < 3) return 0;
     const SE3 pose0 = to_se3quat(Tcw);
+    if (g_rep) { g_rep->priorBranch = g_rep->quatBranch; g_rep->priorFlipped = g_rep->wFlipped; }
     SE3 est = pose0;
     uint8_t* level = new uint8_t[n_edges]();
     Problem P{E, n_edges, c, true, f64z, level};
@@ -395,14 +427,23 @@ extern "C" int sd_pose_oracle(int mode, int n_edges, const void* edges, const fl
         if (!noRestart || it == 0) est = pose0;
         SE3 errPose = est;
         RoundInfo ri;
-        optimize(P, est, errPose, ri);
+        optimize(P, est, errPose, ri, lamSkip);
+        if (g_rep) { g_rep->ending[it] = ri.ending; g_rep->rejected[it] = ri.rejected; }
         nBad = 0;
         for (int i = 0; i < n_edges; i++) {               // mono edges, then stereo edges: independent per edge
             double e[3];
             const bool wasOut = outlier[i] != 0;
             const int D = edge_error(E[i], c, (wasOut || fresh) ? est : errPose, e, f64z);
-            const float chi2 = (float)chi2_of(e, D, (double)E[i].inv_sigma2);
-            if (chi2 > (D == 2 ? chi2Mono : chi2Stereo)) { outlier[i] = 1; level[i] = 1; nBad++; }
+            const double chi2d = chi2_of(e, D, (double)E[i].inv_sigma2);
+            const float chi2 = (float)chi2d, thr = D == 2 ? chi2Mono : chi2Stereo;
+            const bool bad = cmp64 ? (geq ? chi2d >= (double)thr : chi2d > (double)thr) : (geq ? chi2 >= thr : chi2 > thr);
+            if (g_rep) {
+                if (!std::isfinite(chi2d)) g_rep->nonFinite = 1;
+                else g_rep->margin = std::min(g_rep->margin, std::fabs(chi2d - (double)thr) / (double)thr);
+                if (wasOut && !bad) g_rep->reentered++;
+                if (it == 3 && wasOut != bad) g_rep->lastRoundChanges++;
+            }
+            if (bad) { outlier[i] = 1; level[i] = 1; nBad++; }
             else { outlier[i] = 0; level[i] = 0; }
         }
         if (it == 2) P.robust = false;
@@ -412,4 +453,25 @@ extern "C" int sd_pose_oracle(int mode, int n_edges, const void* edges, const fl
     delete[] level;
     to_cvmat(est, Tcw);
     return n_edges - nBad;
+}
+
+// The same solve with its path report.  paths [16] int32: 0 Quaterniond(Matrix3d) branch of the prior (0 tr > 0, 1 / 2 / 3 = largest
+// diagonal entry 0 / 1 / 2), 1 normalizeRotation flipped the prior's w, 2 small-angle exp calls, 3 some chi2 was not finite,
+// 4 + 2 r how optimize() ended in round r (0 round not run, 1 ten iterations, 2 qmax == 10, 3 rho == 0, 4 nStop >= 3, 5 no active edge),
+// 5 + 2 r rejected trials of round r, 12 flags that went from outlier to inlier, 13 flags changed by the round without the robust
+// kernel, 14 bit mask of the Quaterniond(Matrix3d) branches exp took.  margin [1]: the smallest |chi2 - thr| / thr of any
+// classification (f64 chi2, finite ones only; DBL_MAX when there was none).
+extern "C" int sd_pose_oracle_paths(int mode, int n_edges, const void* edges, const float* cam5, float* Tcw, uint8_t* outlier, int32_t* stats,
+                                    int32_t* paths, double* margin)
+{
+    Report rep;
+    g_rep = &rep;
+    const int r = sd_pose_oracle(mode, n_edges, edges, cam5, Tcw, outlier, stats, nullptr);
+    g_rep = nullptr;
+    for (int k = 0; k < 16; k++) paths[k] = 0;
+    paths[0] = rep.priorBranch; paths[1] = rep.priorFlipped; paths[2] = rep.smallAngleExp; paths[3] = rep.nonFinite;
+    for (int k = 0; k < 4; k++) { paths[4 + 2 * k] = rep.ending[k]; paths[5 + 2 * k] = rep.rejected[k]; }
+    paths[12] = rep.reentered; paths[13] = rep.lastRoundChanges; paths[14] = rep.otherBranches;
+    *margin = rep.margin;
+    return r;
 }

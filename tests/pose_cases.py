@@ -11,6 +11,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EDGE_DTYPE = np.dtype([("xw", "<f4", (3,)), ("u", "<f4"), ("v", "<f4"), ("ur", "<f4"), ("inv_sigma2", "<f4"), ("kp_index", "<i4")])
 CAM = dict(fx=np.float32(718.856), fy=np.float32(718.856), cx=np.float32(607.1928), cy=np.float32(185.2157), mbf=np.float32(386.1448))
 MODE_FRESH_ERRORS, MODE_NO_RESTART, MODE_F64_INVZ, MODE_EVAL = 1, 2, 4, 256
+MODE_LAMBDA_FMAX, MODE_GEQ, MODE_F64_COMPARE = 8, 16, 32                              # variants, see tests/cpp/pose_oracle.cpp
+MODE_FLIP_BRANCH = (128, 512, 1024)                                                     # wrong sign of w in the i = 0 / 1 / 2 branch
+QUAT_BRANCHES = ("tr>0", "i=0", "i=1", "i=2")                                            # Quaterniond(Matrix3d)
+ROUND_ENDINGS = ("not_run", "ten_iterations", "qmax==10", "rho==0", "nStop>=3", "no_active_edge")
 
 _oracle = None
 
@@ -24,6 +28,7 @@ def oracle():
                                os.path.join(ROOT, "tests", "cpp", "pose_oracle.cpp")])
         L = C.CDLL(so)
         L.sd_pose_oracle.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.sd_pose_oracle_paths.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 7
         _oracle = L
     return _oracle
 
@@ -44,6 +49,25 @@ def optimize(edges, cam, Tcw, mode=0):
     st = np.zeros(13, np.int32)
     r = oracle().sd_pose_oracle(mode, len(e), _p(e), _p(cam5(cam)), _p(T), _p(out), _p(st), None)
     return r, T.reshape(4, 4), out[:len(e)], st
+
+
+def optimize_paths(edges, cam, Tcw, mode=0):
+    """optimize() with the path report: (return value, Tcw, outlier, stats, paths).  paths: quat (the prior's Quaterniond(Matrix3d)
+    branch, of QUAT_BRANCHES), w_flip, small_exp (small-angle exp calls), non_finite (some chi2 was inf or NaN), endings (per round run,
+    of ROUND_ENDINGS), rejected (trials per round run), reentered (flags that went from outlier to inlier), last_round_changes (flags
+    the round without the robust kernel changed), exp_quat (branches the quaternion of an exp took), margin (the smallest
+    |chi2 - thr| / thr of any classification)."""
+    e = np.ascontiguousarray(edges, EDGE_DTYPE)
+    T = np.ascontiguousarray(np.array(Tcw, np.float32).reshape(16))
+    out = np.full(max(len(e), 1), 7, np.uint8)
+    st = np.zeros(13, np.int32); pa = np.zeros(16, np.int32); mg = np.zeros(1, np.float64)
+    r = oracle().sd_pose_oracle_paths(mode, len(e), _p(e), _p(cam5(cam)), _p(T), _p(out), _p(st), _p(pa), _p(mg))
+    rounds = int(st[0])
+    paths = dict(quat=QUAT_BRANCHES[pa[0]] if pa[0] >= 0 else None, w_flip=bool(pa[1]), small_exp=int(pa[2]), non_finite=bool(pa[3]),
+                 endings=[ROUND_ENDINGS[pa[4 + 2 * k]] for k in range(rounds)], rejected=[int(pa[5 + 2 * k]) for k in range(rounds)],
+                 reentered=int(pa[12]), last_round_changes=int(pa[13]),
+                 exp_quat=[QUAT_BRANCHES[b] for b in range(4) if pa[14] >> b & 1], margin=float(mg[0]))
+    return r, T.reshape(4, 4), out[:len(e)], st, paths
 
 
 def evaluate(edges, cam, q, t, delta, mode=0):

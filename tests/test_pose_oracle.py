@@ -85,7 +85,8 @@ def test_classification_after_a_rejected_last_trial():
     edges' cached _error, and the inlier classification reads that cache (Optimizer.cc:380-395).  The oracle (and the kernel) keep the
     pose of the last error pass for this.  What this case shows is only that a round does end on a rejected trial; it does NOT show a
     classification that differs from fresh errors: after the lambda escalation that rejected step is ~2^-45 of the first, and no case
-    tried made the two differ, so the quirk is reproduced but not covered by a differing case."""
+    tried made the two differ; the case that does differ has a point on the camera plane and lives in
+    pose_crafted.py (depth_zero_mono, test_pose_crafted.py)."""
     rng = np.random.default_rng(2)
     e, T, bad = pc.make_problem(rng, 60, "mixed", 0.2, noise=1.0)
     T0 = pc.perturb(T, rng, 10.0, 0.5)
