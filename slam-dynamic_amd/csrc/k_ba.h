@@ -55,50 +55,16 @@ struct SdBaArgs {
 #define SD_BA_MARK(ph) do { if (A.prof) { __syncthreads(); if (tid == 0) { const long long t_ = wall_clock64(); A.prof[(size_t)blockIdx.x * SD_BA_PHASES + (ph)] += t_ - profT; profT = t_; } } } while (0)
 
 namespace sdba {
-using sdpose::block_sum;
-using sdpose::Q;
 using sdpose::T;
-
-__device__ __forceinline__ double block_max(double x, double* red)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) x = fmax(x, __shfl_xor(x, o, 64));
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    __syncthreads();
-    if (lane == 0) red[wave] = x;
-    __syncthreads();
-    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-}
+typedef sd_se3_cam Cam;
 
 __device__ __forceinline__ T load_pose(const double* p) { T s; s.r.x = p[0]; s.r.y = p[1]; s.r.z = p[2]; s.r.w = p[3]; s.t0 = p[4]; s.t1 = p[5]; s.t2 = p[6]; return s; }
 __device__ __forceinline__ void store_pose(double* p, const T& s) { p[0] = s.r.x; p[1] = s.r.y; p[2] = s.r.z; p[3] = s.r.w; p[4] = s.t0; p[5] = s.t1; p[6] = s.t2; }
 
-struct Cam { double fx, fy, cx, cy, bf; };
-
-// computeError of either two-vertex edge; D = 2 (mono, ur < 0) or 3 (stereo: invz rounded to f32, types_six_dof_expmap.cpp:188-195)
+// computeError of either two-vertex edge at the stored pose and point
 __device__ __forceinline__ int err(const sd_ba_edge& E, const Cam& c, const double* pose, const double* X, double (&r)[3], double (&p)[3])
 {
-    const T s = load_pose(pose);
-    sdpose::rot(s.r, X[0], X[1], X[2], p[0], p[1], p[2]);
-    p[0] = p[0] + s.t0; p[1] = p[1] + s.t1; p[2] = p[2] + s.t2;
-    if (E.ur < 0) {
-        r[0] = (double)E.u - ((p[0] / p[2]) * c.fx + c.cx);
-        r[1] = (double)E.v - ((p[1] / p[2]) * c.fy + c.cy);
-        r[2] = 0.0;
-        return 2;
-    }
-    const double iz = (double)(float)(1.0 / p[2]);
-    const double r0 = p[0] * iz * c.fx + c.cx;
-    r[0] = (double)E.u - r0;
-    r[1] = (double)E.v - (p[1] * iz * c.fy + c.cy);
-    r[2] = (double)E.ur - (r0 - c.bf * iz);
-    return 3;
-}
-__device__ __forceinline__ double chi2(const double (&r)[3], int D, double w)
-{
-    double s = r[0] * (w * r[0]) + r[1] * (w * r[1]);
-    if (D == 3) s = s + r[2] * (w * r[2]);
-    return s;
+    return sd_se3_error(load_pose(pose), c, X[0], X[1], X[2], E.u, E.v, E.ur, r, p);
 }
 __device__ __forceinline__ Cam cam_of(const sd_ba_keyframe& k) { return {(double)k.fx, (double)k.fy, (double)k.cx, (double)k.cy, (double)k.mbf}; }
 
@@ -124,10 +90,8 @@ __device__ __forceinline__ void wave_lds_sync()
 __device__ __noinline__ void edge_record(bool robust, int D, const Cam& c, double wgt, double rho1, const double (&r)[3], const double (&p)[3],
                                          const double* pose, double* o)
 {
-    const Q q = load_pose(pose).r;
-    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z, twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x, tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    const double R[3][3] = {{1 - (tyy + tzz), txy - twz, txz + twy}, {txy + twz, 1 - (txx + tzz), tyz - twx}, {txz - twy, tyz + twx, 1 - (txx + tyy)}};
+    double R[3][3];
+    sd_quat_matrix(load_pose(pose).r, R);
     const double x = p[0], y = p[1], z = p[2], z_2 = z * z;
     double Ja[3][3], Jb[3][6];
     if (D == 2) {
@@ -282,10 +246,13 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
     // ---- estimates: Converter::toSE3Quat(GetPose()), toVector3d(GetWorldPos())
     for (int k = tid; k < nKF; k += SD_BA_THREADS) {
         const float* Tq = KF[k].Tcw;
+        // sd_se3_of(Tq), spelled out: through the call the kernel comes out 8 bytes shorter here, which moves every loop of the trial
+        // off the addresses it is measured at (profiles/lm_shared_math.txt)
+        const double R0[3][3] ={{Tq[0], Tq[1], Tq[2]}, {Tq[4], Tq[5], Tq[6]}, {Tq[8], Tq[9], Tq[10]}};
         T s;
-        s.r = sdpose::quat_of(Tq[0], Tq[1], Tq[2], Tq[4], Tq[5], Tq[6], Tq[8], Tq[9], Tq[10]);
+        s.r = sd_quat_of(R0);
         s.t0 = Tq[3]; s.t1 = Tq[7]; s.t2 = Tq[11];
-        sdpose::renorm(s.r);
+        sd_quat_renorm(s.r);
         store_pose(est + 7 * k, s);
         kfStart[k] = 0;
     }
@@ -336,7 +303,7 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
         __syncthreads();
         double na[1] = {0.0};
         for (int i = tid; i < nE; i += SD_BA_THREADS) if (!level[i]) { kfAct[E[i].kf] = 1; ptAct[E[i].point] = 1; na[0] += 1.0; }
-        block_sum<1>(na, red);
+        sd_block_sum<1>(na, red);
         if (tid == 0) {
             int n = 0;
             for (int k = 0; k < nKF; k++) { const bool fixed = k >= nL || KF[k].fixed; if (kfAct[k] && !fixed) { poseIdx[k] = n; poseKf[n] = k; n++; } else poseIdx[k] = -1; }
@@ -360,17 +327,14 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
                 const Cam c = cam_of(KF[ed.kf]);
                 double r[3], p[3];
                 const int D = err(ed, c, est + 7 * ed.kf, X + 3 * ed.point, r, p);
-                const double wgt = (double)ed.inv_sigma2, c2 = chi2(r, D, wgt);
+                const double wgt = (double)ed.inv_sigma2, c2 = sd_se3_chi2(r, D, wgt);
                 chi2c[i] = c2;
                 double rho0 = c2, rho1 = 1.0;
-                if (robust) {
-                    const double delta = D == 2 ? dM : dS, dsqr = delta * delta;
-                    if (!(c2 <= dsqr)) { const double sq = sqrt(c2); rho0 = 2 * sq * delta - dsqr; rho1 = delta / sq; }
-                }
+                if (robust) sd_huber(c2, D == 2 ? dM : dS, rho0, rho1);
                 cs[0] += rho0;
                 edge_record(robust, D, c, wgt, rho1, r, p, est + 7 * ed.kf, rec + (size_t)SD_BA_REC * i);
             }
-            block_sum<1>(cs, red);                                           // (its barriers also publish the records)
+            sd_block_sum<1>(cs, red);                                          // (its barriers also publish the records)
             currentChi = cs[0];
             const double iniChi = currentChi;
             // ---- gather: pose blocks a wave each, point blocks a lane each
@@ -386,13 +350,7 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
 #pragma unroll
                     for (int j = 0; j < 27; j++) v[j] += o[j];
                 }
-#pragma unroll
-                for (int j = 0; j < 27; j++) {
-                    double x = v[j];
-#pragma unroll
-                    for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-                    v[j] = x;
-                }
+                sd_wave_sum<27>(v);
                 if (lane < 36) {
                     const int a = lane / 6, b = lane % 6, idx = a >= b ? a * (a + 1) / 2 + b : b * (b + 1) / 2 + a;
                     double x = 0.0;
@@ -430,7 +388,7 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
                 for (int i = tid; i < n6; i += SD_BA_THREADS) md = fmax(fabs(Hpp[36 * (i / 6) + 7 * (i % 6)]), md);
                 for (int p = tid; p < nPt; p += SD_BA_THREADS)
                     if (ptAct[p]) md = fmax(fmax(fabs(Hll[6 * p]), fabs(Hll[6 * p + 2])), fmax(fabs(Hll[6 * p + 5]), md));
-                md = block_max(md, red);
+                md = sd_block_max(md, red);
                 lambda = 1e-5 * md; ni = 2; nStop = 0;
             }
             double rho = 0.0;
@@ -615,13 +573,10 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
                     const sd_ba_edge ed = E[i];
                     double r[3], p[3];
                     const int D = err(ed, cam_of(KF[ed.kf]), est + 7 * ed.kf, X + 3 * ed.point, r, p);
-                    const double c2 = chi2(r, D, (double)ed.inv_sigma2);
+                    const double c2 = sd_se3_chi2(r, D, (double)ed.inv_sigma2);
                     chi2c[i] = c2;
-                    double rho0 = c2;
-                    if (robust) {
-                        const double delta = D == 2 ? dM : dS, dsqr = delta * delta;
-                        if (!(c2 <= dsqr)) rho0 = 2 * sqrt(c2) * delta - dsqr;
-                    }
+                    double rho0 = c2, rho1;
+                    if (robust) sd_huber(c2, D == 2 ? dM : dS, rho0, rho1);
                     tc[0] += rho0;
                 }
                 for (int i = tid; i < n6; i += SD_BA_THREADS) tc[1] += xp[i] * (lambda * xp[i] + bp[i]);
@@ -630,7 +585,7 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
 #pragma unroll
                         for (int j = 0; j < 3; j++) tc[1] += xl[3 * p + j] * (lambda * xl[3 * p + j] + bl[3 * p + j]);
                     }
-                block_sum<2>(tc, red);
+                sd_block_sum<2>(tc, red);
                 SD_BA_MARK(5);
                 const double tempChi = ok2 ? tc[0] : 1.7976931348623157e308;
                 rho = currentChi - tempChi;
@@ -664,14 +619,14 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
                 const sd_ba_edge ed = E[i];
                 const T s = load_pose(est + 7 * ed.kf);
                 double p0, p1, p2;
-                sdpose::rot(s.r, X[3 * ed.point], X[3 * ed.point + 1], X[3 * ed.point + 2], p0, p1, p2);
+                sd_quat_rot(s.r, X[3 * ed.point], X[3 * ed.point + 1], X[3 * ed.point + 2], p0, p1, p2);
                 p2 = p2 + s.t2;
                 const bool out = chi2c[i] > (ed.ur < 0 ? 5.991 : 7.815) || !(p2 > 0.0);
                 level[i] = out ? 1 : 0;
                 A.level1[(size_t)P.e0 + i] = out ? 1 : 0;
                 nb1[0] += out ? 1.0 : 0.0;
             }
-            block_sum<1>(nb1, red);
+            sd_block_sum<1>(nb1, red);
             nLevel1 = (int)nb1[0];
         }
     }
@@ -683,14 +638,14 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
             const sd_ba_edge ed = E[i];
             const T s = load_pose(est + 7 * ed.kf);
             double p0, p1, p2;
-            sdpose::rot(s.r, X[3 * ed.point], X[3 * ed.point + 1], X[3 * ed.point + 2], p0, p1, p2);
+            sd_quat_rot(s.r, X[3 * ed.point], X[3 * ed.point + 1], X[3 * ed.point + 2], p0, p1, p2);
             p2 = p2 + s.t2;
             const bool out = chi2c[i] > (ed.ur < 0 ? 5.991 : 7.815) || !(p2 > 0.0);
             A.erase[(size_t)P.e0 + i] = out ? 1 : 0;
             level[i] = out ? 1 : 0;                                          // reused below: 1 = erased
             ne[0] += out ? 1.0 : 0.0;
         }
-        block_sum<1>(ne, red);
+        sd_block_sum<1>(ne, red);
         nErased = (int)ne[0];
     }
     // ---- outputs: Converter::toCvMat(SE3Quat) of the local keyframes, the points in f32; a no-op problem hands its input back
@@ -701,12 +656,11 @@ __global__ void __launch_bounds__(SD_BA_THREADS) k_local_ba(SdBaArgs A)
             for (int j = 0; j < 16; j++) To[j] = KF[k].Tcw[j];
         } else {
             const T s = load_pose(est + 7 * k);
-            const Q& r = s.r;
-            const double tx = 2 * r.x, ty = 2 * r.y, tz = 2 * r.z, twx = tx * r.w, twy = ty * r.w, twz = tz * r.w;
-            const double txx = tx * r.x, txy = ty * r.x, txz = tz * r.x, tyy = ty * r.y, tyz = tz * r.y, tzz = tz * r.z;
-            To[0] = (float)(1 - (tyy + tzz)); To[1] = (float)(txy - twz); To[2] = (float)(txz + twy); To[3] = (float)s.t0;
-            To[4] = (float)(txy + twz); To[5] = (float)(1 - (txx + tzz)); To[6] = (float)(tyz - twx); To[7] = (float)s.t1;
-            To[8] = (float)(txz - twy); To[9] = (float)(tyz + twx); To[10] = (float)(1 - (txx + tyy)); To[11] = (float)s.t2;
+            double R[3][3];
+            sd_quat_matrix(s.r, R);
+            To[0] = (float)R[0][0]; To[1] = (float)R[0][1]; To[2] = (float)R[0][2]; To[3] = (float)s.t0;
+            To[4] = (float)R[1][0]; To[5] = (float)R[1][1]; To[6] = (float)R[1][2]; To[7] = (float)s.t1;
+            To[8] = (float)R[2][0]; To[9] = (float)R[2][1]; To[10] = (float)R[2][2]; To[11] = (float)s.t2;
             To[12] = 0.f; To[13] = 0.f; To[14] = 0.f; To[15] = 1.f;
         }
     }

@@ -26,18 +26,6 @@ struct SdSim3OptArgs {
 
 namespace sds3o {
 
-template <int K>
-__device__ __forceinline__ void wave_sum(double (&v)[K])
-{
-#pragma unroll
-    for (int k = 0; k < K; k++) {
-        double x = v[k];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) x += __shfl_xor(x, o, 64);
-        v[k] = x;
-    }
-}
-
 __device__ __forceinline__ int wave_count(bool pred) { return __popcll(__ballot(pred)); }
 
 struct Pt { double X1, Y1, Z1, X2, Y2, Z2, u1, v1, u2, v2, w1, w2; };
@@ -66,13 +54,13 @@ __device__ __forceinline__ double robust_chi2(const sd_sim3_opt_corr* corr, cons
         const Pt p = load(corr[i], Q.P);
         double e0, e1, r0, r1;
         sd_s3_error(S, c1, p.X2, p.Y2, p.Z2, p.u1, p.v1, e0, e1);
-        sd_s3_huber(sd_s3_chi2(e0, e1, p.w1), delta, r0, r1);
+        sd_huber(sd_s3_chi2(e0, e1, p.w1), delta, r0, r1);
         tc[0] += r0;
         sd_s3_error(Si, c2, p.X1, p.Y1, p.Z1, p.u2, p.v2, e0, e1);
-        sd_s3_huber(sd_s3_chi2(e0, e1, p.w2), delta, r0, r1);
+        sd_huber(sd_s3_chi2(e0, e1, p.w2), delta, r0, r1);
         tc[0] += r0;
     }
-    wave_sum<1>(tc);
+    sd_wave_sum<1>(tc);
     return tc[0];
 }
 
@@ -99,7 +87,7 @@ __global__ void __launch_bounds__(64) k_sim3_optimize(SdSim3OptArgs A)
         for (int i = 0; i < 3; i++)
 #pragma unroll
             for (int j = 0; j < 3; j++) R[i][j] = (double)P.R12[i * 3 + j];
-        sd_s3_quat_of(R, prior);
+        prior.r = sd_quat_of(R);
         prior.t0 = (double)P.t12[0]; prior.t1 = (double)P.t12[1]; prior.t2 = (double)P.t12[2];
         prior.s = (double)P.s12;
     }
@@ -148,7 +136,7 @@ __global__ void __launch_bounds__(64) k_sim3_optimize(SdSim3OptArgs A)
                     sd_s3_error(inv, c2, p.X1, p.Y1, p.Z1, p.u2, p.v2, b0, b1);
                     sd_s3_accumulate(b0, b1, J21, p.w2, delta, v);
                 }
-                wave_sum<36>(v);
+                sd_wave_sum<36>(v);
                 errEst = est;
                 double currentChi = v[35];
                 const double iniChi = currentChi;
@@ -226,16 +214,14 @@ __global__ void __launch_bounds__(64) k_sim3_optimize(SdSim3OptArgs A)
         r.ret = ret; r.n_correspondences = n; r.n_bad = nBad; r.more_iterations = more;
         r.iterations[0] = its[0]; r.iterations[1] = its[1]; r.trials[0] = trials[0]; r.trials[1] = trials[1];
         r.stop[0] = stop[0]; r.stop[1] = stop[1]; r.written = written; r.reserved = 0;
-        r.q[0] = o.qx; r.q[1] = o.qy; r.q[2] = o.qz; r.q[3] = o.qw; r.t[0] = o.t0; r.t[1] = o.t1; r.t[2] = o.t2; r.s = o.s;
+        r.q[0] = o.r.x; r.q[1] = o.r.y; r.q[2] = o.r.z; r.q[3] = o.r.w; r.t[0] = o.t0; r.t[1] = o.t1; r.t[2] = o.t2; r.s = o.s;
         // Converter::toCvSE3(s * R, t) with R = Quaterniond::toRotationMatrix()
-        const double tx = 2 * o.qx, ty = 2 * o.qy, tz = 2 * o.qz;
-        const double twx = tx * o.qw, twy = ty * o.qw, twz = tz * o.qw, txx = tx * o.qx, txy = ty * o.qx, txz = tz * o.qx;
-        const double tyy = ty * o.qy, tyz = tz * o.qy, tzz = tz * o.qz;
-        const double R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+        double R[3][3];
+        sd_quat_matrix(o.r, R);
 #pragma unroll
         for (int i = 0; i < 3; i++) {
 #pragma unroll
-            for (int j = 0; j < 3; j++) r.T12[i * 4 + j] = (float)(o.s * R[i * 3 + j]);
+            for (int j = 0; j < 3; j++) r.T12[i * 4 + j] = (float)(o.s * R[i][j]);
         }
         r.T12[3] = (float)o.t0; r.T12[7] = (float)o.t1; r.T12[11] = (float)o.t2;
         r.T12[12] = 0.f; r.T12[13] = 0.f; r.T12[14] = 0.f; r.T12[15] = 1.f;

@@ -145,20 +145,18 @@ __global__ void __launch_bounds__(256) k_refine_finish(SdRefineArgs A)
         r.ran = run ? 1 : 0; r.matched = (run && O.ret >= 20) ? 1 : 0; r.n_built = O.n_correspondences; r.reserved = 0;
         // g2o::Sim3 gSmw(Converter::toMatrix3d(pKF->GetRotation()), Converter::toVector3d(pKF->GetTranslation()), 1.0); mg2oScw = gScm * gSmw
         sd_s3 gScm, gSmw;
-        gScm.qx = O.q[0]; gScm.qy = O.q[1]; gScm.qz = O.q[2]; gScm.qw = O.q[3]; gScm.t0 = O.t[0]; gScm.t1 = O.t[1]; gScm.t2 = O.t[2]; gScm.s = O.s;
+        gScm.r.x = O.q[0]; gScm.r.y = O.q[1]; gScm.r.z = O.q[2]; gScm.r.w = O.q[3]; gScm.t0 = O.t[0]; gScm.t1 = O.t[1]; gScm.t2 = O.t[2]; gScm.s = O.s;
         double Rm[3][3];
         for (int i = 0; i < 3; i++)
             for (int j = 0; j < 3; j++) Rm[i][j] = (double)J.T2[4 * i + j];
-        sd_s3_quat_of(Rm, gSmw);
+        gSmw.r = sd_quat_of(Rm);
         gSmw.t0 = (double)J.T2[3]; gSmw.t1 = (double)J.T2[7]; gSmw.t2 = (double)J.T2[11]; gSmw.s = 1.0;
         const sd_s3 S = sd_s3_mul(gScm, gSmw);
-        r.Scw_q[0] = S.qx; r.Scw_q[1] = S.qy; r.Scw_q[2] = S.qz; r.Scw_q[3] = S.qw; r.Scw_t[0] = S.t0; r.Scw_t[1] = S.t1; r.Scw_t[2] = S.t2; r.Scw_s = S.s;
-        const double tx = 2 * S.qx, ty = 2 * S.qy, tz = 2 * S.qz;
-        const double twx = tx * S.qw, twy = ty * S.qw, twz = tz * S.qw, txx = tx * S.qx, txy = ty * S.qx, txz = tz * S.qx;
-        const double tyy = ty * S.qy, tyz = tz * S.qy, tzz = tz * S.qz;
-        const double Rq[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+        r.Scw_q[0] = S.r.x; r.Scw_q[1] = S.r.y; r.Scw_q[2] = S.r.z; r.Scw_q[3] = S.r.w; r.Scw_t[0] = S.t0; r.Scw_t[1] = S.t1; r.Scw_t[2] = S.t2; r.Scw_s = S.s;
+        double Rq[3][3];
+        sd_quat_matrix(S.r, Rq);
         for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) r.Scw[i * 4 + j] = (float)(S.s * Rq[i * 3 + j]);       // Converter::toCvMat(g2o::Sim3)
+            for (int j = 0; j < 3; j++) r.Scw[i * 4 + j] = (float)(S.s * Rq[i][j]);            // Converter::toCvMat(g2o::Sim3)
         r.Scw[3] = (float)S.t0; r.Scw[7] = (float)S.t1; r.Scw[11] = (float)S.t2;
         r.Scw[12] = 0.f; r.Scw[13] = 0.f; r.Scw[14] = 0.f; r.Scw[15] = 1.f;
         r.opt = O;

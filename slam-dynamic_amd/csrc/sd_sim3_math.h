@@ -1,18 +1,23 @@
 // The arithmetic of Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241) that both the kernel (k_sim3_opt.h) and the CPU oracle
 // (tests/cpp/sim3_opt_oracle.cpp) must evaluate to the same bits: g2o's Sim3 (types/sim3.h), VertexSim3Expmap::oplusImpl, the two
-// projection edges' computeError (types_seven_dof_expmap.h:130-171), the robustified quadratic form of one edge
-// (base_binary_edge.hpp:54-120) and the dense pivoted LDL^T of LinearSolverDense.
+// projection edges' computeError (types_seven_dof_expmap.h:130-171) and the robustified quadratic form of one edge
+// (base_binary_edge.hpp:54-120).  What Sim3 shares with the SE3 solvers (the quaternion, Huber, the dense pivoted LDL^T of
+// LinearSolverDense) is sd_g2o_math.h.
 // The edges have no analytic Jacobian, so g2o differentiates them numerically with delta = 1e-9: a one-ulp difference in an error is
 // a 1e-5 difference in J.  Hence ONE header, plain f64 + - * / sqrt and explicit fma only (all correctly rounded on x86 and gfx950),
 // compiled without contraction on either side, and private sin / cos / exp built from those operations (DESIGN Q45).
 #pragma once
-#if !defined(__HIPCC__)
-#include <cmath>
-using std::sqrt;
-#endif
-#include "sd_trig.h"
+#include "sd_g2o_math.h"
 
-struct sd_s3 { double qx, qy, qz, qw, t0, t1, t2, s; };          // g2o::Sim3: r (Eigen coefficient order x y z w), t, s
+// g2o::Sim3: r, t, s.  The rotation is the shared sd_quat; qx .. qw name the same four doubles (two layout-compatible structs in
+// a union, read through either), which is how the oracle spells them.
+struct sd_s3 { union { sd_quat r; struct { double qx, qy, qz, qw; }; }; double t0, t1, t2, s; };
+
+// the shared functions under the names the oracle calls them by
+SD_HD void sd_s3_quat_of(const double (&m)[3][3], sd_s3& o) { o.r = sd_quat_of(m); }
+SD_HD void sd_s3_huber(double e, double delta, double& rho0, double& rho1) { sd_huber(e, delta, rho0, rho1); }
+template <int N>
+SD_HD bool sd_s3_solve(const double* H, const double* b, double lambda, double (&x)[N]) { return sd_ldlt_solve<N>(H, b, lambda, x); }
 
 // sin and cos of x >= 0 (an update's rotation angle): the quadrant reduction and fdlibm kernels of sd_cos_sin_f32, kept in f64.
 // Within 1 ulp of glibc on [1e-5, 8] (tests/cpp/sim3_math_check.cpp); beyond 1e9, or not finite: NaN.
@@ -61,59 +66,19 @@ SD_HD double sd_s3_exp(double x)
     return (y * sd_s3_pow2(k1)) * sd_s3_pow2(k - k1);
 }
 
-SD_HD void sd_s3_quat_of(const double (&m)[3][3], sd_s3& o)       // Eigen::Quaterniond(const Matrix3d&)
-{
-    const double tr = m[0][0] + m[1][1] + m[2][2];
-    int i = 0;
-    if (m[1][1] > m[0][0]) i = 1;
-    if (m[2][2] > (i == 1 ? m[1][1] : m[0][0])) i = 2;
-    if (tr > 0) {
-        double t = sqrt(tr + 1.0);
-        o.qw = 0.5 * t;
-        t = 0.5 / t;
-        o.qx = (m[2][1] - m[1][2]) * t; o.qy = (m[0][2] - m[2][0]) * t; o.qz = (m[1][0] - m[0][1]) * t;
-    } else if (i == 2) {
-        double t = sqrt(m[2][2] - m[0][0] - m[1][1] + 1.0);
-        o.qz = 0.5 * t;
-        t = 0.5 / t;
-        o.qw = (m[1][0] - m[0][1]) * t; o.qx = (m[0][2] + m[2][0]) * t; o.qy = (m[1][2] + m[2][1]) * t;
-    } else if (i == 1) {
-        double t = sqrt(m[1][1] - m[2][2] - m[0][0] + 1.0);
-        o.qy = 0.5 * t;
-        t = 0.5 / t;
-        o.qw = (m[0][2] - m[2][0]) * t; o.qz = (m[2][1] + m[1][2]) * t; o.qx = (m[0][1] + m[1][0]) * t;
-    } else {
-        double t = sqrt(m[0][0] - m[1][1] - m[2][2] + 1.0);
-        o.qx = 0.5 * t;
-        t = 0.5 / t;
-        o.qw = (m[2][1] - m[1][2]) * t; o.qy = (m[1][0] + m[0][1]) * t; o.qz = (m[2][0] + m[0][2]) * t;
-    }
-}
-
-SD_HD void sd_s3_rot(double qx, double qy, double qz, double qw, double v0, double v1, double v2, double& o0, double& o1, double& o2)
-{                                                                // Quaterniond * Vector3d
-    double u0 = qy * v2 - qz * v1, u1 = qz * v0 - qx * v2, u2 = qx * v1 - qy * v0;
-    u0 = u0 + u0; u1 = u1 + u1; u2 = u2 + u2;
-    const double c0 = qy * u2 - qz * u1, c1 = qz * u0 - qx * u2, c2 = qx * u1 - qy * u0;
-    o0 = v0 + qw * u0 + c0; o1 = v1 + qw * u1 + c1; o2 = v2 + qw * u2 + c2;
-}
-
 SD_HD void sd_s3_map(const sd_s3& S, double x, double y, double z, double& o0, double& o1, double& o2)      // s * (r * xyz) + t
 {
     double r0, r1, r2;
-    sd_s3_rot(S.qx, S.qy, S.qz, S.qw, x, y, z, r0, r1, r2);
+    sd_quat_rot(S.r, x, y, z, r0, r1, r2);
     o0 = S.s * r0 + S.t0; o1 = S.s * r1 + S.t1; o2 = S.s * r2 + S.t2;
 }
 
 SD_HD sd_s3 sd_s3_mul(const sd_s3& a, const sd_s3& b)           // Sim3::operator* (no renormalisation)
 {
     sd_s3 r;
-    r.qw = a.qw * b.qw - a.qx * b.qx - a.qy * b.qy - a.qz * b.qz;
-    r.qx = a.qw * b.qx + a.qx * b.qw + a.qy * b.qz - a.qz * b.qy;
-    r.qy = a.qw * b.qy + a.qy * b.qw + a.qz * b.qx - a.qx * b.qz;
-    r.qz = a.qw * b.qz + a.qz * b.qw + a.qx * b.qy - a.qy * b.qx;
+    r.r = sd_quat_mul(a.r, b.r);
     double p0, p1, p2;
-    sd_s3_rot(a.qx, a.qy, a.qz, a.qw, b.t0, b.t1, b.t2, p0, p1, p2);
+    sd_quat_rot(a.r, b.t0, b.t1, b.t2, p0, p1, p2);
     r.t0 = a.s * p0 + a.t0; r.t1 = a.s * p1 + a.t1; r.t2 = a.s * p2 + a.t2;
     r.s = a.s * b.s;
     return r;
@@ -122,9 +87,9 @@ SD_HD sd_s3 sd_s3_mul(const sd_s3& a, const sd_s3& b)           // Sim3::operato
 SD_HD sd_s3 sd_s3_inverse(const sd_s3& a)                       // Sim3(r.conjugate(), r.conjugate() * ((-1. / s) * t), 1. / s)
 {
     sd_s3 r;
-    r.qx = -a.qx; r.qy = -a.qy; r.qz = -a.qz; r.qw = a.qw;
+    r.r.x = -a.r.x; r.r.y = -a.r.y; r.r.z = -a.r.z; r.r.w = a.r.w;
     const double m = -1. / a.s;
-    sd_s3_rot(r.qx, r.qy, r.qz, r.qw, m * a.t0, m * a.t1, m * a.t2, r.t0, r.t1, r.t2);
+    sd_quat_rot(r.r, m * a.t0, m * a.t1, m * a.t2, r.t0, r.t1, r.t2);
     r.s = 1. / a.s;
     return r;
 }
@@ -175,7 +140,7 @@ SD_HD sd_s3 sd_s3_exp_update(const double (&u)[7], int& branch)
             B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
         }
     }
-    sd_s3_quat_of(R, S);
+    S.r = sd_quat_of(R);
     double W[3][3];
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) W[i][j] = (A * O[i][j] + B * O2[i][j]) + C * (i == j ? 1.0 : 0.0);
@@ -220,20 +185,12 @@ SD_HD double sd_s3_chi2(double e0, double e1, double w)
     return e0 * (w * e0 + 0.0 * e1) + e1 * (0.0 * e0 + w * e1);
 }
 
-// RobustKernelHuber::robustify: rho[0], rho[1]
-SD_HD void sd_s3_huber(double e, double delta, double& rho0, double& rho1)
-{
-    const double dsqr = delta * delta;
-    if (e <= dsqr) { rho0 = e; rho1 = 1.; }
-    else { const double sq = sqrt(e); rho0 = 2 * sq * delta - dsqr; rho1 = delta / sq; }
-}
-
 // One edge's share of the 7x7 system (constructQuadraticForm's robust branch, the Sim3 vertex being the only free one):
 // v[0..27] += lower triangle of J^T (rho1 w I) J row by row, v[28..34] += J^T (rho1 * -(w I) e), v[35] += rho0.
 SD_HD void sd_s3_accumulate(double e0, double e1, const double (&J)[2][7], double w, double delta, double (&v)[36])
 {
     double rho0, rho1;
-    sd_s3_huber(sd_s3_chi2(e0, e1, w), delta, rho0, rho1);
+    sd_huber(sd_s3_chi2(e0, e1, w), delta, rho0, rho1);
     const double wo = rho1 * w;
     double r0 = -(w * e0 + 0.0 * e1), r1 = -(0.0 * e0 + w * e1);
     r0 = r0 * rho1; r1 = r1 * rho1;
@@ -255,98 +212,4 @@ SD_HD double sd_s3_good_step_scale(double rho)
     return 1. / 3. > alpha ? 1. / 3. : alpha;                    // (std::max)(_goodStepLowerScale, alpha)
 }
 
-// (H + lambda I) x = b by Eigen::LDLT's pivoted LDL^T (lower storage), k_pose.h's solve6 for 7 unknowns; returns isPositive().
-// x keeps its value when not positive.  H holds the lower triangle row by row (so the first N rows of a larger one serve as well).
-template <int N>
-SD_HD bool sd_s3_solve(const double* H, const double* b, double lambda, double (&x)[N])
-{
-    double A[N][N];
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int j = 0; j < N; j++) A[i][j] = j <= i ? H[i * (i + 1) / 2 + j] : 0.0;
-#pragma unroll
-    for (int i = 0; i < N; i++) A[i][i] += lambda;
-    int tr[N];
-    int sign = 0;                                                // 0 zero, 1 positive semi-definite, 2 negative semi-definite, 3 indefinite
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        int p = k;
-        double big = A[k][k] < 0 ? -A[k][k] : A[k][k];
-#pragma unroll
-        for (int i = k + 1; i < N; i++) { const double a = A[i][i] < 0 ? -A[i][i] : A[i][i]; if (a > big) { big = a; p = i; } }
-        tr[k] = p;
-#pragma unroll
-        for (int q = k + 1; q < N; q++) {                        // every index a compile-time constant after unrolling
-            if (p == q) {
-                double t;
-#pragma unroll
-                for (int j = 0; j < k; j++) { t = A[k][j]; A[k][j] = A[q][j]; A[q][j] = t; }
-                t = A[k][k]; A[k][k] = A[q][q]; A[q][q] = t;
-#pragma unroll
-                for (int i = k + 1; i < q; i++) { t = A[i][k]; A[i][k] = A[q][i]; A[q][i] = t; }
-#pragma unroll
-                for (int i = q + 1; i < N; i++) { t = A[i][k]; A[i][k] = A[i][q]; A[i][q] = t; }
-            }
-        }
-        if (k > 0) {
-            double tmp[N];
-#pragma unroll
-            for (int j = 0; j < k; j++) tmp[j] = A[j][j] * A[k][j];
-            double s = A[k][0] * tmp[0];
-#pragma unroll
-            for (int j = 1; j < k; j++) s = s + A[k][j] * tmp[j];
-            A[k][k] -= s;
-#pragma unroll
-            for (int i = k + 1; i < N; i++) {
-                double r = A[i][0] * tmp[0];
-#pragma unroll
-                for (int j = 1; j < k; j++) r = r + A[i][j] * tmp[j];
-                A[i][k] -= r;
-            }
-        }
-        const double akk = A[k][k];
-        if ((akk < 0 ? -akk : akk) > 0) {
-#pragma unroll
-            for (int i = k + 1; i < N; i++) A[i][k] /= akk;
-        }
-        if (sign == 1) { if (akk < 0) sign = 3; }
-        else if (sign == 2) { if (akk > 0) sign = 3; }
-        else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = 2; }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double y[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) y[i] = b[i];
-#pragma unroll
-    for (int k = 0; k < N; k++)
-#pragma unroll
-        for (int q = k + 1; q < N; q++)
-            if (tr[k] == q) { const double t = y[k]; y[k] = y[q]; y[q] = t; }
-#pragma unroll
-    for (int i = 1; i < N; i++) {
-        double s = A[i][0] * y[0];
-#pragma unroll
-        for (int j = 1; j < i; j++) s = s + A[i][j] * y[j];
-        y[i] -= s;
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) { const double a = A[i][i] < 0 ? -A[i][i] : A[i][i]; y[i] = a > 2.2250738585072014e-308 ? y[i] / A[i][i] : 0.0; }
-#pragma unroll
-    for (int i = N - 2; i >= 0; i--) {
-        double s = A[i + 1][i] * y[i + 1];
-#pragma unroll
-        for (int j = i + 2; j < N; j++) s = s + A[j][i] * y[j];
-        y[i] -= s;
-    }
-#pragma unroll
-    for (int k = N - 1; k >= 0; k--)
-#pragma unroll
-        for (int q = k + 1; q < N; q++)
-            if (tr[k] == q) { const double t = y[k]; y[k] = y[q]; y[q] = t; }
-#pragma unroll
-    for (int i = 0; i < N; i++) x[i] = y[i];
-    return true;
-}
-
-SD_HD bool sd_s3_solve7(const double* H, const double* b, double lambda, double (&x)[7]) { return sd_s3_solve<7>(H, b, lambda, x); }
+SD_HD bool sd_s3_solve7(const double* H, const double* b, double lambda, double (&x)[7]) { return sd_ldlt_solve<7>(H, b, lambda, x); }
