@@ -93,6 +93,83 @@ static int sd_grow(hipStream_t prev, hipStream_t s, size_t& cap, int* jobs, size
 }
 #define SD_MAX_ENTRIES ((size_t)INT_MAX)      // entry tables are addressed through int32 offsets
 
+// ---- THE process-wide state of the stateless solver entry points (sd_pose_optimize_*, sd_local_ba_*, sd_sim3_ransac_*,
+// sd_sim3_optimize_*, sd_pnp_ransac_* and the PnP stage of sd_batch_relocalize_pnp): per solver one SdDeviceTable of a state made of an
+// SdTableRing and, where the kernels need scratch memory, an SdWorkspace.  These tables follow the largest call EXACTLY (no doubling as in
+// sd_grow: the footprint of a process is the largest call's) and wait on events, not on streams: successive calls may use any streams.
+#define SD_SOLVER_RING 8
+#define SD_SOLVER_MAX_DEVICES 64
+
+// One State per device behind one mutex per solver.  The array is never destroyed: no device call after the runtime has shut down at exit.
+template <typename State>
+struct SdDeviceTable {
+    State* const states = new State[SD_SOLVER_MAX_DEVICES];
+    std::mutex mu;
+    struct Locked { std::unique_lock<std::mutex> lk; State* st = nullptr; int device = 0; State* operator->() const { return st; } };
+    // the state of the current device, the table locked for as long as `out` lives
+    int lock(const char* who, Locked& out)
+    {
+        HIPCHK(hipGetDevice(&out.device));
+        if (out.device < 0 || out.device >= SD_SOLVER_MAX_DEVICES)
+            return set_err(SD_ERR_UNSUPPORTED, std::string(who) + ": device index beyond the solver tables");
+        out.lk = std::unique_lock<std::mutex>(mu);
+        out.st = states + out.device;
+        return SD_OK;
+    }
+};
+
+// The host rows of a call (cameras, problem records) reach its kernels through a ring of SD_SOLVER_RING library-owned device tables, so
+// that the host waits only when the call SD_SOLVER_RING calls earlier on the same device has not finished yet.  stage(): the slot `next`
+// waits for the event of the call that last used it (created on first use), is regrown to exactly n rows when it is smaller (cap 0 while
+// it is freed) and receives the rows on `s`.  publish(), after the call's last launch: records the event on `s` and only then advances,
+// so a call that fails in between leaves `next` where it was and the next call stages the same slot again.
+template <typename T>
+struct SdTableRing {
+    SdDevBuf<T> d[SD_SOLVER_RING]; size_t cap[SD_SOLVER_RING] = {}; hipEvent_t done[SD_SOLVER_RING] = {}; int next = 0;
+    int stage(const T* rows, size_t n, hipStream_t s, const T*& table)
+    {
+        const int k = next;
+        if (done[k]) HIPCHK(hipEventSynchronize(done[k]));     // the launch that last used this table has read it
+        else HIPCHK(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+        if (cap[k] < n) { cap[k] = 0; HIPCHK(d[k].alloc(n * sizeof(T))); cap[k] = n; }
+        HIPCHK(hipMemcpyAsync(d[k], rows, n * sizeof(T), hipMemcpyHostToDevice, s));
+        table = d[k];
+        return SD_OK;
+    }
+    int publish(hipStream_t s)
+    {
+        HIPCHK(hipEventRecord(done[next], s));
+        next = (next + 1) % SD_SOLVER_RING;
+        return SD_OK;
+    }
+};
+
+// The grow-only scratch arrays the calls of one solver on one device share, behind ONE event recorded after the last launch that used
+// them.  enter(): a call that has to grow an array waits for that launch on the host (the arrays are about to be freed), any other call
+// makes its stream wait.  grow(): a group of arrays that share a cap goes to exactly `need` units, the cap 0 while they are freed: a
+// non-zero cap never stands over a freed array.  leave(): records.  wait(): the host waits for the last call (sd_local_ba_profile).
+struct SdWorkspace {
+    hipEvent_t done = nullptr;
+    int enter(hipStream_t s, bool grows)
+    {
+        if (!done) HIPCHK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        else if (grows) HIPCHK(hipEventSynchronize(done));
+        else HIPCHK(hipStreamWaitEvent(s, done, 0));
+        return SD_OK;
+    }
+    static int grow(size_t& cap, size_t need, std::initializer_list<SdGrowArray> arrays)
+    {
+        if (cap >= need) return SD_OK;
+        cap = 0;
+        for (const SdGrowArray& a : arrays) HIPCHK(a.buf->alloc(need * a.unit));
+        cap = need;
+        return SD_OK;
+    }
+    int leave(hipStream_t s) { HIPCHK(hipEventRecord(done, s)); return SD_OK; }
+    int wait() { HIPCHK(hipEventSynchronize(done)); return SD_OK; }
+};
+#define SD_TRY(call) do { int rc_ = (call); if (rc_ != SD_OK) return rc_; } while (0)
+
 struct sd_batch {
     std::vector<SdPyrTiles> pyrTiles;      // per level: tile grid of k_pyr_level_tiles
     SdDevBuf<int> d_pyrExt;
@@ -703,7 +780,7 @@ static int check_offsets(const char* who, const int32_t* off, int n, int* maxLen
 {
     bool ok = off[0] == 0;
     int longest = 0;
-    for (int j = 0; j < n && ok; j++) { ok = off[j + 1] >= off[j]; longest = std::max(longest, off[j + 1] - off[j]); }
+    for (int j = 0; j < n && ok; j++) { ok = off[j + 1] >= off[j]; if (ok) longest = std::max(longest, off[j + 1] - off[j]); }
     if (!ok) return set_err(SD_ERR_INVALID, std::string(who) + ": offsets must start at 0 and ascend");
     if (maxLen) *maxLen = longest;
     return SD_OK;
@@ -2343,15 +2420,9 @@ int sd_batch_download_matches(sd_batch* b, int pair, int32_t* match, int32_t* pa
 
 
 // ---------------------------------------------------------------- Optimizer::PoseOptimization (k_pose.h)
-// Plain form: the caller's edges.  The cameras travel through a per-device ring of SD_POSE_CAM_RING library-owned device tables; an
-// event recorded after each launch guards the reuse of its table, so the host waits only when the launch SD_POSE_CAM_RING calls
-// earlier on the same device has not finished yet.
-#define SD_POSE_CAM_RING 8
-#define SD_POSE_MAX_DEVICES 64
+// Plain form: the caller's edges.  The cameras travel through an SdTableRing.
 namespace {
-struct PoseCamRing { SdDevBuf<sd_camera> d[SD_POSE_CAM_RING]; size_t cap[SD_POSE_CAM_RING] = {}; hipEvent_t done[SD_POSE_CAM_RING] = {}; int next = 0; };
-PoseCamRing* const g_poseCams = new PoseCamRing[SD_POSE_MAX_DEVICES];     // never destroyed: no device call after the runtime has shut down at exit
-std::mutex g_poseCamsMu;
+SdDeviceTable<SdTableRing<sd_camera>> g_poseCams;
 }
 
 static int pose_launch(const SdPoseArgs& A, int n, hipStream_t s)
@@ -2368,28 +2439,14 @@ int sd_pose_optimize_device(int n_problems, const int32_t* d_edge_offset, const 
         return set_err(SD_ERR_INVALID, "bad pose_optimize arguments");
     if (n_problems == 0) return SD_OK;
     hipStream_t s = (hipStream_t)stream_;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the pose camera tables");
-    std::lock_guard<std::mutex> lk(g_poseCamsMu);
-    PoseCamRing& C = g_poseCams[dev];
-    const int k = C.next;
-    if (C.done[k]) HIPCHK(hipEventSynchronize(C.done[k]));     // the launch that last used this table has read it
-    else HIPCHK(hipEventCreateWithFlags(&C.done[k], hipEventDisableTiming));
-    if (C.cap[k] < (size_t)n_problems) {
-        C.cap[k] = 0;
-        HIPCHK(C.d[k].alloc((size_t)n_problems * sizeof(sd_camera)));
-        C.cap[k] = (size_t)n_problems;
-    }
-    HIPCHK(hipMemcpyAsync(C.d[k], cams, (size_t)n_problems * sizeof(sd_camera), hipMemcpyHostToDevice, s));
+    decltype(g_poseCams)::Locked C;
+    SD_TRY(g_poseCams.lock("pose_optimize", C));
     SdPoseArgs A;
-    A.edges = d_edges; A.first = d_edge_offset; A.last = d_edge_offset + 1; A.cam = C.d[k]; A.Tcw = d_Tcw; A.outlier = d_outlier;
+    SD_TRY(C->stage(cams, (size_t)n_problems, s, A.cam));
+    A.edges = d_edges; A.first = d_edge_offset; A.last = d_edge_offset + 1; A.Tcw = d_Tcw; A.outlier = d_outlier;
     A.nGood = d_n_good; A.map = nullptr;
-    int rc = pose_launch(A, n_problems, s);
-    if (rc != SD_OK) return rc;
-    HIPCHK(hipEventRecord(C.done[k], s));
-    C.next = (k + 1) % SD_POSE_CAM_RING;
-    return SD_OK;
+    SD_TRY(pose_launch(A, n_problems, s));
+    return C->publish(s);
 }
 
 int sd_pose_optimize_host(int n_problems, const int32_t* edge_offset, const sd_pose_edge* edges, const sd_camera* cams,
@@ -2397,11 +2454,11 @@ int sd_pose_optimize_host(int n_problems, const int32_t* edge_offset, const sd_p
 {
     if (n_problems < 0 || (n_problems > 0 && (!edge_offset || !cams || !Tcw || !n_good))) return set_err(SD_ERR_INVALID, "bad pose_optimize arguments");
     if (n_problems == 0) return SD_OK;
-    if (edge_offset[0] != 0) return set_err(SD_ERR_INVALID, "edge_offset[0] must be 0");
-    for (int p = 0; p < n_problems; p++) if (edge_offset[p + 1] < edge_offset[p]) return set_err(SD_ERR_INVALID, "edge offsets must not decrease");
+    int rc = check_offsets("pose_optimize", edge_offset, n_problems, nullptr);
+    if (rc != SD_OK) return rc;
     const size_t nE = (size_t)edge_offset[n_problems];
     if (nE > 0 && (!edges || !outlier)) return set_err(SD_ERR_INVALID, "bad pose_optimize arguments");
-    int rc = require_device();
+    rc = require_device();
     if (rc != SD_OK) return rc;
     SdDevBuf<int32_t> d_off, d_g; SdDevBuf<sd_pose_edge> d_e; SdDevBuf<float> d_T; SdDevBuf<uint8_t> d_o;
     HIPCHK(d_off.alloc((size_t)(n_problems + 1) * 4)); HIPCHK(d_e.alloc(std::max<size_t>(nE, 1) * sizeof(sd_pose_edge)));
@@ -2422,16 +2479,14 @@ int sd_pose_optimize_host(int n_problems, const int32_t* edge_offset, const sd_p
 static_assert(sizeof(sd_ba_keyframe) == 88 && sizeof(sd_ba_edge) == 32 && sizeof(sd_ba_stats) == 48, "local BA records");
 static_assert(SD_BA_MAX_LOCAL == SD_BA_MAX_LOCAL_KEYFRAMES && SD_BA_MAX_FIXED == SD_BA_MAX_FIXED_KEYFRAMES &&
               SD_BA_MAX_POINTS == SD_BA_MAX_POINTS_PER_PROBLEM && SD_BA_MAX_EDGES == SD_BA_MAX_EDGES_PER_PROBLEM, "local BA caps");
-#define SD_BA_RING 8
 namespace {
 struct BaState {
-    SdDevBuf<SdBaProblem> prob[SD_BA_RING]; size_t probCap[SD_BA_RING] = {}; hipEvent_t done[SD_BA_RING] = {}; int next = 0;
-    SdDevBuf<double> wsD; SdDevBuf<int> wsI; size_t capD = 0, capI = 0; hipEvent_t wsDone = nullptr;
+    SdTableRing<SdBaProblem> prob;
+    SdWorkspace ws; SdDevBuf<double> wsD; SdDevBuf<int> wsI; size_t capD = 0, capI = 0;
     SdDevBuf<long long> prof; size_t capProf = 0; int profProblems = 0;      // the last profiled call
 };
-BaState* const g_ba = new BaState[SD_POSE_MAX_DEVICES];       // never destroyed, as g_poseCams
-std::mutex g_baMu;
-bool g_baProfiling = false;
+SdDeviceTable<BaState> g_ba;
+bool g_baProfiling = false;       // under g_ba.mu
 }
 static_assert(SD_BA_PHASES == SD_BA_PROFILE_PHASES, "local BA phases");
 
@@ -2440,17 +2495,16 @@ static int ba_plan(int n, const int32_t* kfOff, const int32_t* nLocal, const int
                    size_t& needD, size_t& needI, int& maxLocal)
 {
     if (!kfOff || !nLocal || !ptOff || !eOff) return set_err(SD_ERR_INVALID, "bad local_ba arguments");
-    if (kfOff[0] != 0 || ptOff[0] != 0 || eOff[0] != 0) return set_err(SD_ERR_INVALID, "local_ba offsets must start at 0");
+    for (const int32_t* off : {kfOff, ptOff, eOff}) SD_TRY(check_offsets("local_ba", off, n, nullptr));
     tab.resize(n);
     needD = needI = 0; maxLocal = 0;
     for (int p = 0; p < n; p++) {
-        const long long nk = (long long)kfOff[p + 1] - kfOff[p], np = (long long)ptOff[p + 1] - ptOff[p], ne = (long long)eOff[p + 1] - eOff[p];
-        if (nk < 0 || np < 0 || ne < 0) return set_err(SD_ERR_INVALID, "local_ba offsets must not decrease");
+        const int nk = kfOff[p + 1] - kfOff[p], np = ptOff[p + 1] - ptOff[p], ne = eOff[p + 1] - eOff[p];
         if (nLocal[p] < 0 || nLocal[p] > nk) return set_err(SD_ERR_INVALID, "n_local outside the problem's keyframes");
         if (nLocal[p] > SD_BA_MAX_LOCAL || nk - nLocal[p] > SD_BA_MAX_FIXED || np > SD_BA_MAX_POINTS || ne > SD_BA_MAX_EDGES)
             return set_err(SD_ERR_INVALID, "local_ba problem " + std::to_string(p) + " is over the caps (64 local / 128 fixed keyframes, 8192 points, 65536 edges)");
         SdBaProblem& q = tab[p];
-        q.kf0 = kfOff[p]; q.nKF = (int)nk; q.nLocal = nLocal[p]; q.pt0 = ptOff[p]; q.nPt = (int)np; q.e0 = eOff[p]; q.nE = (int)ne; q.pad = 0;
+        q.kf0 = kfOff[p]; q.nKF = nk; q.nLocal = nLocal[p]; q.pt0 = ptOff[p]; q.nPt = np; q.e0 = eOff[p]; q.nE = ne; q.pad = 0;
         q.wsD = needD; q.wsI = needI;
         needD += (sd_ba_ws_doubles(nk, nLocal[p], np, ne) + 1) & ~(size_t)1;
         needI += (sd_ba_ws_ints(nk, nLocal[p], np, ne) + 3) & ~(size_t)3;
@@ -2477,47 +2531,32 @@ int sd_local_ba_device(int n_problems, const int32_t* kf_offset, const int32_t* 
         (anyE && (!d_edges || !d_level1 || !d_erase)))
         return set_err(SD_ERR_INVALID, "bad local_ba arguments");
     hipStream_t s = (hipStream_t)stream_;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the local_ba tables");
-    std::lock_guard<std::mutex> lk(g_baMu);
-    BaState& B = g_ba[dev];
-    const int k = B.next;
-    if (B.done[k]) HIPCHK(hipEventSynchronize(B.done[k]));
-    else HIPCHK(hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
-    if (B.probCap[k] < (size_t)n_problems) {
-        B.probCap[k] = 0;
-        HIPCHK(B.prob[k].alloc((size_t)n_problems * sizeof(SdBaProblem)));
-        B.probCap[k] = (size_t)n_problems;
-    }
-    if (!B.wsDone) HIPCHK(hipEventCreateWithFlags(&B.wsDone, hipEventDisableTiming));
-    else if (B.capD < needD || B.capI < needI) HIPCHK(hipEventSynchronize(B.wsDone));     // growing: the last launch must be done with it
-    else HIPCHK(hipStreamWaitEvent(s, B.wsDone, 0));
-    if (B.capD < needD) { B.capD = 0; HIPCHK(B.wsD.alloc(needD * sizeof(double))); B.capD = needD; }
-    if (B.capI < needI) { B.capI = 0; HIPCHK(B.wsI.alloc(needI * sizeof(int))); B.capI = needI; }
-    HIPCHK(hipMemcpyAsync(B.prob[k], tab.data(), (size_t)n_problems * sizeof(SdBaProblem), hipMemcpyHostToDevice, s));
+    decltype(g_ba)::Locked B;
+    SD_TRY(g_ba.lock("local_ba", B));
+    SdBaArgs A;
+    SD_TRY(B->prob.stage(tab.data(), (size_t)n_problems, s, A.prob));
+    const size_t needProf = g_baProfiling ? (size_t)n_problems * SD_BA_PHASES : 0;      // (the wait of enter() also covers the previous call's use of `prof`)
+    SD_TRY(B->ws.enter(s, B->capD < needD || B->capI < needI || B->capProf < needProf));
+    SD_TRY(SdWorkspace::grow(B->capD, needD, {{&B->wsD, sizeof(double)}}));
+    SD_TRY(SdWorkspace::grow(B->capI, needI, {{&B->wsI, sizeof(int)}}));
+    SD_TRY(SdWorkspace::grow(B->capProf, needProf, {{&B->prof, sizeof(long long)}}));
     const int lds = (int)sd_ba_lds_bytes(maxLocal);
     HIPCHK(sd_raise_lds_limit((const void*)k_local_ba, lds));
-    SdBaArgs A;
-    A.prob = B.prob[k]; A.kfs = d_kfs; A.xw = d_xw; A.edges = d_edges; A.refKf = d_ref_kf; A.Tcw = d_Tcw; A.xwOut = d_xw_out; A.normal = d_normal;
-    A.dist = d_dist; A.level1 = d_level1; A.erase = d_erase; A.stats = d_stats; A.wsD = B.wsD; A.wsI = B.wsI; A.prof = nullptr;
-    if (g_baProfiling) {                                       // (the wait on wsDone above also covers the previous call's use of `prof`)
-        const size_t need = (size_t)n_problems * SD_BA_PHASES;
-        if (B.capProf < need) { HIPCHK(hipEventSynchronize(B.wsDone)); B.capProf = 0; HIPCHK(B.prof.alloc(need * sizeof(long long))); B.capProf = need; }
-        HIPCHK(hipMemsetAsync(B.prof, 0, need * sizeof(long long), s));
-        A.prof = B.prof; B.profProblems = n_problems;
+    A.kfs = d_kfs; A.xw = d_xw; A.edges = d_edges; A.refKf = d_ref_kf; A.Tcw = d_Tcw; A.xwOut = d_xw_out; A.normal = d_normal;
+    A.dist = d_dist; A.level1 = d_level1; A.erase = d_erase; A.stats = d_stats; A.wsD = B->wsD; A.wsI = B->wsI; A.prof = nullptr;
+    if (needProf) {
+        HIPCHK(hipMemsetAsync(B->prof, 0, needProf * sizeof(long long), s));
+        A.prof = B->prof; B->profProblems = n_problems;
     }
     hipLaunchKernelGGL(k_local_ba, dim3(n_problems), dim3(SD_BA_THREADS), lds, s, A);
     LAUNCH_CHECK("k_local_ba");
-    HIPCHK(hipEventRecord(B.done[k], s));
-    HIPCHK(hipEventRecord(B.wsDone, s));
-    B.next = (k + 1) % SD_BA_RING;
-    return SD_OK;
+    SD_TRY(B->ws.leave(s));
+    return B->prob.publish(s);
 }
 
 int sd_local_ba_set_profiling(int on)
 {
-    std::lock_guard<std::mutex> lk(g_baMu);
+    std::lock_guard<std::mutex> lk(g_ba.mu);
     g_baProfiling = on != 0;
     return SD_OK;
 }
@@ -2525,18 +2564,15 @@ int sd_local_ba_set_profiling(int on)
 int sd_local_ba_profile(int n_problems, double* ms)
 {
     if (!ms) return set_err(SD_ERR_INVALID, "bad local_ba_profile arguments");
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the local_ba tables");
-    std::lock_guard<std::mutex> lk(g_baMu);
-    BaState& B = g_ba[dev];
-    if (B.profProblems == 0 || !B.wsDone) return set_err(SD_ERR_STATE, "no profiled sd_local_ba_device call on this device");
-    if (n_problems != B.profProblems) return set_err(SD_ERR_INVALID, "n_problems is not that of the last profiled call");
-    HIPCHK(hipEventSynchronize(B.wsDone));
+    decltype(g_ba)::Locked B;
+    SD_TRY(g_ba.lock("local_ba_profile", B));
+    if (B->profProblems == 0) return set_err(SD_ERR_STATE, "no profiled sd_local_ba_device call on this device");      // else ws has its event
+    if (n_problems != B->profProblems) return set_err(SD_ERR_INVALID, "n_problems is not that of the last profiled call");
+    SD_TRY(B->ws.wait());
     std::vector<long long> t((size_t)n_problems * SD_BA_PHASES);
-    HIPCHK(hipMemcpy(t.data(), B.prof, t.size() * sizeof(long long), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(t.data(), B->prof, t.size() * sizeof(long long), hipMemcpyDeviceToHost));
     int khz = 0;
-    HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev));
+    HIPCHK(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, B.device));
     if (khz <= 0) return set_err(SD_ERR_UNSUPPORTED, "the device reports no wall-clock rate");
     for (size_t i = 0; i < t.size(); i++) ms[i] = (double)t[i] / (double)khz;
     return SD_OK;
@@ -2599,14 +2635,12 @@ static_assert(sizeof(SdSim3Pt) == 48 && sizeof(SdSim3Hyp) == 192 && sizeof(SdSim
 static_assert(SD_SIM3_MAX_N == SD_SIM3_MAX_CORRESPONDENCES && SD_SIM3_MAX_ITS == SD_SIM3_MAX_ITERATIONS, "sim3 caps");
 static_assert(SD_SIM3_MAX_N < (1 << 15) && SD_SIM3_MAX_ITS < (1 << 16), "a (count, iteration) key is 32 bits");
 static_assert(SD_SIM3_MAX_PROBLEMS <= 65535, "a problem is a grid row");
-#define SD_SIM3_RING 8
 namespace {
 struct Sim3State {
-    SdDevBuf<SdSim3Prob> prob[SD_SIM3_RING]; size_t probCap[SD_SIM3_RING] = {}; hipEvent_t done[SD_SIM3_RING] = {}; int next = 0;
-    SdDevBuf<SdSim3Pt> pts; SdDevBuf<SdSim3Hyp> hyp; SdDevBuf<int> count; size_t capPts = 0, capHyp = 0; hipEvent_t wsDone = nullptr;
+    SdTableRing<SdSim3Prob> prob;
+    SdWorkspace ws; SdDevBuf<SdSim3Pt> pts; SdDevBuf<SdSim3Hyp> hyp; SdDevBuf<int> count; size_t capPts = 0, capHyp = 0;
 };
-Sim3State* const g_sim3 = new Sim3State[SD_POSE_MAX_DEVICES];       // never destroyed, as g_poseCams
-std::mutex g_sim3Mu;
+SdDeviceTable<Sim3State> g_sim3;
 }
 
 // Sim3Solver::SetRansacParameters (Sim3Solver.cc:114-138) as written; the double is clamped before the conversion to int so that no
@@ -2632,16 +2666,15 @@ static int sim3_plan(int n, const int32_t* off, const sd_sim3_problem* problems,
     if (minInliers < 0) return set_err(SD_ERR_INVALID, "sim3_ransac min_inliers must not be negative");
     if (maxIterations < 1 || maxIterations > SD_SIM3_MAX_ITS) return set_err(SD_ERR_INVALID, "sim3_ransac max_iterations outside [1, 4096]");
     if (n > SD_SIM3_MAX_PROBLEMS) return set_err(SD_ERR_INVALID, "sim3_ransac: more than 65535 problems in one call");
-    if (off[0] != 0) return set_err(SD_ERR_INVALID, "sim3_ransac corr_offset[0] must be 0");
+    SD_TRY(check_offsets("sim3_ransac", off, n, nullptr));
     tab.resize(n);
     nHyp = 0; maxN = 0; maxIts = 0;
     for (int p = 0; p < n; p++) {
-        const long long N = (long long)off[p + 1] - off[p];
-        if (N < 0) return set_err(SD_ERR_INVALID, "sim3_ransac offsets must not decrease");
+        const int N = off[p + 1] - off[p];
         if (N > SD_SIM3_MAX_N) return set_err(SD_ERR_INVALID, "sim3_ransac problem " + std::to_string(p) + " holds more than 4096 correspondences");
         SdSim3Prob& q = tab[p];
-        q.P = problems[p]; q.c0 = off[p]; q.n = (int)N; q.minInliers = minInliers; q.pad[0] = q.pad[1] = 0;
-        q.ransacMaxIts = sim3_max_its(probability, minInliers, maxIterations, (int)N);
+        q.P = problems[p]; q.c0 = off[p]; q.n = N; q.minInliers = minInliers; q.pad[0] = q.pad[1] = 0;
+        q.ransacMaxIts = sim3_max_its(probability, minInliers, maxIterations, N);
         q.maxIts = (N < minInliers || N < 3) ? 0 : q.ransacMaxIts;
         q.h0 = (int)nHyp;
         nHyp += (size_t)q.maxIts;
@@ -2668,32 +2701,15 @@ int sd_sim3_ransac_device(int n_problems, const int32_t* corr_offset, const sd_s
         for (int p = 0; p < n_problems; p++)
             max_its_out[p] = tab[p].ransacMaxIts;
     hipStream_t s = (hipStream_t)stream_;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the sim3 tables");
-    std::lock_guard<std::mutex> lk(g_sim3Mu);
-    Sim3State& B = g_sim3[dev];
-    const int k = B.next;
-    if (B.done[k]) HIPCHK(hipEventSynchronize(B.done[k]));
-    else HIPCHK(hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
-    if (B.probCap[k] < (size_t)n_problems) {
-        B.probCap[k] = 0;
-        HIPCHK(B.prob[k].alloc((size_t)n_problems * sizeof(SdSim3Prob)));
-        B.probCap[k] = (size_t)n_problems;
-    }
-    const size_t needPts = std::max<size_t>(nC, 1), needHyp = std::max<size_t>(nHyp, 1);
-    if (!B.wsDone) HIPCHK(hipEventCreateWithFlags(&B.wsDone, hipEventDisableTiming));
-    else if (B.capPts < needPts || B.capHyp < needHyp) HIPCHK(hipEventSynchronize(B.wsDone));   // growing: the last launch must be done with it
-    else HIPCHK(hipStreamWaitEvent(s, B.wsDone, 0));
-    if (B.capPts < needPts) { B.capPts = 0; HIPCHK(B.pts.alloc(needPts * sizeof(SdSim3Pt))); B.capPts = needPts; }
-    if (B.capHyp < needHyp) {
-        B.capHyp = 0;
-        HIPCHK(B.hyp.alloc(needHyp * sizeof(SdSim3Hyp))); HIPCHK(B.count.alloc(needHyp * sizeof(int)));
-        B.capHyp = needHyp;
-    }
-    HIPCHK(hipMemcpyAsync(B.prob[k], tab.data(), (size_t)n_problems * sizeof(SdSim3Prob), hipMemcpyHostToDevice, s));
+    decltype(g_sim3)::Locked B;
+    SD_TRY(g_sim3.lock("sim3_ransac", B));
     SdSim3Args A;
-    A.prob = B.prob[k]; A.corr = d_corr; A.pts = B.pts; A.hyp = B.hyp; A.count = B.count; A.result = d_results; A.inlier = d_inliers;
+    SD_TRY(B->prob.stage(tab.data(), (size_t)n_problems, s, A.prob));
+    const size_t needPts = std::max<size_t>(nC, 1), needHyp = std::max<size_t>(nHyp, 1);
+    SD_TRY(B->ws.enter(s, B->capPts < needPts || B->capHyp < needHyp));
+    SD_TRY(SdWorkspace::grow(B->capPts, needPts, {{&B->pts, sizeof(SdSim3Pt)}}));
+    SD_TRY(SdWorkspace::grow(B->capHyp, needHyp, {{&B->hyp, sizeof(SdSim3Hyp)}, {&B->count, sizeof(int)}}));
+    A.corr = d_corr; A.pts = B->pts; A.hyp = B->hyp; A.count = B->count; A.result = d_results; A.inlier = d_inliers;
     const int rowBlocks = std::max(1, (maxN + 255) / 256);
     if (maxN > 0) {
         hipLaunchKernelGGL(k_sim3_prepare, dim3(rowBlocks, n_problems), dim3(256), 0, s, A);
@@ -2711,10 +2727,8 @@ int sd_sim3_ransac_device(int n_problems, const int32_t* corr_offset, const sd_s
         hipLaunchKernelGGL(k_sim3_inliers, dim3(rowBlocks, n_problems), dim3(256), 0, s, A);
         LAUNCH_CHECK("k_sim3_inliers");
     }
-    HIPCHK(hipEventRecord(B.done[k], s));
-    HIPCHK(hipEventRecord(B.wsDone, s));
-    B.next = (k + 1) % SD_SIM3_RING;
-    return SD_OK;
+    SD_TRY(B->ws.leave(s));
+    return B->prob.publish(s);
 }
 
 int sd_sim3_ransac_host(int n_problems, const int32_t* corr_offset, const sd_sim3_corr* corr, const sd_sim3_problem* problems,

@@ -1,16 +1,23 @@
 // PnPsolver on the device (include/sd_frontend.h, kernels in k_pnp.h, arithmetic in sd_pnp_math.h, DESIGN.md Q46).  Included by
-// sd_api.hip inside its extern "C" block.  Stateless like sd_sim3_ransac_*: the problem table goes through the same kind of ring.
+// sd_api.hip inside its extern "C" block.  Stateless like sd_sim3_ransac_*: the problem table goes through an SdTableRing, the scratch
+// arrays sit behind an SdWorkspace, which sd_pnp_ransac_device shares with the PnP stage of sd_batch_relocalize_pnp.
 static_assert(sizeof(sd_pnp_corr) == 28 && sizeof(sd_pnp_problem) == 32 && sizeof(sd_pnp_result) == 104, "pnp records");
 static_assert(sizeof(SdPnpPt) == 24 && sizeof(SdPnpHyp) == 96 && sizeof(SdPnpProb) == 64, "pnp workspace records");
 static_assert(SD_PNP_MAX_N == SD_PNP_MAX_CORRESPONDENCES && SD_PNP_MAX_ITS == SD_PNP_MAX_ITERATIONS, "pnp caps");
 static_assert(SD_PNP_MAX_PROBLEMS <= 65535, "a problem is a grid row");
 namespace {
 struct PnpState {
-    SdDevBuf<SdPnpProb> prob[SD_SIM3_RING]; size_t probCap[SD_SIM3_RING] = {}; hipEvent_t done[SD_SIM3_RING] = {}; int next = 0;
-    SdDevBuf<SdPnpPt> pts; SdDevBuf<SdPnpHyp> hyp; SdDevBuf<int> count; size_t capPts = 0, capHyp = 0; hipEvent_t wsDone = nullptr;
+    SdTableRing<SdPnpProb> prob;
+    SdWorkspace ws; SdDevBuf<SdPnpPt> pts; SdDevBuf<SdPnpHyp> hyp; SdDevBuf<int> count; size_t capPts = 0, capHyp = 0;
+    // the workspace entered on `s` with room for needPts points and needHyp hypotheses
+    int enter(hipStream_t s, size_t needPts, size_t needHyp)
+    {
+        SD_TRY(ws.enter(s, capPts < needPts || capHyp < needHyp));
+        SD_TRY(SdWorkspace::grow(capPts, needPts, {{&pts, sizeof(SdPnpPt)}}));
+        return SdWorkspace::grow(capHyp, needHyp, {{&hyp, sizeof(SdPnpHyp)}, {&count, sizeof(int)}});
+    }
 };
-PnpState* const g_pnp = new PnpState[SD_POSE_MAX_DEVICES];       // never destroyed, as g_sim3
-std::mutex g_pnpMu;
+SdDeviceTable<PnpState> g_pnp;
 }
 
 // PnPsolver::SetRansacParameters (PnPsolver.cc:121-157) as written: `int nMinInliers = N*epsilon` through float, the epsilon raise,
@@ -45,19 +52,18 @@ static int pnp_plan(int n, const int32_t* off, const sd_pnp_problem* problems, d
     if (!(epsilon > 0.f && epsilon <= 1.f)) return set_err(SD_ERR_INVALID, "pnp_ransac epsilon must lie in (0, 1]");
     if (!(th2 > 0.f)) return set_err(SD_ERR_INVALID, "pnp_ransac th2 must be positive");
     if (n > SD_PNP_MAX_PROBLEMS) return set_err(SD_ERR_INVALID, "pnp_ransac: more than 65535 problems in one call");
-    if (off[0] != 0) return set_err(SD_ERR_INVALID, "pnp_ransac corr_offset[0] must be 0");
+    SD_TRY(check_offsets("pnp_ransac", off, n, nullptr));
     tab.resize(n);
     nHyp = 0; maxN = 0; maxEnd = 0;
     for (int p = 0; p < n; p++) {
-        const long long N = (long long)off[p + 1] - off[p];
-        if (N < 0) return set_err(SD_ERR_INVALID, "pnp_ransac offsets must not decrease");
+        const int N = off[p + 1] - off[p];
         if (N > SD_PNP_MAX_N) return set_err(SD_ERR_INVALID, "pnp_ransac problem " + std::to_string(p) + " holds more than 4096 correspondences");
         const sd_pnp_problem& P = problems[p];
         if (P.start_iteration < 0 || P.n_iterations < 1 || (long long)P.start_iteration + P.n_iterations > SD_PNP_MAX_ITS)
             return set_err(SD_ERR_INVALID, "pnp_ransac problem " + std::to_string(p) + ": start_iteration + n_iterations outside [1, 4096]");
         SdPnpProb& q = tab[p];
-        q.P = P; q.c0 = off[p]; q.n = (int)N; q.th2 = th2; q.pad = 0;
-        pnp_ransac_parameters(probability, minInliers, maxIterations, minSet, epsilon, (int)N, q.minInliers, q.maxIts);
+        q.P = P; q.c0 = off[p]; q.n = N; q.th2 = th2; q.pad = 0;
+        pnp_ransac_parameters(probability, minInliers, maxIterations, minSet, epsilon, N, q.minInliers, q.maxIts);
         q.end = N < q.minInliers ? 0 : std::max(q.maxIts, P.start_iteration + P.n_iterations);
         q.h0 = (int)nHyp;
         nHyp += (size_t)q.end;
@@ -82,33 +88,13 @@ int sd_pnp_ransac_device(int n_problems, const int32_t* corr_offset, const sd_pn
     if (!d_results || (nC && (!d_corr || !d_inliers))) return set_err(SD_ERR_INVALID, "bad pnp_ransac arguments");
     if ((d_counts || d_poses) && counts_stride < maxEnd) return set_err(SD_ERR_INVALID, "pnp_ransac counts_stride is smaller than a problem's iteration count");
     hipStream_t s = (hipStream_t)stream_;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the pnp tables");
     HIPCHK(sd_raise_lds_limit((const void*)k_pnp_hypotheses, SD_PNP_HYP_LDS));
-    std::lock_guard<std::mutex> lk(g_pnpMu);
-    PnpState& B = g_pnp[dev];
-    const int k = B.next;
-    if (B.done[k]) HIPCHK(hipEventSynchronize(B.done[k]));
-    else HIPCHK(hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
-    if (B.probCap[k] < (size_t)n_problems) {
-        B.probCap[k] = 0;
-        HIPCHK(B.prob[k].alloc((size_t)n_problems * sizeof(SdPnpProb)));
-        B.probCap[k] = (size_t)n_problems;
-    }
-    const size_t needPts = std::max<size_t>(nC, 1), needHyp = std::max<size_t>(nHyp, 1);
-    if (!B.wsDone) HIPCHK(hipEventCreateWithFlags(&B.wsDone, hipEventDisableTiming));
-    else if (B.capPts < needPts || B.capHyp < needHyp) HIPCHK(hipEventSynchronize(B.wsDone));   // growing: the last launch must be done with it
-    else HIPCHK(hipStreamWaitEvent(s, B.wsDone, 0));
-    if (B.capPts < needPts) { B.capPts = 0; HIPCHK(B.pts.alloc(needPts * sizeof(SdPnpPt))); B.capPts = needPts; }
-    if (B.capHyp < needHyp) {
-        B.capHyp = 0;
-        HIPCHK(B.hyp.alloc(needHyp * sizeof(SdPnpHyp))); HIPCHK(B.count.alloc(needHyp * sizeof(int)));
-        B.capHyp = needHyp;
-    }
-    HIPCHK(hipMemcpyAsync(B.prob[k], tab.data(), (size_t)n_problems * sizeof(SdPnpProb), hipMemcpyHostToDevice, s));
+    decltype(g_pnp)::Locked B;
+    SD_TRY(g_pnp.lock("pnp_ransac", B));
     SdPnpArgs A;
-    A.prob = B.prob[k]; A.corr = d_corr; A.pts = B.pts; A.hyp = B.hyp; A.count = B.count; A.result = d_results; A.inlier = d_inliers;
+    SD_TRY(B->prob.stage(tab.data(), (size_t)n_problems, s, A.prob));
+    SD_TRY(B->enter(s, std::max<size_t>(nC, 1), std::max<size_t>(nHyp, 1)));
+    A.corr = d_corr; A.pts = B->pts; A.hyp = B->hyp; A.count = B->count; A.result = d_results; A.inlier = d_inliers;
     if (maxN > 0) {
         hipLaunchKernelGGL(k_pnp_prepare, dim3(std::max(1, (maxN + 255) / 256), n_problems), dim3(256), 0, s, A);
         LAUNCH_CHECK("k_pnp_prepare");
@@ -125,10 +111,8 @@ int sd_pnp_ransac_device(int n_problems, const int32_t* corr_offset, const sd_pn
     }
     hipLaunchKernelGGL(k_pnp_refine, dim3(n_problems), dim3(256), 0, s, A);
     LAUNCH_CHECK("k_pnp_refine");
-    HIPCHK(hipEventRecord(B.done[k], s));
-    HIPCHK(hipEventRecord(B.wsDone, s));
-    B.next = (k + 1) % SD_SIM3_RING;
-    return SD_OK;
+    SD_TRY(B->ws.leave(s));
+    return B->prob.publish(s);
 }
 
 int sd_pnp_ransac_host(int n_problems, const int32_t* corr_offset, const sd_pnp_corr* corr, const sd_pnp_problem* problems,
@@ -199,9 +183,6 @@ int sd_batch_relocalize_pnp(sd_batch* b, int n_jobs, const int32_t* frame_index,
     if (cap > SD_PNP_MAX_N) return set_err(SD_ERR_UNSUPPORTED, "relocalize_pnp: more than 4096 keypoints per image");      // a problem's cap; never a truncation
     const size_t J = (size_t)n_jobs, nHyp = J * (size_t)endCap, nPts = J * (size_t)cap;
     if (nHyp > (size_t)0x7FFFFFFF) return set_err(SD_ERR_INVALID, "relocalize_pnp: more than 2^31 hypotheses in one call");
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the pnp tables");
     HIPCHK(sd_raise_lds_limit((const void*)k_pnp_hypotheses, SD_PNP_HYP_LDS));
     hipStream_t s = pick_stream(b, stream_);
     rc = b->reloc.grow(b, s, n_jobs);                              // the slot table is the matcher's, as in the cascade
@@ -217,23 +198,15 @@ int sd_batch_relocalize_pnp(sd_batch* b, int n_jobs, const int32_t* frame_index,
     HIPCHK(hipMemcpyAsync(R.d_table, R.table.data(), ((size_t)cap + 1) * sizeof(int2), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(R.d_in, problems, J * sizeof(sd_pnp_problem), hipMemcpyHostToDevice, s));
     {
-        std::lock_guard<std::mutex> lk(g_pnpMu);
-        PnpState& B = g_pnp[dev];
-        if (!B.wsDone) HIPCHK(hipEventCreateWithFlags(&B.wsDone, hipEventDisableTiming));
-        else if (B.capPts < nPts || B.capHyp < nHyp) HIPCHK(hipEventSynchronize(B.wsDone));       // growing: the last launch must be done with it
-        else HIPCHK(hipStreamWaitEvent(s, B.wsDone, 0));
-        if (B.capPts < nPts) { B.capPts = 0; HIPCHK(B.pts.alloc(nPts * sizeof(SdPnpPt))); B.capPts = nPts; }
-        if (B.capHyp < nHyp) {
-            B.capHyp = 0;
-            HIPCHK(B.hyp.alloc(nHyp * sizeof(SdPnpHyp))); HIPCHK(B.count.alloc(nHyp * sizeof(int)));
-            B.capHyp = nHyp;
-        }
+        decltype(g_pnp)::Locked B;
+        SD_TRY(g_pnp.lock("relocalize_pnp", B));
+        SD_TRY(B->enter(s, nPts, nHyp));
         SdPnpChainArgs G;
         G.kp = KPUN(b); G.count = b->d_count; G.slots = b->reloc.d_slots; G.match = d_bow_match; G.mps = (const SdMapPoint*)d_points; G.nPoints = n_points;
         G.cap = cap; G.in = R.d_in; G.table = R.d_table; G.corr = R.d_corr; G.prob = R.d_prob; G.th2 = th2; G.endCap = endCap; G.row = R.d_row; G.T = R.d_T;
         G.result = R.d_res; G.inlier = R.d_inl;
         SdPnpArgs A;
-        A.prob = R.d_prob; A.corr = R.d_corr; A.pts = B.pts; A.hyp = B.hyp; A.count = B.count; A.result = R.d_res; A.inlier = R.d_inl;
+        A.prob = R.d_prob; A.corr = R.d_corr; A.pts = B->pts; A.hyp = B->hyp; A.count = B->count; A.result = R.d_res; A.inlier = R.d_inl;
         hipLaunchKernelGGL(k_pnp_gather, dim3(n_jobs), dim3(256), 0, s, G, level_tables(b));
         LAUNCH_CHECK("k_pnp_gather");
         hipLaunchKernelGGL(k_pnp_prepare, dim3((cap + 255) / 256, n_jobs), dim3(256), 0, s, A);
@@ -246,7 +219,7 @@ int sd_batch_relocalize_pnp(sd_batch* b, int n_jobs, const int32_t* frame_index,
         LAUNCH_CHECK("k_pnp_refine");
         hipLaunchKernelGGL(k_pnp_handover, dim3(n_jobs), dim3(256), 0, s, G);
         LAUNCH_CHECK("k_pnp_handover");
-        HIPCHK(hipEventRecord(B.wsDone, s));
+        SD_TRY(B->ws.leave(s));
     }
     rc = reloc_refine_run(b, n_jobs, frame_index, kf_index, nullptr, R.d_T, d_kf_point, R.d_row, d_points, d_point_desc, n_points, cam, d_results, s);
     if (rc != SD_OK) return rc;

@@ -1,13 +1,9 @@
 // Optimizer::OptimizeSim3 on the device (include/sd_frontend.h, kernel in k_sim3_opt.h, DESIGN.md Q45).  Included by sd_api.hip inside
-// its extern "C" block.  Stateless like sd_sim3_ransac_*: the problem table goes through the same kind of ring.
+// its extern "C" block.  Stateless like sd_sim3_ransac_*: the problem table goes through an SdTableRing; the kernel needs no workspace.
 static_assert(sizeof(sd_sim3_opt_corr) == 52 && sizeof(sd_sim3_opt_problem) == 220 && sizeof(sd_sim3_opt_result) == 176, "sim3_opt records");
 static_assert(sizeof(SdSim3OptProb) == 228, "sim3_opt problem row");
 namespace {
-struct Sim3OptState {
-    SdDevBuf<SdSim3OptProb> prob[SD_SIM3_RING]; size_t probCap[SD_SIM3_RING] = {}; hipEvent_t done[SD_SIM3_RING] = {}; int next = 0;
-};
-Sim3OptState* const g_sim3Opt = new Sim3OptState[SD_POSE_MAX_DEVICES];      // never destroyed, as g_sim3
-std::mutex g_sim3OptMu;
+SdDeviceTable<SdTableRing<SdSim3OptProb>> g_sim3Opt;
 }
 
 // the host-side checks both entry points share; fills the problem table
@@ -15,11 +11,10 @@ static int sim3_opt_plan(int n, const int32_t* off, const sd_sim3_opt_problem* p
 {
     if (!off || !problems) return set_err(SD_ERR_INVALID, "bad sim3_optimize arguments");
     if (n > SD_SIM3_MAX_PROBLEMS) return set_err(SD_ERR_INVALID, "sim3_optimize: more than 65535 problems in one call");
-    if (off[0] != 0) return set_err(SD_ERR_INVALID, "sim3_optimize corr_offset[0] must be 0");
+    SD_TRY(check_offsets("sim3_optimize", off, n, nullptr));
     tab.resize(n);
     for (int p = 0; p < n; p++) {
-        const long long N = (long long)off[p + 1] - off[p];
-        if (N < 0) return set_err(SD_ERR_INVALID, "sim3_optimize offsets must not decrease");
+        const int N = off[p + 1] - off[p];
         if (N > SD_SIM3_MAX_CORRESPONDENCES)
             return set_err(SD_ERR_INVALID, "sim3_optimize problem " + std::to_string(p) + " holds more than 4096 correspondences");
         const sd_sim3_opt_problem& P = problems[p];
@@ -28,7 +23,7 @@ static int sim3_opt_plan(int n, const int32_t* off, const sd_sim3_opt_problem* p
         for (int k = 0; k < 9; k++) finite = finite && std::isfinite(P.R12[k]);
         for (int k = 0; k < 3; k++) finite = finite && std::isfinite(P.t12[k]);
         if (!finite) return set_err(SD_ERR_INVALID, "sim3_optimize problem " + std::to_string(p) + ": the prior is not finite");
-        tab[p].P = P; tab[p].c0 = off[p]; tab[p].n = (int)N;
+        tab[p].P = P; tab[p].c0 = off[p]; tab[p].n = N;
     }
     return SD_OK;
 }
@@ -44,27 +39,14 @@ int sd_sim3_optimize_device(int n_problems, const int32_t* corr_offset, const sd
     const size_t nC = (size_t)corr_offset[n_problems];
     if (!d_results || (nC && (!d_corr || !d_state))) return set_err(SD_ERR_INVALID, "bad sim3_optimize arguments");
     hipStream_t s = (hipStream_t)stream_;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= SD_POSE_MAX_DEVICES) return set_err(SD_ERR_UNSUPPORTED, "device index beyond the sim3 tables");
-    std::lock_guard<std::mutex> lk(g_sim3OptMu);
-    Sim3OptState& B = g_sim3Opt[dev];
-    const int k = B.next;
-    if (B.done[k]) HIPCHK(hipEventSynchronize(B.done[k]));
-    else HIPCHK(hipEventCreateWithFlags(&B.done[k], hipEventDisableTiming));
-    if (B.probCap[k] < (size_t)n_problems) {
-        B.probCap[k] = 0;
-        HIPCHK(B.prob[k].alloc((size_t)n_problems * sizeof(SdSim3OptProb)));
-        B.probCap[k] = (size_t)n_problems;
-    }
-    HIPCHK(hipMemcpyAsync(B.prob[k], tab.data(), (size_t)n_problems * sizeof(SdSim3OptProb), hipMemcpyHostToDevice, s));
+    decltype(g_sim3Opt)::Locked ring;
+    SD_TRY(g_sim3Opt.lock("sim3_optimize", ring));
     SdSim3OptArgs A;
-    A.prob = B.prob[k]; A.corr = d_corr; A.result = d_results; A.state = d_state;
+    SD_TRY(ring->stage(tab.data(), (size_t)n_problems, s, A.prob));
+    A.corr = d_corr; A.result = d_results; A.state = d_state;
     hipLaunchKernelGGL(k_sim3_optimize, dim3(n_problems), dim3(64), 0, s, A);
     LAUNCH_CHECK("k_sim3_optimize");
-    HIPCHK(hipEventRecord(B.done[k], s));
-    B.next = (k + 1) % SD_SIM3_RING;
-    return SD_OK;
+    return ring->publish(s);
 }
 
 int sd_sim3_optimize_host(int n_problems, const int32_t* corr_offset, const sd_sim3_opt_corr* corr, const sd_sim3_opt_problem* problems,

@@ -36,6 +36,45 @@ def same_bits(a, b):
     return all(np.array_equal(a[f].view(np.uint8), b[f].view(np.uint8)) for f in FIELDS) and a["stats"].tobytes() == b["stats"].tobytes()
 
 
+def test_problem_ring_and_workspace_over_many_launches_on_two_streams(gpu, fe):
+    """sd_local_ba_device on the schedule of solver_ring.py: every output byte of every call equals the problem run alone through the host
+    form, and the Tcw rows of fixed cameras, which no call writes, keep their sentinel."""
+    import torch
+    import solver_ring as sr
+    pool = [bc.problem_of(bc.make_scene(400 + k, 1 + k % 3, 2, 6 + k, stereo_frac=0.6)) for k in range(16)]
+    calls = sr.schedule(pool, lambda q: len(q["edges"]))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    dp = lambda t: C.c_void_p(t.data_ptr())
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()
+
+    def prepare(prs):
+        ko, nl, po, eo, kfs, xw, ed, ref = fe.pack_ba_problems(prs)
+        outs = [torch.full((n,), 0x5A, dtype=torch.uint8, device="cuda")
+                for n in (len(kfs) * 64, len(xw) * 12, len(xw) * 12, len(xw) * 4, len(ed), len(ed), len(prs) * 48)]
+        return dict(prs=prs, tabs=(ko, nl, po, eo), ins=[dev(kfs), dev(xw), dev(ed), dev(ref)], outs=outs)
+
+    def enqueue(a, stream):
+        rc = fe.lib().sd_local_ba_device(len(a["prs"]), *[p(t) for t in a["tabs"]], *[dp(t) for t in a["ins"]], *[dp(o) for o in a["outs"]],
+                                         C.c_void_p(stream))
+        assert rc == 0, fe.lib().sd_last_error()
+
+    done = sr.drive(calls, prepare, enqueue)
+    alone = {}
+    for k, a in enumerate(done):
+        ko, nl, po, eo = a["tabs"]
+        T, xo, nrm, dist, l1, er, st = [o.cpu().numpy() for o in a["outs"]]
+        T = T.reshape(-1, 64)
+        for q, pr in enumerate(a["prs"]):
+            if id(pr) not in alone:
+                alone[id(pr)] = fe.local_bundle_adjustment([pr])[0]
+            w = alone[id(pr)]
+            got = dict(Tcw=T[ko[q]:ko[q] + nl[q]], xw=xo[12 * po[q]:12 * po[q + 1]], normal=nrm[12 * po[q]:12 * po[q + 1]],
+                       dist=dist[4 * po[q]:4 * po[q + 1]], level1=l1[eo[q]:eo[q + 1]], erase=er[eo[q]:eo[q + 1]], stats=st[48 * q:48 * q + 48])
+            for f in FIELDS + ("stats",):
+                assert got[f].tobytes() == w[f].tobytes(), (k, q, f)
+            assert (T[ko[q] + nl[q]:ko[q + 1]] == 0x5A).all(), (k, q)
+
+
 @pytest.mark.parametrize("name", NAMES)
 def test_case_matches_oracle(together, recorded, name):
     got, want = together[name], bc.expected(name)

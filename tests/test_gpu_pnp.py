@@ -51,6 +51,40 @@ def oracle_results():
     return {pr["name"]: (pc.iterate(pr, order=0), pc.iterate(pr, order=1)) for pr in pc.ransac_cases()}
 
 
+def test_problem_ring_and_workspace_over_many_launches_on_two_streams(gpu, fe):
+    """sd_pnp_ransac_device on the schedule of solver_ring.py: every output byte of every call equals the problem run alone through the
+    host form.  8 .. 53 correspondences: below and above min_inliers = 10."""
+    import ctypes as C
+    import torch
+    import solver_ring as sr
+    pool = [pc.make_problem(300 + k, n, outliers=0.3, noise=0.2, name="ring_%d" % n) for k, n in enumerate(range(8, 56, 3))]
+    calls = sr.schedule(pool, lambda pr: len(pr["corr"]))
+    D = pc.DEFAULTS
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    dp = lambda t: C.c_void_p(t.data_ptr())
+
+    def prepare(prs):
+        off, corr, probs = pc.pack(prs)
+        return dict(prs=prs, off=off, probs=probs, corr=torch.from_numpy(corr.view(np.uint8).reshape(-1).copy()).cuda(),
+                    res=torch.full((len(prs) * pc.RESULT_DTYPE.itemsize,), 0x5A, dtype=torch.uint8, device="cuda"),
+                    inl=torch.full((len(corr),), 0x5A, dtype=torch.uint8, device="cuda"))
+
+    def enqueue(a, stream):
+        fe.check(fe.lib().sd_pnp_ransac_device(len(a["prs"]), p(a["off"]), dp(a["corr"]), p(a["probs"]), D["probability"], D["min_inliers"],
+                                               D["max_iterations"], D["min_set"], D["epsilon"], D["th2"], dp(a["res"]), dp(a["inl"]), None, None, 0,
+                                               C.c_void_p(stream)))
+
+    done = sr.drive(calls, prepare, enqueue)
+    alone = {}
+    for k, a in enumerate(done):
+        res = a["res"].cpu().numpy().view(pc.RESULT_DTYPE); inl = a["inl"].cpu().numpy(); off = a["off"]
+        for q, pr in enumerate(a["prs"]):
+            if pr["name"] not in alone:
+                alone[pr["name"]] = fe.pnp_ransac(*pc.pack([pr]), **D)
+            r, i = alone[pr["name"]]
+            assert res[q].tobytes() == r[0].tobytes() and inl[off[q]:off[q + 1]].tobytes() == i.tobytes(), (k, q, pr["name"])
+
+
 def test_ransac_stage_gives_the_sequential_oracles_bytes(device_results, oracle_results):
     by, _ = device_results
     assert len(by) == len(pc.ransac_cases())

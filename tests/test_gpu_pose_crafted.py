@@ -12,7 +12,7 @@ import pose_crafted as pcr
 
 pytestmark = pytest.mark.gpu
 
-CAM_RING = 8              # SD_POSE_CAM_RING (csrc/sd_api.hip)
+CAM_RING = 8              # SD_SOLVER_RING (csrc/sd_api.hip)
 
 
 def _pack(names):
@@ -73,7 +73,7 @@ def test_alone_twice_and_reversed_give_the_same_bytes(batch, fe):
 
 
 def test_camera_ring_over_many_launches(batch, fe):
-    """2 * SD_POSE_CAM_RING + 1 launches back to back: every table of the ring is reused twice, and regrown when a later launch has
+    """2 * SD_SOLVER_RING + 1 launches back to back: every table of the ring is reused twice, and regrown when a later launch has
     more problems than the one that last used it.  Successive launches take successive cases, so their cameras differ."""
     names = pcr.names()
     counts = [1, 3, 2, 40, 5, 1, 7, 2, 33, 4, 1, 50, 2, 9, 1, 64, 3]

@@ -85,7 +85,8 @@ def chain(gpu, fe, synth):
         ws.b.relocalize_pnp([fr[q] for q in rev], [kf[q] for q in rev], probs[rev], d_bow2.data_ptr(), d_kfp2.data_ptr(), d_pts.data_ptr(), d_desc.data_ptr(),
                             rc.CAM, n_points=len(pts), **pc.DEFAULTS)
         got_rev = [ws.b.download_reloc_pnp(q) for q in range(n)][::-1]
-        yield dict(ws=ws, sc=sc, jobs=jobs, names=names, pts=pts, bow=bow, probs=probs, got=got, ref=ref, rev=got_rev, bad=(bad_job, bad_i))
+        yield dict(ws=ws, sc=sc, jobs=jobs, names=names, pts=pts, bow=bow, probs=probs, got=got, ref=ref, rev=got_rev, bad=(bad_job, bad_i),
+                   slots=(fr, kf), dev=dict(pts=d_pts, desc=d_desc, kfp=d_kfp, bow=d_bow))
     finally:
         ws.close()
 
@@ -172,3 +173,38 @@ def test_refusals(chain, fe):
     assert code(problems=late) == fe.SD_ERR_INVALID
     with pytest.raises(fe.SdError):
         ws.b.relocalize_pnp([0], [1], probs, 0, 1, 1, 1, rc.CAM, n_points=1, **pc.DEFAULTS)                  # no BoW row
+
+
+def test_ransac_and_the_chain_share_one_workspace_across_streams(chain, fe):
+    """sd_pnp_ransac_device on one side stream, the chain on another, the same sd_pnp_ransac_device call again on the first: the PnP
+    workspace of the device serves all three with no synchronisation until the end, and each gives what it gives alone."""
+    import ctypes as C
+    import torch
+    ws, got, D = chain["ws"], chain["got"], pc.DEFAULTS
+    prs = [dict(corr=g["corr"], prob=chain["probs"][q:q + 1]) for q, g in enumerate(got)]      # the chain's own gathered problems
+    off, corr, probs = pc.pack(prs)
+    want_res, want_inl = fe.pnp_ransac(off, corr, probs, **D)
+    d_c = torch.from_numpy(corr.view(np.uint8).reshape(-1).copy()).cuda()
+    outs = [(torch.full((len(prs) * pc.RESULT_DTYPE.itemsize,), 0x5A, dtype=torch.uint8, device="cuda"),
+             torch.full((len(corr),), 0x5A, dtype=torch.uint8, device="cuda")) for _ in range(2)]
+    a, b = torch.cuda.Stream(), torch.cuda.Stream()
+    p = lambda x: x.ctypes.data_as(C.c_void_p)
+    dp = lambda t: C.c_void_p(t.data_ptr())
+
+    def ransac(d_r, d_i):
+        fe.check(fe.lib().sd_pnp_ransac_device(len(prs), p(off), dp(d_c), p(probs), D["probability"], D["min_inliers"], D["max_iterations"], D["min_set"],
+                                               D["epsilon"], D["th2"], dp(d_r), dp(d_i), None, None, 0, C.c_void_p(a.cuda_stream)))
+
+    dev, (fr, kf) = chain["dev"], chain["slots"]
+    torch.cuda.synchronize()
+    ransac(*outs[0])
+    ws.b.relocalize_pnp(fr, kf, chain["probs"], dev["bow"].data_ptr(), dev["kfp"].data_ptr(), dev["pts"].data_ptr(), dev["desc"].data_ptr(), rc.CAM,
+                        stream=b.cuda_stream, n_points=len(chain["pts"]), **D)
+    ransac(*outs[1])
+    a.synchronize(); b.synchronize()
+    for d_r, d_i in outs:
+        assert d_r.cpu().numpy().tobytes() == want_res.tobytes() and d_i.cpu().numpy().tobytes() == want_inl.tobytes()
+    for q, g in enumerate(got):
+        again = ws.b.download_reloc_pnp(q)
+        for k in g:
+            assert np.asarray(again[k]).tobytes() == np.asarray(g[k]).tobytes(), (chain["names"][q], k)

@@ -39,6 +39,38 @@ def device_results(gpu, fe):
     return by, calls
 
 
+def test_problem_ring_and_workspace_over_many_launches_on_two_streams(gpu, fe):
+    """sd_sim3_ransac_device on the schedule of solver_ring.py: every output byte of every call equals the problem run alone through the
+    host form.  12 .. 57 correspondences: below and above min_inliers = 20."""
+    import ctypes as C
+    import torch
+    import solver_ring as sr
+    pool = [sc.make_problem(40 + k, n, outliers=0.3, noise=0.002) for k, n in enumerate(range(12, 60, 3))]
+    calls = sr.schedule(pool, lambda pr: len(pr["corr"]))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    dp = lambda t: C.c_void_p(t.data_ptr())
+
+    def prepare(prs):
+        off, corr, probs = sc.pack(prs)
+        return dict(prs=prs, off=off, probs=probs, corr=torch.from_numpy(corr.view(np.uint8).reshape(-1).copy()).cuda(),
+                    res=torch.full((len(prs) * sc.RESULT_DTYPE.itemsize,), 0x5A, dtype=torch.uint8, device="cuda"),
+                    inl=torch.full((len(corr),), 0x5A, dtype=torch.uint8, device="cuda"))
+
+    def enqueue(a, stream):
+        fe.check(fe.lib().sd_sim3_ransac_device(len(a["prs"]), p(a["off"]), dp(a["corr"]), p(a["probs"]), 0.99, 20, 300, dp(a["res"]), dp(a["inl"]),
+                                                None, C.c_void_p(stream)))
+
+    done = sr.drive(calls, prepare, enqueue)
+    alone = {}
+    for k, a in enumerate(done):
+        res = a["res"].cpu().numpy().view(sc.RESULT_DTYPE); inl = a["inl"].cpu().numpy(); off = a["off"]
+        for q, pr in enumerate(a["prs"]):
+            if id(pr) not in alone:
+                alone[id(pr)] = fe.sim3_ransac(*sc.pack([pr]), 0.99, 20, 300)
+            r, i = alone[id(pr)]
+            assert res[q].tobytes() == r[0].tobytes() and inl[off[q]:off[q + 1]].tobytes() == i.tobytes(), (k, q)
+
+
 def test_every_crafted_problem_gives_the_oracles_bytes(device_results):
     by, _ = device_results
     bad = []

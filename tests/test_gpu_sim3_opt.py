@@ -37,6 +37,37 @@ def same_record(a, b):
     return all(np.array_equal(np.asarray(a[f]), np.asarray(b[f]), equal_nan=np.asarray(a[f]).dtype.kind == "f") for f in sc.RESULT_DTYPE.names)
 
 
+def test_problem_ring_over_many_launches_on_two_streams(gpu, fe):
+    """sd_sim3_optimize_device on the schedule of solver_ring.py (this solver has a ring and no workspace): every output byte of every
+    call equals the problem run alone through the host form.  5 .. 50 correspondences: below and above the `< 10` return."""
+    import ctypes as C
+    import torch
+    import solver_ring as sr
+    pool = [sc.scene("ring_%d" % n, n, 50 + k, outliers=n // 8) for k, n in enumerate(range(5, 53, 3))]
+    calls = sr.schedule(pool, lambda c: len(c["corr"]))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    dp = lambda t: C.c_void_p(t.data_ptr())
+
+    def prepare(cs):
+        off, corr, probs = sc.pack(cs)
+        return dict(cs=cs, off=off, probs=probs, corr=torch.from_numpy(corr.view(np.uint8).reshape(-1).copy()).cuda(),
+                    res=torch.full((len(cs) * sc.RESULT_DTYPE.itemsize,), 0x5A, dtype=torch.uint8, device="cuda"),
+                    st=torch.full((len(corr),), 0x5A, dtype=torch.uint8, device="cuda"))
+
+    def enqueue(a, stream):
+        fe.check(fe.lib().sd_sim3_optimize_device(len(a["cs"]), p(a["off"]), dp(a["corr"]), p(a["probs"]), dp(a["res"]), dp(a["st"]), C.c_void_p(stream)))
+
+    done = sr.drive(calls, prepare, enqueue)
+    alone = {}
+    for k, a in enumerate(done):
+        res = a["res"].cpu().numpy().view(sc.RESULT_DTYPE); st = a["st"].cpu().numpy(); off = a["off"]
+        for q, c in enumerate(a["cs"]):
+            if c["name"] not in alone:
+                alone[c["name"]] = fe.sim3_optimize(*sc.pack([c]))
+            r, s = alone[c["name"]]
+            assert res[q].tobytes() == r[0].tobytes() and st[off[q]:off[q + 1]].tobytes() == s.tobytes(), (k, q, c["name"])
+
+
 def test_every_crafted_problem_equals_the_oracle_in_the_kernels_order(device_results, cases):
     res, st, off = device_results
     for k, c in enumerate(cases):
