@@ -21,7 +21,10 @@ STATS_DTYPE = np.dtype([("iterations", "<i4", (2,)), ("trials", "<i4", (2,)), ("
                         ("n_erased", "<i4"), ("chi2", "<f8", (2,))])                                   # sd_ba_stats, 48 bytes
 BRANCHES = ["mono_edge", "stereo_edge", "fixed_local", "edge_to_fixed", "single_mono", "level1_chi2", "level1_depth", "point_inactive",
             "kf_inactive", "rejected", "stop_nbad", "stop_terminate", "noop", "huber", "pose_pose", "factor_fail", "erase_chi2",
-            "erase_depth", "round2_empty", "fixed_plus_one_local", "no_pose", "duplicate_edge"]
+            "erase_depth", "round2_empty", "fixed_plus_one_local", "no_pose", "duplicate_edge", "last_rejected_r1", "last_rejected_r2",
+            "level1_point_active", "stereo_between", "quat_tr", "quat_i0", "quat_i1", "quat_i2"]
+# flags of the oracle: the deliberately wrong twins (T_* of ba_oracle.cpp); tests/ba_crafted.py names the case each must differ on
+TWINS = dict(f32_compare=1, no_depth_test=2, fresh_chi2=4, level1_active=8, lambda_carried=16, delta_swapped=32)
 MARGINS = ["chi2", "depth", "rho", "stop"]
 MARGIN = 1e-6
 CHOL_TILE = 48          # SD_BA_NB of k_ba.h: rows of the reduced camera system factorised per LDS tile
@@ -47,7 +50,7 @@ def oracle(contract="off"):
         vp, i = C.c_void_p, C.c_int
         L.sd_ba_oracle_branches.restype = C.POINTER(C.c_int64)
         L.sd_ba_oracle_round1_points.argtypes = [vp, i]
-        L.sd_ba_oracle.argtypes = [i, i, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.sd_ba_oracle.argtypes = [i, i, vp, i, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp]
         assert L.sd_ba_oracle_branch_count() == len(BRANCHES)
         _oracles[contract] = L
     return _oracles[contract]
@@ -65,10 +68,11 @@ def problem_of(scene):
     return {k: scene[k] for k in ("kfs", "n_local", "xw", "edges", "ref_kf")}
 
 
-def run_oracle(prob, contract="off", reverse=False):
+def run_oracle(prob, contract="off", reverse=False, twin=None):
     """One problem through the oracle.  reverse = the same edges in reversed insertion order (per-edge outputs come back in the
-    caller's order).  Returns dict(Tcw (n_local, 4, 4), xw, normal, dist, level1, erase, stats (STATS_DTYPE scalar), margins {name: v},
-    branches {name: count})."""
+    caller's order).  twin = a name of TWINS: the deliberately wrong variant.  Returns dict(Tcw (n_local, 4, 4), xw, normal, dist,
+    level1, erase, stats (STATS_DTYPE scalar), margins {name: v}, branches {name: count}, round1_xw, cached (2, E): every edge's cached
+    chi2 as the first and the second classification read it).  Nothing of `prob` is modified."""
     L = oracle(contract)
     kfs = np.ascontiguousarray(prob["kfs"], KF_DTYPE); xw = np.ascontiguousarray(prob["xw"], F32).reshape(-1, 3)
     e = np.ascontiguousarray(prob["edges"], EDGE_DTYPE); ref = np.ascontiguousarray(prob["ref_kf"], np.int32)
@@ -77,23 +81,24 @@ def run_oracle(prob, contract="off", reverse=False):
     nl, nk, npt, ne = int(prob["n_local"]), len(kfs), len(xw), len(e)
     T = np.zeros((max(nl, 1), 16), F32); xo = np.zeros((max(npt, 1), 3), F32); nrm = np.zeros((max(npt, 1), 3), F32)
     dist = np.zeros(max(npt, 1), F32); l1 = np.zeros(max(ne, 1), np.uint8); er = np.zeros(max(ne, 1), np.uint8)
-    st = np.zeros(1, STATS_DTYPE); mg = np.zeros(4, np.float64)
+    st = np.zeros(1, STATS_DTYPE); mg = np.zeros(4, np.float64); cached = np.zeros((2, max(ne, 1)), np.float64)
     branches(L, reset=True)
-    rc = L.sd_ba_oracle(nk, nl, _p(kfs), npt, _p(xw), ne, _p(e), _p(ref), _p(T), _p(xo), _p(nrm), _p(dist), _p(l1), _p(er), _p(st), _p(mg))
+    rc = L.sd_ba_oracle(nk, nl, _p(kfs), npt, _p(xw), ne, _p(e), _p(ref), _p(T), _p(xo), _p(nrm), _p(dist), _p(l1), _p(er), _p(st), _p(mg),
+                        TWINS[twin] if twin else 0, _p(cached))
     assert rc == 0, rc
     r1 = np.zeros(max(3 * npt, 1), np.float64)
     r1 = r1[:L.sd_ba_oracle_round1_points(_p(r1), 3 * npt)].reshape(-1, 3)
-    l1, er = l1[:ne], er[:ne]
+    l1, er, cached = l1[:ne], er[:ne], cached[:, :ne]
     if reverse:
-        l1, er = l1[::-1].copy(), er[::-1].copy()
+        l1, er, cached = l1[::-1].copy(), er[::-1].copy(), cached[:, ::-1].copy()
     return dict(Tcw=T[:nl].reshape(nl, 4, 4), xw=xo[:npt], normal=nrm[:npt], dist=dist[:npt], level1=l1, erase=er, stats=st[0],
-                margins=dict(zip(MARGINS, mg.tolist())), branches=branches(L), round1_xw=r1)
+                margins=dict(zip(MARGINS, mg.tolist())), branches=branches(L), round1_xw=r1, cached=cached)
 
 
 def run_oracle_plain(prob):
     """run_oracle without the branch counters (they are process-wide): the form tools/bench_ba.py calls from several threads."""
     r = run_oracle(prob)
-    r.pop("branches"); r.pop("round1_xw")
+    r.pop("branches"); r.pop("round1_xw"); r.pop("cached")
     return r
 
 

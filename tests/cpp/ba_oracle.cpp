@@ -23,8 +23,20 @@ static_assert(sizeof(KF) == 88 && sizeof(Edge) == 32 && sizeof(Stats) == 48, "re
 
 enum { B_MONO, B_STEREO, B_FIXED_LOCAL, B_EDGE_TO_FIXED, B_SINGLE_MONO, B_LEVEL1_CHI2, B_LEVEL1_DEPTH, B_POINT_INACTIVE, B_KF_INACTIVE,
        B_REJECTED, B_STOP_NBAD, B_STOP_TERMINATE, B_NOOP, B_HUBER, B_POSE_POSE, B_FACTOR_FAIL, B_ERASE_CHI2, B_ERASE_DEPTH, B_ROUND2_EMPTY,
-       B_FIXED_PLUS_ONE_LOCAL, B_NO_POSE, B_DUPLICATE, B_COUNT };
+       B_FIXED_PLUS_ONE_LOCAL, B_NO_POSE, B_DUPLICATE,
+       // info slots of the crafted cases (tests/ba_crafted.py): the last LM trial of round 1 / 2 was rejected; level-1 edges whose point
+       // stays active in round 2; stereo edges linearised in round 1 with 5.991 < chi2 <= 7.815; Quaterniond(Matrix3d) branches taken
+       B_LAST_REJECTED_R1, B_LAST_REJECTED_R2, B_LEVEL1_POINT_ACTIVE, B_STEREO_BETWEEN, B_QUAT_TR, B_QUAT_I0, B_QUAT_I1, B_QUAT_I2, B_COUNT };
 int64_t g_branch[B_COUNT];
+// The deliberately wrong twins (`flags` of sd_ba_oracle; 0 = the oracle).  Each makes one mistake a restatement of Optimizer.cc:453-778
+// could make; tests/test_ba_crafted.py shows that each differs from the oracle on the crafted case named for it.
+enum { T_F32_COMPARE = 1,       // classification as PoseOptimization does it: (float)chi2 > (float)bound
+       T_NO_DEPTH_TEST = 2,     // drops !isDepthPositive()
+       T_FRESH_CHI2 = 4,        // recomputes every edge's error at the current estimates before each classification
+       T_LEVEL1_ACTIVE = 8,     // round 2 runs over all edges
+       T_LAMBDA_CARRIED = 16,   // round 2 starts from round 1's lambda, nu and stop counter
+       T_DELTA_SWAPPED = 32 };  // stereo edges get the mono Huber delta
+int g_flags = 0;
 std::vector<double> g_round1_points;                      // the point estimates of the last call when round 1 ended (test hook)
 
 struct Quat { double x, y, z, w; };
@@ -42,6 +54,7 @@ Quat q_from_matrix(const double m[3][3])
     double c[3];
     const double tr = m[0][0] + m[1][1] + m[2][2];
     if (tr > 0) {
+        g_branch[B_QUAT_TR]++;
         double t = std::sqrt(tr + 1.0);
         q.w = 0.5 * t;
         t = 0.5 / t;
@@ -52,6 +65,7 @@ Quat q_from_matrix(const double m[3][3])
     if (m[1][1] > m[0][0]) i = 1;
     if (m[2][2] > m[i][i]) i = 2;
     const int j = (i + 1) % 3, k = (j + 1) % 3;
+    g_branch[B_QUAT_I0 + i]++;
     double t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
     c[i] = 0.5 * t;
     t = 0.5 / t;
@@ -149,6 +163,7 @@ struct Graph {
     std::vector<uint8_t> level;                            // per edge
     std::vector<double> chi2c;                             // the edges' cached chi2 (error of the last computeActiveErrors that saw them)
     bool robust;
+    double lambda; int ni, nBad;                           // LM state at the end of the last optimize() (read by T_LAMBDA_CARRIED only)
     // per round
     std::vector<int> poseIdx, ptIdx;                       // index in Hpp / Hll, -1 when fixed or inactive
     int nPose, nLm;
@@ -218,6 +233,7 @@ void edge_jacobians(const Graph& G, const Edge& e, int D, double A[3][3], double
 }
 
 const double kDeltaMono = (double)(float)std::sqrt(5.991), kDeltaStereo = (double)(float)std::sqrt(7.815);
+double delta_of(int D) { return D == 2 || (g_flags & T_DELTA_SWAPPED) ? kDeltaMono : kDeltaStereo; }
 
 // computeActiveErrors + activeRobustChi2
 double active_chi(Graph& G)
@@ -230,7 +246,7 @@ double active_chi(Graph& G)
         const double c2 = chi2_of(r, D, (double)G.E[i].inv_sigma2);
         G.chi2c[i] = c2;
         if (G.robust) {
-            const double d = D == 2 ? kDeltaMono : kDeltaStereo, dsqr = d * d;
+            const double d = delta_of(D), dsqr = d * d;
             chi += c2 <= dsqr ? c2 : 2 * std::sqrt(c2) * d - dsqr;
         } else chi += c2;
     }
@@ -257,7 +273,8 @@ void build_system(Graph& G, System& Y)
         const double w = (double)e.inv_sigma2;
         double rho1 = 1.0;
         if (G.robust) {
-            const double c2 = chi2_of(r, D, w), d = D == 2 ? kDeltaMono : kDeltaStereo, dsqr = d * d;
+            const double c2 = chi2_of(r, D, w), d = delta_of(D), dsqr = d * d;
+            if (D == 3 && c2 > 5.991 && c2 <= 7.815) g_branch[B_STEREO_BETWEEN]++;
             if (!(c2 <= dsqr)) { rho1 = d / std::sqrt(c2); g_branch[B_HUBER]++; }
         }
         const double wo = G.robust ? rho1 * w : w;
@@ -408,15 +425,17 @@ void optimize(Graph& G, int maxIt, int round, Stats& st, Margins& mg)
     const int n6 = 6 * G.nPose, nx = n6 + 3 * G.nLm;
     std::vector<double> x(nx, 0.0), xs(nx);
     System Y;
-    double lambda = 0;
-    int ni = 2, nBad = 0;
+    const bool carried = (g_flags & T_LAMBDA_CARRIED) && round == 1;
+    double lambda = carried ? G.lambda : 0;
+    int ni = carried ? G.ni : 2, nBad = carried ? G.nBad : 0;
     double currentChi = 0;
+    bool lastRejected = false;
     for (int it = 0; it < maxIt; it++) {
         st.iterations[round]++;
         currentChi = active_chi(G);
         const double iniChi = currentChi;
         build_system(G, Y);
-        if (it == 0) {
+        if (it == 0 && !carried) {
             double md = 0;
             for (int p = 0; p < G.nPose; p++) for (int j = 0; j < 6; j++) md = std::max(std::fabs(Y.Hpp[(size_t)p * 36 + j * 7]), md);
             for (int l = 0; l < G.nLm; l++) for (int j = 0; j < 3; j++) md = std::max(std::fabs(Y.Hll[(size_t)l * 9 + j * 4]), md);
@@ -447,12 +466,14 @@ void optimize(Graph& G, int maxIt, int round, Stats& st, Margins& mg)
                 lambda *= std::max(1. / 3., alpha);
                 ni = 2;
                 currentChi = tempChi;
+                lastRejected = false;
             } else {
                 lambda *= ni;
                 ni *= 2;
                 G.pose = poseBackup; G.X = XBackup;
                 st.rejected[round]++;
                 g_branch[B_REJECTED]++;
+                lastRejected = true;
             }
             qmax++;
         } while (rho < 0 && qmax < 10);
@@ -462,6 +483,18 @@ void optimize(Graph& G, int maxIt, int round, Stats& st, Margins& mg)
         if (nBad >= 3) { g_branch[B_STOP_NBAD]++; break; }
     }
     st.chi2[round] = currentChi;
+    G.lambda = lambda; G.ni = ni; G.nBad = nBad;
+    if (lastRejected) g_branch[B_LAST_REJECTED_R1 + round]++;
+}
+
+// T_FRESH_CHI2: the error of every edge at the current estimates, whatever its level
+void refresh_chi2(Graph& G)
+{
+    for (int i = 0; i < G.nE; i++) {
+        double r[3], p[3];
+        const int D = edge_error(G, G.E[i], r, p);
+        G.chi2c[i] = chi2_of(r, D, (double)G.E[i].inv_sigma2);
+    }
 }
 
 // chi2() > bound || !isDepthPositive(): chi2 from the edge's cached error, the depth from the current estimates
@@ -473,7 +506,8 @@ bool classify(const Graph& G, int i, Margins& mg, int chiBranch, int depthBranch
     const double bound = e.ur < 0 ? 5.991 : 7.815;
     margin_min(mg.chi2, std::fabs(G.chi2c[i] - bound) / bound);
     margin_min(mg.depth, std::fabs(p[2]) / std::max(std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]), DBL_MIN));
-    const bool c = G.chi2c[i] > bound, dneg = !(p[2] > 0.0);
+    const bool c = (g_flags & T_F32_COMPARE) ? (float)G.chi2c[i] > (float)bound : G.chi2c[i] > bound;
+    const bool dneg = (g_flags & T_NO_DEPTH_TEST) ? false : !(p[2] > 0.0);
     if (c) g_branch[chiBranch]++;
     if (dneg) g_branch[depthBranch]++;
     return c || dneg;
@@ -495,12 +529,15 @@ extern "C" void sd_ba_oracle_reset_branches() { std::memset(g_branch, 0, sizeof 
 // One problem.  kfs [n_kf] (the first n_local are the local keyframes), xw [n_pt][3], edges [n_e] in insertion order, ref_kf [n_pt]
 // (-1 = skip).  Out: Tcw [n_local][16], xw_out [n_pt][3], normal [n_pt][3], dist [n_pt], level1 / erase [n_e], stats, margins [4] =
 // the smallest relative distance of a decision from its threshold (chi2 bound, depth over range, |rho|, stop rule).
-// Returns 0, or -1 for an index out of range.
+// flags: 0 = the oracle, else a sum of the T_* twins.  cached (may be null) [2][n_e]: every edge's cached chi2 as the first and the
+// second classification read it.  Returns 0, or -1 for an index out of range.
 extern "C" int sd_ba_oracle(int n_kf, int n_local, const void* kfs, int n_pt, const float* xw, int n_e, const void* edges,
                             const int32_t* ref_kf, float* Tcw, float* xw_out, float* normal, float* dist, uint8_t* level1, uint8_t* erase,
-                            void* stats, double* margins)
+                            void* stats, double* margins, int flags, double* cached)
 {
     Graph G;
+    g_flags = flags;
+    G.lambda = 0; G.ni = 2; G.nBad = 0;
     G.nKF = n_kf; G.nLocal = n_local; G.nPt = n_pt; G.nE = n_e;
     G.kf = (const KF*)kfs; G.E = (const Edge*)edges;
     for (int i = 0; i < n_e; i++) if (G.E[i].kf < 0 || G.E[i].kf >= n_kf || G.E[i].point < 0 || G.E[i].point >= n_pt) return -1;
@@ -533,13 +570,23 @@ extern "C" int sd_ba_oracle(int n_kf, int n_local, const void* kfs, int n_pt, co
     if (noop) g_branch[B_NOOP]++;
     if (!noop) {
         optimize(G, 5, 0, st, mg);
+        if (flags & T_FRESH_CHI2) refresh_chi2(G);
+        if (cached) for (int i = 0; i < n_e; i++) cached[i] = G.chi2c[i];
         for (int i = 0; i < n_e; i++) {
-            if (classify(G, i, mg, B_LEVEL1_CHI2, B_LEVEL1_DEPTH)) { G.level[i] = 1; st.n_level1++; }
-            level1[i] = G.level[i];
+            level1[i] = 0;
+            if (classify(G, i, mg, B_LEVEL1_CHI2, B_LEVEL1_DEPTH)) { level1[i] = 1; st.n_level1++; }
+            if (!(flags & T_LEVEL1_ACTIVE)) G.level[i] = level1[i];
+        }
+        {
+            std::vector<int> left(n_pt, 0);
+            for (int i = 0; i < n_e; i++) if (!G.level[i]) left[G.E[i].point]++;
+            for (int i = 0; i < n_e; i++) if (G.level[i] && left[G.E[i].point]) g_branch[B_LEVEL1_POINT_ACTIVE]++;
         }
         g_round1_points = G.X;
         G.robust = false;
         optimize(G, 10, 1, st, mg);
+        if (flags & T_FRESH_CHI2) refresh_chi2(G);
+        if (cached) for (int i = 0; i < n_e; i++) cached[n_e + i] = G.chi2c[i];
         for (int i = 0; i < n_e; i++) { erase[i] = classify(G, i, mg, B_ERASE_CHI2, B_ERASE_DEPTH); st.n_erased += erase[i]; }
     }
     // outputs
